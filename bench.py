@@ -13,10 +13,16 @@ than one rank — one RCCL all-reduce of [flat gradient || loss sum].
 points (north_star: ">= 6x strong scaling at 8 GPUs"), sampled identically on every rank and split by
 `pinnrl_amd.distributed.shard_bounds`; `value` is then global points/s.
 
-Besides the timed region the N = 1 line carries (all outside the timed region): the CPU oracle on the same points
-(`cpu_baseline`, all host threads and one thread), the 4 900-point figure north_star quotes its >= 10x target on,
-the second half of the metric — `training.final_residual_l2` after a fixed 200-step Adam schedule on the GPU and on
-the CPU from identical theta_0 and batches — and the per-kernel figures of the other BASELINE configurations.
+A plain run sets up, warms up, times --steps steps and prints the result line (+ --dump-outputs).  With --full the
+line also carries (all outside the timed region): the sustained-clock figure, and for N = 1 the CPU oracle on the same
+points (`cpu_baseline`, all host threads and one thread), the 4 900-point figure north_star quotes its >= 10x target
+on, the second half of the metric — `training.final_residual_l2` after a fixed 200-step Adam schedule on the GPU and
+on the CPU from identical theta_0 and batches — and the per-kernel figures of the other BASELINE configurations; for
+N > 1 the 10^6-point strong-scaling figure and BASELINE configs[3]/[4] in their sharded form.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the step receives it: DIR/grad.npy (the
+gradient of the trainable tensors in parameter order, float32, 41 473 values) and DIR/loss_sum.npy (sum of r^2 over the points, float32).  Inputs (theta_0,
+collocation points) are seeded, so two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -312,11 +318,16 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--spinup", type=int, default=0, help="extra untimed launches before the warm-up steps (experiments; "
                     "the sustained-clock figure is reported separately as `sustained`)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline figure (sustained "
+                    "clock, CPU baseline, parity, training schedule, secondary / sharded configurations, strong scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the final-residual-L2 schedule")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C1/C3/C4/C5 figures")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline, parity and training legs")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the final-residual-L2 schedule")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the C1/C3/C4/C5 figures")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -391,9 +402,16 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax)
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
+    if args.dump_outputs and rank == 0:  # before any later launch reuses buf
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        grad = torch.cat([g.flatten() for g in E.split_flat_grad(prog, flat) if g is not None])  # trainable, unpadded
+        np.save(os.path.join(args.dump_outputs, "grad.npy"), grad.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "loss_sum.npy"), loss_sum.cpu().numpy().astype(np.float32))
     # sustained-clock figure, outside the timed region: 100 more launches, then 50 timed ones
     sustained = None
-    if world == 1:
+    if world == 1 and args.full:
         for _ in range(100):
             step()
         torch.cuda.synchronize()
@@ -408,7 +426,7 @@ def main():
     # north_star's ">= 6x strong scaling at 8 GPUs": beside the weak-scaling `value`, every N > 1 run also times ONE global
     # 10^6-point batch split over the ranks by shard_bounds (+ the all-reduce) against the same batch on rank 0 alone
     strong_fig = None
-    if world > 1:
+    if world > 1 and args.full:
         torch.manual_seed(7)  # identical on every rank
         xs, ts_ = pde.generate_collocation_points(1000000, strategy="uniform")
         ns = xs.shape[0]
@@ -442,7 +460,7 @@ def main():
         del xs, ts_
 
     sharded = None
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.full and not args.no_secondary:
         sharded = sharded_configs(E, D, dist, dev, rank, world)
 
     if rank == 0:
@@ -491,7 +509,7 @@ def main():
         }
         if rehearsal:
             out["config"]["rehearsal"] = "all ranks on cuda:0 over gloo - code-path check, not a measurement"
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             import oracle as O  # checker and CPU baseline only; never inside the timed region
 
             pspec = O.PdeSpec(name="burgers", parameters={"nu": 0.01 / math.pi})
@@ -525,7 +543,7 @@ def main():
                                 "note": "154 tiles on 256 CUs: launch- and occupancy-bound, see DESIGN.md"}
             if not args.no_train:
                 out["training"] = training_parity(dev, O, pspec, aspec)
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             out["secondary"] = secondary_configs(E)
         print(json.dumps(out))
     if world > 1:

@@ -422,7 +422,7 @@ def test_bench_multi_rank_rehearsal(scaling, dev):
     env = dict(os.environ, PINN_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29600 + os.getpid() % 300), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--scaling", scaling, "--points", "20000"]
+           "--warmup", "1", "--scaling", scaling, "--points", "20000", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]

@@ -13,7 +13,7 @@ run() { d=$1; shift; timeout -k 10 240 rocprofv3 "$@" > "$OUT/$d.log" 2>&1; }
 # headline command
 python3 $REPO/bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err" || exit 1
 run bench_kt --kernel-trace --stats --output-format csv -d "$OUT/bench/kt" -- $B --steps 200 || exit 1
-run bench_full --kernel-trace --stats --output-format csv -d "$OUT/bench/kt_full" -- python3 $REPO/bench.py --no-cpu --steps 200 || exit 1
+run bench_full --kernel-trace --stats --output-format csv -d "$OUT/bench/kt_full" -- python3 $REPO/bench.py --full --no-cpu --steps 200 || exit 1
 run bench_fetch --pmc FETCH_SIZE --output-format csv -d "$OUT/bench/pmc_fetch" -- $B --steps 30 || exit 1
 run bench_write --pmc WRITE_SIZE --output-format csv -d "$OUT/bench/pmc_write" -- $B --steps 30 || exit 1
 run bench_sq1 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d "$OUT/bench/pmc_sq1" -- $B --steps 30 || exit 1
