@@ -11,6 +11,9 @@
  *                               u and its input derivatives ("jets") in one launch.
  *   pinn_jet_backward        <- loss.backward() through that graph (pinnrl/training/trainer.py:689):
  *                               d(sum_s <cotangent_s, jet_s>)/d(theta), accumulated into weight_grads.
+ *   pinn_jet_backward_inputs <- torch.autograd.grad(u, (x, t)) through the same graph (pinnrl/pdes/allen_cahn.py:50-108,
+ *                               heat_equation.py:425-445, pde_base.py:640-794): the same reverse sweep, plus the
+ *                               cotangents of the coordinates; weight gradients optional.
  *   pinn_residual_forward    <- XxxEquation.compute_residual (pinnrl/pdes/burgers_equation.py:40-75,
  *                               heat_equation.py:54-110, allen_cahn.py:39-111, kdv_equation.py:38-92,
  *                               cahn_hilliard.py:39-160, wave_equation.py:38-119,
@@ -134,7 +137,8 @@ int pinn_num_tensors(const PinnNetDesc* net);
 /* (time_order, space_order) of the jet streams a PDE's residual consumes; K = 1 + nt + nx. */
 int pinn_pde_streams(const PinnPdeDesc* pde, int32_t* time_order, int32_t* space_order);
 
-/* Bytes of scratch a call on N points needs (`backward` = 0 for the forward-only entry points, 1 otherwise).
+/* Bytes of scratch a call on N points needs (`backward` = 0 for the forward-only entry points, 2 for
+ * pinn_jet_backward_inputs — which always runs the layer-major engine — and 1 for the other entry points).
  * Zero is a valid answer (small networks run from registers and LDS alone); 0 is also returned for a descriptor the
  * library cannot run — the compute entry points then report why. */
 size_t pinn_workspace_bytes(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward);
@@ -158,6 +162,19 @@ int pinn_jet_backward(const PinnNetDesc* net, const float* const* weights, int32
                       const float* t, int64_t N, int32_t time_order, int32_t space_order,
                       const float* const* jet_cotangents, float* const* weight_grads, void* workspace, size_t ws_bytes,
                       void* stream);
+
+/* The reverse sweep of pinn_jet_backward on the layer-major engine, whatever the descriptor's flags say (the descriptor is
+ * not modified; size the workspace with pinn_workspace_bytes(..., backward = 2)):
+ * weight_grads += d<c, J>/d(weights) (table may be NULL: input cotangents only, and no weight-gradient work is done);
+ * x_grad[n*dim + c] = sum_s c_s[n] dJ_s[n]/dx[n,c]  (N x dim, row-major, overwritten, nullable);
+ * t_grad[n]         = sum_s c_s[n] dJ_s[n]/dt[n]    (N, overwritten, nullable).
+ * dim = input_dim - 1.  Mixed terms (e.g. d(u_t)/dx) and every spatial column are exact.  x_grad / t_grad are reduced over
+ * the features in a fixed order: bit-identical across launches on the same inputs, with or without
+ * PINN_FLAG_DETERMINISTIC.  Validation and error codes as pinn_jet_backward. */
+int pinn_jet_backward_inputs(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors, const float* x,
+                             const float* t, int64_t N, int32_t time_order, int32_t space_order,
+                             const float* const* jet_cotangents, float* const* weight_grads,
+                             float* x_grad, float* t_grad, void* workspace, size_t ws_bytes, void* stream);
 
 /* residual_out: N floats or NULL.  loss_sum_out: 1 float or NULL; receives += sum_n l(r_n)
  * (l = r^2 | |r| | huber), i.e. the UNnormalised loss — the caller divides by the global N. */

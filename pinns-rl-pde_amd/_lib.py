@@ -30,6 +30,7 @@ EXPORTS = (
     "pinn_abi_version", "pinn_last_error", "pinn_build_info", "pinn_num_tensors", "pinn_pde_streams",
     "pinn_workspace_bytes", "pinn_jet_forward", "pinn_jet_backward", "pinn_residual_forward", "pinn_residual_backward",
     "pinn_residual_loss_grad", "pinn_residual_loss_grad_coef", "pinn_point_losses", "pinn_jet_losses", "pinn_adam_clip_step",
+    "pinn_jet_backward_inputs",
 )
 
 
@@ -103,6 +104,9 @@ def load():
         lib.pinn_jet_forward.argtypes = [P(PinnNetDesc), P(vp), i32, vp, vp, i64, i32, i32, P(vp), vp, sz, vp]
         lib.pinn_jet_backward.restype = ctypes.c_int
         lib.pinn_jet_backward.argtypes = [P(PinnNetDesc), P(vp), i32, vp, vp, i64, i32, i32, P(vp), P(vp), vp, sz, vp]
+        lib.pinn_jet_backward_inputs.restype = ctypes.c_int
+        lib.pinn_jet_backward_inputs.argtypes = [P(PinnNetDesc), P(vp), i32, vp, vp, i64, i32, i32, P(vp), P(vp), vp, vp, vp,
+                                                 sz, vp]
         lib.pinn_residual_forward.restype = ctypes.c_int
         lib.pinn_residual_forward.argtypes = [P(PinnNetDesc), P(vp), i32, P(PinnPdeDesc), vp, vp, i64, vp, vp, vp, sz, vp]
         lib.pinn_residual_backward.restype = ctypes.c_int

@@ -33,6 +33,8 @@ struct CallArgs {
   bool bwd;
   bool deterministic;
   hipStream_t stream;
+  float* x_grad;  // input cotangents (pinn_jet_backward_inputs): written, nullable
+  float* t_grad;
 };
 
 // tensors the reference's state_dict holds for this descriptor (the length every weight table must have)
@@ -42,7 +44,7 @@ int lm_check(const PinnNetDesc* d, char* err, size_t errlen);
 size_t lm_workspace_bytes(const PinnNetDesc* d, long long N, int nt, int nx, bool bwd, bool deterministic);
 int lm_run(const CallArgs& c, char* err, size_t errlen);
 
-// per-stream-set translation units (lm_inst.hip); `act` = PinnAct, -1 = none, -2 = Fourier features (forward only)
+// per-stream-set translation units (lm_inst.hip); `act` = PinnAct, -1 = none, -2 = Fourier features (reverse: input cotangents)
 #define PINN_LM_DECL(nt, nx)                                                                              \
   hipError_t launch_lm_ew_##nt##_##nx(const EwArgs&, bool bwd, int act, int fpt, int grid, hipStream_t); \
   hipError_t launch_lm_head_##nt##_##nx(const HeadArgs&, int fpt, int grid, hipStream_t);

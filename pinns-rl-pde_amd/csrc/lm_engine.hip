@@ -898,7 +898,10 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     hipLaunchKernelGGL(lm_pack_kernel, dim3(8, second.n), dim3(256), 0, st, second, params);
     LM_CHECK(hipGetLastError());
   }
-  if (c.bwd) LM_CHECK(hipMemsetAsync(grads, 0, L.n_packed * sizeof(float), st));
+  // input cotangents only (pinn_jet_backward_inputs without a gradient table): no dW / db GEMM, no packed-gradient traffic
+  const bool wgrads = c.bwd && c.grads;
+  const bool want_xg = c.bwd && (c.x_grad || c.t_grad);
+  if (wgrads) LM_CHECK(hipMemsetAsync(grads, 0, L.n_packed * sizeof(float), st));
   auto pp = [&](int idx) -> const float* { return idx >= 0 ? params + L.tab.item[idx].off : nullptr; };
   auto gp = [&](int idx) -> float* {  // packed gradient slot, or null when nobody wants it (merged tensors: always wanted)
     if (idx < 0 || !c.bwd || !c.grads) return nullptr;
@@ -1071,7 +1074,8 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     };
     auto run_ew_bwd = [&](const Prologue& pro, int self, const float* vbar) -> int {
       // self = node index (kMaxNodes for the head); vbar = cotangent record of its V, or null for the head's (U, w_out) form
-      const bool needs = pro.src_kind == SRC_REC || (pro.src_kind == SRC_COORDS_LINEAR) || pro.ln_g >= 0 || pro.skip_node >= 0;
+      const bool xg = want_xg && pro.src_kind != SRC_REC;  // coordinate-fed prologue of a call that wants input cotangents
+      const bool needs = pro.src_kind == SRC_REC || (pro.src_kind == SRC_COORDS_LINEAR) || pro.ln_g >= 0 || pro.skip_node >= 0 || xg;
       if (!needs) return PINN_OK;  // Fourier features straight from the coordinates: nothing upstream to differentiate
       EwArgs a;
       const int fpt = fill_ew(a, pro, ct, p_base, self);
@@ -1087,15 +1091,19 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
       }
       a.d_ln_g = gp(pro.ln_g);
       a.d_ln_b = gp(pro.ln_b);
+      if (xg) {
+        a.x_grad = c.x_grad;
+        a.t_grad = c.t_grad;
+      }
       if (pro.src_kind == SRC_COORDS_LINEAR) {
         a.d_encW = gp(pro.enc_w);
         a.d_encb = gp(pro.enc_b);
-        if (!a.d_encW && pro.ln_g < 0 && pro.skip_node < 0) return PINN_OK;
+        if (!a.d_encW && pro.ln_g < 0 && pro.skip_node < 0 && !xg) return PINN_OK;
       }
       const bool has_sums = pro.ln_g >= 0 || (pro.src_kind == SRC_COORDS_LINEAR && a.d_encW);
       if (c.deterministic && has_sums) a.det_partial = ws + L.det;
       const int egrid = ew_grid(ct, a.G);
-      e = launch_ew(c.nt, c.nx, a, true, pro.act, fpt, egrid, st);
+      e = launch_ew(c.nt, c.nx, a, true, pro.src_kind == SRC_COORDS_FOURIER ? -2 : pro.act, fpt, egrid, st);
       if (e != hipSuccess) return failf(err, en, PINN_ERR_HIP, "HIP error %d: %s (lm_ew_bwd)", (int)e, hipGetErrorString(e));
       if (a.det_partial) {
         SlotReduce r;
@@ -1240,9 +1248,11 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
       }
       // cotangent of this node's GEMM input, then through its prologue
       const Prologue& pro = nd.pro;
-      const bool upstream = pro.src_kind == SRC_REC || pro.src_kind == SRC_COORDS_LINEAR || pro.ln_g >= 0 || pro.skip_node >= 0;
+      // (Fourier node 0: its input cotangent W_1^T Zbar_1 is formed only when the call wants input cotangents)
+      const bool xg_here = want_xg && pro.src_kind != SRC_REC;
+      const bool upstream = pro.src_kind == SRC_REC || pro.src_kind == SRC_COORDS_LINEAR || pro.ln_g >= 0 || pro.skip_node >= 0 || xg_here;
       if (!upstream) continue;
-      if (pro.src_kind == SRC_COORDS_LINEAR && !gp(pro.enc_w) && !gp(pro.enc_b) && pro.ln_g < 0 && pro.skip_node < 0) continue;
+      if (pro.src_kind == SRC_COORDS_LINEAR && !gp(pro.enc_w) && !gp(pro.enc_b) && pro.ln_g < 0 && pro.skip_node < 0 && !xg_here) continue;
       if (P.fuse_bwd[m].on) {  // Vbar = W^T Zbar (+ extras) and the prologue's adjoint in one launch
         FusedArgs f;
         memset(&f, 0, sizeof(f));
@@ -1299,11 +1309,11 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     }
     for (int w = 0; w < 4; ++w) LM_CHECK(flush_batch(w));
   }
-  if (c.bwd && P.n_derived > 0) {  // merged gradients back onto W_p, b_p, W_v, b_v (their packed slots), then the one unpack
+  if (wgrads && P.n_derived > 0) {  // merged gradients back onto W_p, b_p, W_v, b_v (their packed slots), then the one unpack
     hipLaunchKernelGGL(lm_unmerge_pv_kernel, dim3(16, P.n_derived), dim3(256), 0, st, merge, params, grads);
     LM_CHECK(hipGetLastError());
   }
-  if (c.bwd) {
+  if (wgrads) {
     hipLaunchKernelGGL(lm_unpack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, grads);
     LM_CHECK(hipGetLastError());
   }

@@ -63,6 +63,9 @@ struct EwArgs {
   float* det_partial;   // deterministic mode: per-workgroup partials [grid][7][1024] instead of float atomics
   float* stats;         // LayerNorm prologues: [tile][2 K][32] per-point sums (K stream sums, then K second-moment sums)
                         // written by the forward launch and re-read by the reverse one (saves two block reductions)
+  // input cotangents (coordinate-fed prologues, reverse; instantiations of their own, see lm_ew_bwd<.., XG>): written
+  float* x_grad;        // (N, din - 1) or null
+  float* t_grad;        // (N) or null
 };
 
 // Record access: element (row, point n) of this thread's feature group lives at tile_base + row * 32 floats + tid * 4
@@ -444,6 +447,54 @@ __device__ __forceinline__ void elem_pre(const EwArgs& a, const float* skip_base
 }
 
 
+// ---------------------------------------------------------------------------------------------------------------
+// input cotangents of a coordinate-fed prologue (reverse, XG instantiations and lm_fourier_bwd)
+// ---------------------------------------------------------------------------------------------------------------
+// Per-thread partial of [xbar | tbar] over this thread's features of the first Linear: sum_i W[f_i][c] zbar_0[f_i].  The
+// derivative streams were seeded with constant columns of W (load_source), so zbar_0 is the only path to the input.
+template <int NT, int NX, int FPT>
+__device__ __forceinline__ void xg_partial_linear(const EwArgs& a, unsigned goff, const float (&pb)[FPT][1 + NT + NX], float (&xg)[4]) {
+  const float* encW = in_loop(a.encW);
+#pragma unroll
+  for (int cc = 0; cc < 4; ++cc) xg[cc] = 0.0f;
+#pragma unroll
+  for (int i = 0; i < FPT; ++i) {
+    const f32x4 w = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(encW + 4 * a.G * i) + 4u * goff);  // zero beyond din / H
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) xg[cc] = fmaf(w[cc], pb[i][0], xg[cc]);
+  }
+}
+
+template <int NT, int NX, int FPT>
+__device__ __forceinline__ f32x4 xg_first_linear(const EwArgs& a, unsigned goff, const float (&pb)[FPT][1 + NT + NX]) {
+  float xg[4];
+  xg_partial_linear<NT, NX, FPT>(a, goff, pb, xg);
+  return f32x4{xg[0], xg[1], xg[2], xg[3]};
+}
+
+// Sum the per-thread partials over every feature group of point n (block_sum: shuffles, then the waves in a fixed order —
+// no float atomics, the same bits on every launch) and WRITE x_grad[p][0 .. din-2], t_grad[p] from the lanes of group 0.
+__device__ __forceinline__ void write_input_grads(const EwArgs& a, long long unit, int n, bool ok, f32x4 part, float* red, int& slot,
+                                                  int nwaves, int wave, int tid) {
+  float q[4] = {part[0], part[1], part[2], part[3]};
+  block_sum<4>(q, red, slot, nwaves, wave, tid, n);
+  if (tid < kPT && ok) {
+    const long long p = a.p_base + unit * kPT + n;
+    float* xg = in_loop(a.x_grad);
+    float* tg = in_loop(a.t_grad);
+    if (xg) {
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc)
+        if (cc < a.din - 1) xg[p * (a.din - 1) + cc] = q[cc];
+    }
+    if (tg) {
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc)
+        if (cc == a.din - 1) tg[p] = q[cc];
+    }
+  }
+}
+
 // Fourier features of the coordinates (fourier.py:12-16): V[f] = sin(x B)_f for f < M, cos(x B)_{f-M} for M <= f < 2M,
 // jets included.  A forward-only prologue of its own: B is a buffer, nothing is differentiated through it.
 template <int NT, int NX, int FPT>
@@ -493,6 +544,72 @@ __global__ __launch_bounds__(1024) void lm_fourier_fwd(const EwArgs a) {
 #pragma unroll
       for (int s = 0; s < K; ++s) rec_st(out, s * a.Hp + a.G * i, voff, on ? yy[s] : 0.0f);
     }
+  }
+}
+
+// Adjoint of lm_fourier_fwd with respect to the coordinates.  Feature f of stream s is phi_s = d^k_dir sin|cos(p_m),
+// p_m = x~ . B[:, m], and along a direction whose column of B is w (w = B[din-1][m] for t, B[0][m] for x) the jets
+// are phi_k = f^(k)(p) w^k, so  pbar_m = sum_s phibar_s f^(k_s + 1)(p) w_s^k_s  and  [xbar | tbar] = B pbar.
+// Vbar is node 0's input cotangent (W_1^T Zbar_1 for all K streams); nothing else is read, nothing accumulated.
+template <int NT, int NX, int FPT>
+__global__ __launch_bounds__(1024) void lm_fourier_bwd(const EwArgs a) {
+  constexpr int K = 1 + NT + NX;
+  __shared__ float red[2 * kMaxWavesEw * kRedQ * kPT];
+  const int tid = threadIdx.x, n = tid & (kPT - 1), g = tid >> 4;
+  const int wave = tid >> 6, nwaves = (a.G + 3) >> 2;
+  int slot = 0;
+  const unsigned voff = static_cast<unsigned>(g * kT + n) * 4u;
+  for (long long uu = 2LL * blockIdx.x; uu < 2 * a.ntiles; uu += (uu & 1) ? 2LL * gridDim.x - 1 : 1) {
+    const long long unit = uu;
+    float xin[4];
+    bool ok;
+    load_coords(a, unit, n, xin, ok);
+    const long long rec_off = (unit >> 1) * (long long)K * a.Hp * kT + (unit & 1) * kPT;
+    const float* vb = in_loop(a.Vbar) + rec_off;
+    float xg[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < FPT; ++i) {
+      const int f = g + a.G * i;
+      const bool on = f < 2 * a.M;
+      const int m = f < a.M ? f : f - a.M;
+      const f32x4 w = on ? *reinterpret_cast<const f32x4*>(a.encW + 4 * m) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      float v = 0.0f;
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) v = fmaf(xin[cc], w[cc], v);
+      float wt = w[0];
+#pragma unroll
+      for (int cc = 1; cc < 4; ++cc) wt = (cc == a.din - 1) ? w[cc] : wt;
+      float sn, cs;
+      fast_sincosf(v, &sn, &cs);
+      float fd[6];  // f^(j)(p), j = 0..5
+      fd[0] = f < a.M ? sn : cs;
+      fd[1] = f < a.M ? cs : -sn;
+      fd[2] = -fd[0];
+      fd[3] = -fd[1];
+      fd[4] = fd[0];
+      fd[5] = fd[1];
+      float pbar = rec_ld(vb, a.G * i, voff) * fd[1];
+      if constexpr (NT > 0) {
+        float wk = 1.0f;
+#pragma unroll
+        for (int k = 1; k <= NT; ++k) {
+          wk *= wt;
+          pbar = fmaf(rec_ld(vb, sidx(1, k) * a.Hp + a.G * i, voff) * wk, fd[k + 1], pbar);
+        }
+      }
+      if constexpr (NX > 0) {
+        float wk = 1.0f;
+#pragma unroll
+        for (int k = 1; k <= NX; ++k) {
+          wk *= w[0];
+          pbar = fmaf(rec_ld(vb, sidx(1 + NT, k) * a.Hp + a.G * i, voff) * wk, fd[k + 1], pbar);
+        }
+      }
+      pbar = on ? pbar : 0.0f;
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) xg[cc] = fmaf(w[cc], pbar, xg[cc]);
+    }
+    write_input_grads(a, unit, n, ok, f32x4{xg[0], xg[1], xg[2], xg[3]}, red, slot, nwaves, wave, tid);
   }
 }
 
@@ -552,11 +669,11 @@ __global__ __launch_bounds__(1024) void lm_ew_fwd(const EwArgs a) {
   }
 }
 
-template <int ACT, int NT, int NX, int FPT, bool LN>
+template <int ACT, int NT, int NX, int FPT, bool LN, bool XG = false>
 __global__ __launch_bounds__(1024) void lm_ew_bwd(const EwArgs a) {
   constexpr int K = 1 + NT + NX;
   constexpr int kAcc = 7;  // per-feature accumulators: dgamma, dbeta | encoder: 4 weight columns + bias
-  __shared__ float red[LN ? 2 * kMaxWavesEw * kRedQ * kPT : 1];
+  __shared__ float red[(LN || XG) ? 2 * kMaxWavesEw * kRedQ * kPT : 1];
   __shared__ float pacc[kAcc * 1024];
   const int tid = threadIdx.x, n = tid & (kPT - 1), g = tid >> 4;
   const int wave = tid >> 6, nwaves = (a.G + 3) >> 2;
@@ -641,6 +758,9 @@ __global__ __launch_bounds__(1024) void lm_ew_bwd(const EwArgs a) {
     }
     if constexpr (LN)
       ln_backward<NT, NX, FPT>(zc, pb, valid, gamv, al.G, pacc, pacc + 1024, g, al.H, S, red, slot, nwaves, wave, tid, n);
+    if constexpr (XG) {  // coordinate-fed first Linear: only z_0 = W x~ + b depends on the input, so [xbar | tbar] = W^T zbar_0
+      write_input_grads(al, unit, n, ok, xg_first_linear<NT, NX, FPT>(al, goff, pb), red, slot, nwaves, wave, tid);
+    }
     if (al.src_kind == SRC_REC) {
       if (al.Zbar) {
         float* out = in_loop(al.Zbar) + rec_off;

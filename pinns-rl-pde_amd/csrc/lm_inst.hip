@@ -34,7 +34,10 @@ static hipError_t launch_ew(const EwArgs& a, bool bwd, int grid, hipStream_t st)
       return hipGetLastError();
     }
   }
-  if (bwd) hipLaunchKernelGGL((lm_ew_bwd<ACT, PINN_NT, PINN_NX, FPT, LN>), dim3(grid), dim3(threads), 0, st, a);
+  // input cotangents: instantiations of their own (XG), so that the weight-gradient units keep their code
+  if (bwd && (a.x_grad || a.t_grad))
+    hipLaunchKernelGGL((lm_ew_bwd<ACT, PINN_NT, PINN_NX, FPT, LN, true>), dim3(grid), dim3(threads), 0, st, a);
+  else if (bwd) hipLaunchKernelGGL((lm_ew_bwd<ACT, PINN_NT, PINN_NX, FPT, LN>), dim3(grid), dim3(threads), 0, st, a);
   else hipLaunchKernelGGL((lm_ew_fwd<ACT, PINN_NT, PINN_NX, FPT, LN>), dim3(grid), dim3(threads), 0, st, a);
   return hipGetLastError();
 }
@@ -55,8 +58,18 @@ static hipError_t launch_ew_fpt(const EwArgs& a, bool bwd, int fpt, int grid, hi
   }
 }
 
-static hipError_t launch_fourier(const EwArgs& a, int fpt, int grid, hipStream_t st) {
+static hipError_t launch_fourier(const EwArgs& a, bool bwd, int fpt, int grid, hipStream_t st) {
   const int threads = kPT * a.G;
+  if (bwd) {  // input cotangents through the Fourier features (lm_fourier_bwd)
+    switch (fpt) {
+      case 1: hipLaunchKernelGGL((lm_fourier_bwd<PINN_NT, PINN_NX, 1>), dim3(grid), dim3(threads), 0, st, a); break;
+      case 4: hipLaunchKernelGGL((lm_fourier_bwd<PINN_NT, PINN_NX, 4>), dim3(grid), dim3(threads), 0, st, a); break;
+      case 8: hipLaunchKernelGGL((lm_fourier_bwd<PINN_NT, PINN_NX, 8>), dim3(grid), dim3(threads), 0, st, a); break;
+      case 16: hipLaunchKernelGGL((lm_fourier_bwd<PINN_NT, PINN_NX, 16>), dim3(grid), dim3(threads), 0, st, a); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (fpt) {
     case 1: hipLaunchKernelGGL((lm_fourier_fwd<PINN_NT, PINN_NX, 1>), dim3(grid), dim3(threads), 0, st, a); break;
     case 4: hipLaunchKernelGGL((lm_fourier_fwd<PINN_NT, PINN_NX, 4>), dim3(grid), dim3(threads), 0, st, a); break;
@@ -67,9 +80,9 @@ static hipError_t launch_fourier(const EwArgs& a, int fpt, int grid, hipStream_t
   return hipGetLastError();
 }
 
-// act: PinnAct of the prologue, -1 = no activation, -2 = Fourier features of the coordinates (forward only)
+// act: PinnAct of the prologue, -1 = no activation, -2 = Fourier features of the coordinates (reverse: input cotangents only)
 hipError_t PINN_NAME(ew_, PINN_NT, PINN_NX)(const EwArgs& a, bool bwd, int act, int fpt, int grid, hipStream_t st) {
-  if (act == -2) return bwd ? hipErrorInvalidValue : launch_fourier(a, fpt, grid, st);
+  if (act == -2) return (bwd && !a.x_grad && !a.t_grad) ? hipErrorInvalidValue : launch_fourier(a, bwd, fpt, grid, st);
   switch (act) {
     case PINN_ACT_TANH: return launch_ew_fpt<PINN_ACT_TANH>(a, bwd, fpt, grid, st);
     case PINN_ACT_SIN: return launch_ew_fpt<PINN_ACT_SIN>(a, bwd, fpt, grid, st);

@@ -311,10 +311,10 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
                const PinnPdeDesc* pde, const float* x, const float* t, int64_t N, int nt, int nx, int mode,
                float grad_scale, float* const* jets_out, const float* const* jets_bar, float* residual_out,
                float* loss_sum, void* workspace, size_t ws_bytes, bool bwd, void* stream, const float* res_bar = nullptr,
-               float* coef_grads = nullptr) {
+               float* coef_grads = nullptr, float* x_grad = nullptr, float* t_grad = nullptr, bool lm_only = false) {
   int rc = validate_table(net, weights, num_tensors, "weights");
   if (rc) return rc;
-  if (bwd && (rc = validate_table(net, grads, num_tensors, "weight_grads"))) return rc;
+  if (bwd && grads && (rc = validate_table(net, grads, num_tensors, "weight_grads"))) return rc;  // null only where the entry point allows it
   if (N <= 0) return PINN_OK;
   if (!x && net->input_dim > 1) return fail(PINN_ERR_BAD_DESC, "x is null");
   if (!t) return fail(PINN_ERR_BAD_DESC, "t is null");
@@ -346,7 +346,7 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
   if (coef_grads && !(net->flags & PINN_FLAG_LAYER_MAJOR) && !force_lm() && use_wide(net, nullptr, nullptr, K, bwd, &a.net))
     return fail(PINN_ERR_UNSUPPORTED, "coefficient gradients run on the layer-major engine: set PINN_FLAG_LAYER_MAJOR in the "
                 "descriptor for this call and for its pinn_workspace_bytes query");
-  const bool wide = use_wide(net, weights, grads, K, bwd, &a.net, &misaligned);
+  const bool wide = !lm_only && use_wide(net, weights, grads, K, bwd, &a.net, &misaligned);
   if (!wide && misaligned >= 0)  // pinn_workspace_bytes sized this descriptor for the fused kernel: say what is wrong instead of "workspace too small"
     return fail(PINN_ERR_MISALIGNED, "weight tensor %d is not 16-byte aligned: the fused kernel of this descriptor reads hidden-layer "
                 "weights with 16-byte loads (pass aligned tensors, or set PINN_FLAG_LAYER_MAJOR to take the packing engine)", misaligned);
@@ -451,6 +451,8 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
   c.bwd = bwd;
   c.deterministic = (net->flags & PINN_FLAG_DETERMINISTIC) != 0;
   c.stream = static_cast<hipStream_t>(stream);
+  c.x_grad = x_grad;
+  c.t_grad = t_grad;
   rc = lm::lm_run(c, lerr, sizeof(lerr));
   if (rc) return fail(rc, "%s", lerr);
   return PINN_OK;
@@ -507,7 +509,7 @@ size_t pinn_workspace_bytes(const PinnNetDesc* net, int64_t N, int32_t time_orde
   const int K = 1 + time_order + space_order;
   const bool bwd = backward != 0;
   NetDev n;
-  if (use_wide(net, nullptr, nullptr, K, bwd, &n)) {
+  if (backward != 2 && use_wide(net, nullptr, nullptr, K, bwd, &n)) {  // 2: pinn_jet_backward_inputs, always layer-major
     const size_t grid = (size_t)wide_grid(n, K, N, bwd);
     size_t bytes = bwd ? (size_t)jet_tape_floats_per_wg(K, n.n_layers, 1) * sizeof(float) * grid : 0;
     if ((net->flags & PINN_FLAG_DETERMINISTIC) || (bwd && n.n_layers <= kPersist && wide_store_flush_on())) {
@@ -543,6 +545,32 @@ int pinn_jet_backward(const PinnNetDesc* net, const float* const* weights, int32
   if (!jet_cotangents || !weight_grads) return fail(PINN_ERR_BAD_DESC, "null cotangents or weight_grads");
   return run(net, weights, weight_grads, num_tensors, nullptr, x, t, N, time_order, space_order, MODE_JETS, 0.0f, nullptr,
              jet_cotangents, nullptr, nullptr, workspace, ws_bytes, true, stream);
+}
+
+// The layer-major engine whatever the descriptor's flags say (the fused tile-major kernel has no input cotangents; the
+// descriptor is not modified); pinn_workspace_bytes(..., backward = 2) sizes it.
+int pinn_jet_backward_inputs(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors, const float* x,
+                             const float* t, int64_t N, int32_t time_order, int32_t space_order,
+                             const float* const* jet_cotangents, float* const* weight_grads, float* x_grad, float* t_grad,
+                             void* workspace, size_t ws_bytes, void* stream) {
+  if (!jet_cotangents) return fail(PINN_ERR_BAD_DESC, "null cotangents");
+  if (net && weight_grads) {
+    const int rc = validate_table(net, weight_grads, num_tensors, "weight_grads");
+    if (rc) return rc;
+  }
+  if (net && net->input_dim <= 1) x_grad = nullptr;  // no spatial column
+  if (!weight_grads && !x_grad && !t_grad) {  // nothing requested: validate, launch nothing
+    int rc = validate_table(net, weights, num_tensors, "weights");
+    if (rc || N <= 0) return rc;
+    if ((rc = check_orders(time_order, space_order))) return rc;
+    if (!stream_set_compiled(time_order, space_order))
+      return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", time_order, space_order);
+    char lerr[256] = "";
+    if ((rc = lm::lm_check(net, lerr, sizeof(lerr)))) return fail(rc, "%s", lerr);
+    return PINN_OK;
+  }
+  return run(net, weights, weight_grads, num_tensors, nullptr, x, t, N, time_order, space_order, MODE_JETS, 0.0f, nullptr,
+             jet_cotangents, nullptr, nullptr, workspace, ws_bytes, true, stream, nullptr, nullptr, x_grad, t_grad, true);
 }
 
 int pinn_residual_forward(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors,

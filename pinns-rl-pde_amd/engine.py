@@ -247,6 +247,35 @@ def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot:
                                          t.data_ptr(), N, nt, nx, cptr, _grad_ptrs(prog, flat_grad), wptr, wn, _stream(dev)))
 
 
+def jets_backward_inputs(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor,
+                         flat_grad: Optional[Tensor], want_x: bool, want_t: bool) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """(x_grad (N, dim) | None, t_grad (N, 1) | None) = d<cot, jets>/d(x, t), and flat_grad += d<cot, jets>/d(theta) when
+    given — one `pinn_jet_backward_inputs` launch on the layer-major engine (the descriptor is not touched).  cot: (K, N)."""
+    lib = _lib.load()
+    dev = _require_device(x, t, cot, flat_grad, *prog.tensors)
+    x, t, N = _prep_points(prog, x, t)
+    want_x = bool(want_x) and x.shape[1] > 0
+    xg = torch.empty_like(x) if want_x else None
+    tg = torch.empty_like(t) if want_t else None
+    if N == 0 or (xg is None and tg is None and flat_grad is None):
+        return xg, tg
+    K = 1 + nt + nx
+    cot = _f32c(cot)
+    assert cot.shape == (K, N)
+    cptr = (ctypes.c_void_p * K)(*[cot[s].data_ptr() for s in range(K)])
+    nbytes = lib.pinn_workspace_bytes(ctypes.byref(prog.desc), N, nt, nx, 2)
+    ws = _workspace(dev, nbytes) if nbytes else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_jet_backward_inputs(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
+                                                t.data_ptr(), N, nt, nx, cptr,
+                                                _grad_ptrs(prog, flat_grad) if flat_grad is not None else None,
+                                                xg.data_ptr() if xg is not None else None,
+                                                tg.data_ptr() if tg is not None else None,
+                                                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                                _stream(dev)))
+    return xg, tg
+
+
 def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: bool = True) -> Tuple[Optional[Tensor], Tensor]:
     """(residual (N,1) | None, loss_sum (1,)) with loss_sum = sum_n l(r_n) over THESE points."""
     lib = _lib.load()
@@ -387,12 +416,68 @@ def adam_clip_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: T
 # ---------------------------------------------------------------------------------------------
 # autograd splices
 # ---------------------------------------------------------------------------------------------
+class _NotTwiceDifferentiable(torch.autograd.Function):
+    """Identity on a value the kernel computed exactly but cannot differentiate again (mixed directions, spatial columns
+    >= 1, orders beyond the compiled stream sets, weight gradients under create_graph).  Its backward raises as soon as a
+    NON-zero cotangent reaches it, naming the derivative; a zero cotangent (the value is in the graph but unused) is
+    passed on as zero, which is exact.  `anchors` (the coordinates and parameters the value depends on) put the node
+    into the graph: the value itself is a plain tensor from the kernel."""
+
+    @staticmethod
+    def forward(ctx, v: Tensor, what: str, *anchors: Tensor):
+        ctx.what, ctx.n = what, len(anchors)
+        return v.clone()
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        if bool(torch.any(g != 0)):
+            raise NotImplementedError(
+                f"pinnrl_amd: {ctx.what} is not differentiable again: the jet kernels differentiate pure chains along t and "
+                "along the first spatial column up to the compiled orders (time 2, space 4) only")
+        return (None, None) + (None,) * ctx.n
+
+
+def _stream_set_covering(nt: int, nx: int) -> Optional[Tuple[int, int]]:
+    from .pdes.pde_base import _pick_stream_set
+    try:
+        return _pick_stream_set(nt, nx)
+    except NotImplementedError:
+        return None
+
+
+def _pure_input_grads(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, params, direction: str):
+    """Differentiable part of d<cot, jets>/dx[:, 0] (direction "x") or d<cot, jets>/dt ("t") that stays on one axis: the
+    value and the streams of that axis, each raised by one order, from a JetFunction one order higher.  (N, 1), or None
+    when no compiled stream set reaches that order."""
+    if direction == "x":
+        sel = [0] + [1 + nt + k for k in range(nx)]  # streams whose derivative along x0 is an x-stream of order + 1
+        ss = _stream_set_covering(0, nx + 1)
+    else:
+        sel = [0] + [1 + k for k in range(nt)]
+        ss = _stream_set_covering(nt + 1, 0)
+    if ss is None:
+        return None
+    a, b = ss
+    J = JetFunction.apply(prog, x, t, a, b, *params)
+    # stream of order j + 1 along the direction in the (a, b) set
+    rows = [(1 + a + j) if direction == "x" else (1 + j) for j in range(len(sel))]
+    out = None
+    for s, r in zip(sel, rows):
+        term = cot[s] * J[r]
+        out = term if out is None else out + term
+    return out.unsqueeze(1)
+
+
 class JetFunction(torch.autograd.Function):
-    """jets = f(theta; x, t), differentiable w.r.t. the trainable tensors of the program.
+    """jets = f(theta; x, t), differentiable w.r.t. the trainable tensors of the program AND the coordinates.
 
     Replaces `u = model(cat[x,t])` + the chained `autograd.grad(create_graph=True)` calls of
-    `PDEBase.compute_derivatives` (pinnrl/pdes/pde_base.py:640-732).  The coordinates are treated
-    as constants, as the reference does after its `detach()` (pde_base.py:630-631).
+    `PDEBase.compute_derivatives` (pinnrl/pdes/pde_base.py:640-732).  `compute_derivatives` itself still detaches the
+    coordinates, as the reference does (pde_base.py:630-631); a caller that differentiates w.r.t. x / t itself gets
+    exact input cotangents from `pinn_jet_backward_inputs`.  Under create_graph, the parts of those cotangents that stay
+    on one axis (t, or the first spatial column) are differentiable again through a JetFunction one order higher, up to
+    the compiled orders; everything else keeps its exact value and raises if differentiated again
+    (`_NotTwiceDifferentiable`).
     """
 
     @staticmethod
@@ -403,12 +488,56 @@ class JetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, cot: Tensor):
-        prog = ctx.prog
+        prog, nt, nx = ctx.prog, ctx.nt, ctx.nx
         x, t = ctx.saved_tensors
-        flat = new_flat_grad(prog, cot.device)
-        jets_backward(prog, x, t, ctx.nt, ctx.nx, cot, flat)
-        grads = split_flat_grad(prog, flat)
-        return (None, None, None, None, None, *grads)
+        params = prog.tensors  # the live tensors this node was applied to (PINNModel.jets passes exactly these)
+        want_x, want_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        want_w = any(ctx.needs_input_grad[5:])
+        if not (want_x or want_t):
+            flat = new_flat_grad(prog, cot.device)
+            jets_backward(prog, x, t, nt, nx, cot, flat)
+            grads = split_flat_grad(prog, flat)
+            return (None, None, None, None, None, *grads)
+        flat = new_flat_grad(prog, cot.device) if want_w else None
+        xg, tg = jets_backward_inputs(prog, x, t, nt, nx, cot.detach(), flat, want_x, want_t)
+        grads = split_flat_grad(prog, flat) if flat is not None else [None] * len(prog.tensors)
+        if xg is not None:
+            xg = xg.to(x.dtype)
+        if tg is not None:
+            tg = tg.to(t.dtype)
+        if torch.is_grad_enabled():  # create_graph=True: input gradients that are differentiable again where possible
+            anchors = (x, t, *params)
+            grads = [None if g is None else _NotTwiceDifferentiable.apply(g, "a weight gradient", *anchors) for g in grads]
+            if xg is not None:
+                cols = []
+                for c in range(xg.shape[1]):
+                    what = f"d<cot, jets>/dx[:, {c}]"
+                    if c > 0:
+                        cols.append(_NotTwiceDifferentiable.apply(xg[:, c:c + 1], what + " (spatial column >= 1)", *anchors))
+                        continue
+                    pure = _pure_input_grads(prog, x, t, nt, nx, cot, params, "x")
+                    mixed = nt > 0 and bool(torch.any(cot[1:1 + nt] != 0))
+                    if pure is None:
+                        cols.append(_NotTwiceDifferentiable.apply(xg[:, 0:1], what + f" (x order {nx + 1} is beyond the compiled sets)",
+                                                                  *anchors))
+                    elif mixed:
+                        cols.append(pure + _NotTwiceDifferentiable.apply(xg[:, 0:1] - pure.detach().to(xg.dtype),
+                                                                         what + " (mixed t / x derivative)", *anchors))
+                    else:
+                        cols.append(pure.to(xg.dtype))
+                xg = torch.cat(cols, 1)
+            if tg is not None:
+                what = "d<cot, jets>/dt"
+                pure = _pure_input_grads(prog, x, t, nt, nx, cot, params, "t")
+                mixed = nx > 0 and bool(torch.any(cot[1 + nt:] != 0))
+                if pure is None:
+                    tg = _NotTwiceDifferentiable.apply(tg, what + f" (t order {nt + 1} is beyond the compiled sets)", *anchors)
+                elif mixed:
+                    tg = pure + _NotTwiceDifferentiable.apply(tg - pure.detach().to(tg.dtype), what + " (mixed x / t derivative)",
+                                                                   *anchors)
+                else:
+                    tg = pure.to(tg.dtype)
+        return (None, xg if want_x else None, tg if want_t else None, None, None, *grads)
 
 
 class ResidualFunction(torch.autograd.Function):

@@ -124,10 +124,10 @@ class BaseNetwork(nn.Module):
             self._prog_cache[1].set_deterministic(self._deterministic)
 
     def jets(self, x: torch.Tensor, t: torch.Tensor, time_order: int = 0, space_order: int = 0) -> torch.Tensor:
-        """(K, N) = [u, d/dt.., d/dx..] in one launch; differentiable w.r.t. the parameters."""
+        """(K, N) = [u, d/dt.., d/dx..] in one launch; differentiable w.r.t. the parameters and w.r.t. x / t."""
         prog = self.program()
         params = prog.tensors
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        if torch.is_grad_enabled() and (x.requires_grad or t.requires_grad or any(p.requires_grad for p in params)):
             return _E.JetFunction.apply(prog, x, t, time_order, space_order, *params)
         return _E.jets_forward(prog, x, t, time_order, space_order)
 
