@@ -143,6 +143,25 @@ int pinn_pde_streams(const PinnPdeDesc* pde, int32_t* time_order, int32_t* space
  * library cannot run — the compute entry points then report why. */
 size_t pinn_workspace_bytes(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward);
 
+/* Which kernel a call on N points with stream set (time_order, space_order) takes — the decisions the compute entry points
+ * make, from the same code.  `backward` as for pinn_workspace_bytes (0 forward-only, 1 reverse, 2
+ * pinn_jet_backward_inputs).  No tensors are passed: the query assumes 16-byte-aligned weights (a misaligned hidden
+ * weight makes the compute call fail with PINN_ERR_MISALIGNED instead).  Fields that do not apply to the layer-major
+ * engine are -1 (default_mfma_form 0).  PINN_OK, or the PinnStatus the compute call would return for the descriptor. */
+typedef struct PinnKernelInfo {
+  int32_t engine;            /* 0 layer-major, 1 fused tile-major */
+  int32_t time_order, space_order, act_family, backward;  /* act_family: PinnAct of the compiled unit (leaky_relu and
+                                                             identity run the relu unit) */
+  int32_t hmax, na0;         /* compiled variant: LDS image height (64 | 128), k-tiles of the first MFMA layer's
+                                weight-gradient accumulators (2 | 4) */
+  int32_t grid;              /* workgroups of the launch */
+  int32_t flush;             /* weight gradients / loss sum: 0 direct atomics, 1 store flush, 2 two-level atomic flush,
+                                3 deterministic slab */
+  int32_t default_mfma_form; /* this unit was built in the fallback (default) MFMA form, see pinn_build_info() */
+} PinnKernelInfo;
+int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
+                    PinnKernelInfo* out);
+
 /* Every compute entry point: `weights` (and `weight_grads`) are tables of `num_tensors` device pointers in the
  * reference's state_dict order; the count is validated against the descriptor BEFORE any entry is read.
  * `workspace` must hold pinn_workspace_bytes(...) bytes, 16-byte aligned (may be NULL when that is 0).

@@ -30,7 +30,7 @@ EXPORTS = (
     "pinn_abi_version", "pinn_last_error", "pinn_build_info", "pinn_num_tensors", "pinn_pde_streams",
     "pinn_workspace_bytes", "pinn_jet_forward", "pinn_jet_backward", "pinn_residual_forward", "pinn_residual_backward",
     "pinn_residual_loss_grad", "pinn_residual_loss_grad_coef", "pinn_point_losses", "pinn_jet_losses", "pinn_adam_clip_step",
-    "pinn_jet_backward_inputs",
+    "pinn_jet_backward_inputs", "pinn_kernel_for",
 )
 
 
@@ -48,6 +48,18 @@ class PinnPdeDesc(ctypes.Structure):
         ("kind", ctypes.c_int32), ("dimension", ctypes.c_int32), ("loss", ctypes.c_int32),
         ("coef", ctypes.c_float * 4), ("huber_delta", ctypes.c_float),
     ]
+
+
+class PinnKernelInfo(ctypes.Structure):
+    _fields_ = [
+        ("engine", ctypes.c_int32), ("time_order", ctypes.c_int32), ("space_order", ctypes.c_int32),
+        ("act_family", ctypes.c_int32), ("backward", ctypes.c_int32), ("hmax", ctypes.c_int32), ("na0", ctypes.c_int32),
+        ("grid", ctypes.c_int32), ("flush", ctypes.c_int32), ("default_mfma_form", ctypes.c_int32),
+    ]
+
+
+ENGINE_LAYER_MAJOR, ENGINE_TILE_MAJOR = 0, 1
+FLUSH = {0: "direct", 1: "store", 2: "two_level", 3: "deterministic"}
 
 
 class JetLibraryError(RuntimeError):
@@ -100,6 +112,8 @@ def load():
         lib.pinn_workspace_bytes.restype = ctypes.c_size_t
         lib.pinn_workspace_bytes.argtypes = [P(PinnNetDesc), i64, i32, i32, i32]
         sz = ctypes.c_size_t
+        lib.pinn_kernel_for.restype = ctypes.c_int
+        lib.pinn_kernel_for.argtypes = [P(PinnNetDesc), i64, i32, i32, i32, P(PinnKernelInfo)]
         lib.pinn_jet_forward.restype = ctypes.c_int
         lib.pinn_jet_forward.argtypes = [P(PinnNetDesc), P(vp), i32, vp, vp, i64, i32, i32, P(vp), vp, sz, vp]
         lib.pinn_jet_backward.restype = ctypes.c_int
@@ -134,6 +148,21 @@ def load():
 def build_info() -> str:
     """Kernel translation units that were built in a degraded form ('' when none), see csrc/Makefile."""
     return load().pinn_build_info().decode("utf-8", "replace")
+
+
+def kernel_for(prog, N: int, nt: int, nx: int, backward: int) -> dict:
+    """Which kernel a call on N points with stream set (nt, nx) takes (pinn_kernel_for): engine ("tile_major" |
+    "layer_major"); for the tile-major engine also the compiled variant (hmax, na0), the activation family of its
+    translation unit, grid, weight-gradient flush and whether that unit was built in the default MFMA form.
+    backward: 0 forward-only entry points, 1 the reverse ones, 2 pinn_jet_backward_inputs.  Assumes 16-byte-aligned
+    weights (no tensors are passed)."""
+    info = PinnKernelInfo()
+    check(load().pinn_kernel_for(ctypes.byref(prog.desc), int(N), int(nt), int(nx), int(backward), ctypes.byref(info)))
+    out = {f: getattr(info, f) for f, _ in PinnKernelInfo._fields_}
+    out["engine"] = "tile_major" if info.engine == ENGINE_TILE_MAJOR else "layer_major"
+    out["flush"] = FLUSH.get(info.flush)
+    out["default_mfma_form"] = bool(info.default_mfma_form)
+    return out
 
 
 def check(rc: int) -> None:

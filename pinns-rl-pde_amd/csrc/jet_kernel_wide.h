@@ -862,19 +862,35 @@ inline bool jet_wide_fits(int K, int hmax, bool bwd, int n_layers) {
   return hmax <= 128 && jet_wide_lds_bytes(K, jet_wide_hmax(hmax), bwd, n_layers) <= 160 * 1024;
 }
 
+// Compiled variant a launch takes: image height (64 or 128) and k-tiles of the first MFMA layer's weight-gradient
+// accumulators.  Forward variants: (64, 2) and (128, 4); backward: (64, 2), (128, 2) when the first MFMA layer reads at
+// most 64 features (the headline network's 64 Fourier features), (128, 4) otherwise.  pinn_kernel_for reports the same.
+inline void jet_wide_variant(const NetDev& n, bool bwd, int* hm, int* na0) {
+  *hm = jet_wide_hmax(n.hmax);
+  const int k0 = n.n_layers > 0 ? (n.layer[0].in_dim + 31) / 32 : 4;  // k-tiles of the first MFMA layer
+  *na0 = *hm == 64 ? 2 : (bwd && k0 <= 2) ? 2 : 4;
+}
+
+// activation id of the network -> index of the compiled activation family (piecewise-linear ones share RELU's kernels)
+inline int jet_wide_act_family(const NetDev& n) {
+  const int act = n.n_layers > 0 ? n.layer[0].act : n.enc_act;
+  return (act == PINN_ACT_TANH || act == PINN_ACT_SIN || act == PINN_ACT_GELU || act == PINN_ACT_SIGMOID) ? act : PINN_ACT_RELU;
+}
+inline int jet_wide_act_family(const KernelArgs& a) { return jet_wide_act_family(a.net); }
+
 // one activation's kernels (the library builds one translation unit per stream set AND activation, see the Makefile)
 template <int ACT, int NT, int NX>
 hipError_t launch_jet_wide_act(const KernelArgs& a, bool bwd, int grid, hipStream_t stream) {
   constexpr int K = 1 + NT + NX;
-  const int hm = jet_wide_hmax(a.net.hmax);
-  const int na0 = a.net.n_layers > 0 ? (a.net.layer[0].in_dim + 31) / 32 : 4;  // k-tiles of the first MFMA layer
+  int hm, na0;
+  jet_wide_variant(a.net, bwd, &hm, &na0);
   const size_t lds = jet_wide_lds_bytes(K, hm, bwd, a.net.n_layers);
   hipError_t e = hipSuccess;
 #define PINN_WLAUNCH1(BWD_)                                                                                  \
   do {                                                                                                       \
     auto kern = hm == 64 ? jet_kernel_wide<ACT, NT, NX, BWD_, 64, 2>                                         \
-                : (BWD_ && na0 <= 2) ? jet_kernel_wide<ACT, NT, NX, BWD_, 128, BWD_ ? 2 : 4>                 \
-                                     : jet_kernel_wide<ACT, NT, NX, BWD_, 128, 4>;                           \
+                : na0 == 2 ? jet_kernel_wide<ACT, NT, NX, BWD_, 128, BWD_ ? 2 : 4>                           \
+                           : jet_kernel_wide<ACT, NT, NX, BWD_, 128, 4>;                                     \
     e = allow_full_lds(reinterpret_cast<const void*>(kern));                                                 \
     if (e != hipSuccess) return e;                                                                           \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, a);                                    \
@@ -882,12 +898,6 @@ hipError_t launch_jet_wide_act(const KernelArgs& a, bool bwd, int grid, hipStrea
   if (bwd) PINN_WLAUNCH1(true); else PINN_WLAUNCH1(false);
 #undef PINN_WLAUNCH1
   return hipGetLastError();
-}
-
-// activation id of the network -> index of the compiled activation family (piecewise-linear ones share RELU's kernels)
-inline int jet_wide_act_family(const KernelArgs& a) {
-  const int act = a.net.n_layers > 0 ? a.net.layer[0].act : a.net.enc_act;
-  return (act == PINN_ACT_TANH || act == PINN_ACT_SIN || act == PINN_ACT_GELU || act == PINN_ACT_SIGMOID) ? act : PINN_ACT_RELU;
 }
 
 // all activations from one translation unit (developer builds: tanh only)

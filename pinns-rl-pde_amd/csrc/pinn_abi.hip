@@ -216,6 +216,24 @@ __global__ __launch_bounds__(256) void wide_rows_reduce(const DetTable tab, cons
   }
 }
 
+// How a launch of the fused kernel reduces its weight gradients (and loss sum).  Reverse launches of networks whose MFMA
+// layers all keep their weight-gradient tiles in registers (n_layers <= kPersist: nothing is flushed inside the tile
+// loop) take the STORE flush, in both modes; otherwise PINN_FLAG_DETERMINISTIC takes one slab row per workgroup, and
+// a reverse launch of more than kFlushRows workgroups the TWO-LEVEL flush; everything else adds with direct atomics.
+enum WideFlush { FLUSH_DIRECT = 0, FLUSH_STORE = 1, FLUSH_TWO_LEVEL = 2, FLUSH_DET_SLAB = 3 };
+
+static WideFlush wide_flush(const PinnNetDesc* d, const NetDev& n, int grid, bool bwd) {
+  if (bwd && n.n_layers <= kPersist && wide_store_flush_on()) return FLUSH_STORE;
+  if (d->flags & PINN_FLAG_DETERMINISTIC) return FLUSH_DET_SLAB;
+  if (bwd && grid > kFlushRows) return FLUSH_TWO_LEVEL;
+  return FLUSH_DIRECT;
+}
+
+// slab rows a flush needs in the workspace (0: none)
+static int wide_slab_rows(WideFlush f, int grid) {
+  return f == FLUSH_DIRECT ? 0 : f == FLUSH_TWO_LEVEL ? kFlushRows : grid;
+}
+
 // redirect one accumulation target into the slab; returns the slab pointer (row 0)
 static float* det_slot(DetTable& t, float* slab, float* user, unsigned count) {
   if (!user) return nullptr;
@@ -376,12 +394,11 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
     // flushed inside the tile loop) take the STORE flush instead, in both modes: one slab row per workgroup, written
     // with plain stores, then wide_rows_reduce.  The last workgroups of a launch no longer spend 32 us adding 160 KB
     // at the memory-side atomic rate, and the slab needs no memset (jet_kernel_wide.h, end of the kernel).
-    const int shared_rows = kFlushRows;
-    const bool det_flag = (net->flags & PINN_FLAG_DETERMINISTIC) != 0;
-    const bool store_flush = bwd && a.net.n_layers <= kPersist && wide_store_flush_on();
-    const bool two_level = !det_flag && bwd && grid > shared_rows && !store_flush;
-    const bool det = det_flag || two_level || store_flush;
-    const int slab_rows = two_level ? shared_rows : grid;
+    const WideFlush flush = wide_flush(net, a.net, grid, bwd);
+    const bool store_flush = flush == FLUSH_STORE;
+    const bool two_level = flush == FLUSH_TWO_LEVEL;
+    const bool det = flush != FLUSH_DIRECT;
+    const int slab_rows = wide_slab_rows(flush, grid);
     const size_t tape_floats = bwd ? (size_t)jet_tape_floats_per_wg(K, a.net.n_layers, 1) * grid : 0;
     size_t need = tape_floats * sizeof(float);
     DetTable dt;
@@ -510,24 +527,53 @@ size_t pinn_workspace_bytes(const PinnNetDesc* net, int64_t N, int32_t time_orde
   const bool bwd = backward != 0;
   NetDev n;
   if (backward != 2 && use_wide(net, nullptr, nullptr, K, bwd, &n)) {  // 2: pinn_jet_backward_inputs, always layer-major
-    const size_t grid = (size_t)wide_grid(n, K, N, bwd);
+    const int grid = wide_grid(n, K, N, bwd);
     size_t bytes = bwd ? (size_t)jet_tape_floats_per_wg(K, n.n_layers, 1) * sizeof(float) * grid : 0;
-    if ((net->flags & PINN_FLAG_DETERMINISTIC) || (bwd && n.n_layers <= kPersist && wide_store_flush_on())) {
+    const int rows = wide_slab_rows(wide_flush(net, n, grid, bwd), grid);
+    if (rows > 0) {
       DetTable dt;
       float* lprobe = nullptr;
       float* cprobe = nullptr;
       det_redirect(n, lprobe, cprobe, nullptr, dt);
-      bytes += (size_t)dt.stride * grid * sizeof(float);
-    } else if (bwd && grid > (size_t)kFlushRows) {  // the two-level flush's shared rows
-      DetTable dt;
-      float* lprobe = nullptr;
-      float* cprobe = nullptr;
-      det_redirect(n, lprobe, cprobe, nullptr, dt);
-      bytes += (size_t)dt.stride * kFlushRows * sizeof(float);
+      bytes += (size_t)dt.stride * rows * sizeof(float);
     }
     return bytes;
   }
   return lm::lm_workspace_bytes(net, N, time_order, space_order, bwd, (net->flags & PINN_FLAG_DETERMINISTIC) != 0);
+}
+
+int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
+                    PinnKernelInfo* out) {
+  if (!net || !out) return fail(PINN_ERR_BAD_DESC, "null argument");
+  if (N <= 0) return fail(PINN_ERR_BAD_DESC, "N = %lld: a call on no points launches nothing", (long long)N);
+  if (backward < 0 || backward > 2) return fail(PINN_ERR_BAD_DESC, "backward = %d: 0, 1 or 2", backward);
+  int rc = check_orders(time_order, space_order);
+  if (rc) return rc;
+  if (!stream_set_compiled(time_order, space_order))
+    return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", time_order, space_order);
+  char lerr[256] = "";
+  if ((rc = lm::lm_check(net, lerr, sizeof(lerr)))) return fail(rc, "%s", lerr);
+  PinnKernelInfo r;
+  memset(&r, 0, sizeof(r));
+  r.time_order = time_order;
+  r.space_order = space_order;
+  r.backward = backward;
+  r.act_family = r.hmax = r.na0 = r.grid = r.flush = -1;
+  const int K = 1 + time_order + space_order;
+  const bool bwd = backward != 0;
+  NetDev n;
+  if (backward != 2 && use_wide(net, nullptr, nullptr, K, bwd, &n)) {  // the decisions run() makes, in the same helpers
+    r.engine = 1;
+    r.act_family = jet_wide_act_family(n);
+    jet_wide_variant(n, bwd, &r.hmax, &r.na0);
+    r.grid = wide_grid(n, K, N, bwd);
+    r.flush = wide_flush(net, n, r.grid, bwd);
+    char unit[64];  // pinn_build_info() lists the units built in the default MFMA form as "jet_wide_<nt>_<nx>_<family>: ..."
+    snprintf(unit, sizeof(unit), "jet_wide_%d_%d_%d:", time_order, space_order, r.act_family);
+    r.default_mfma_form = strstr(pinn_build_info(), unit) != nullptr;
+  }
+  *out = r;
+  return PINN_OK;
 }
 
 int pinn_jet_forward(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors, const float* x,

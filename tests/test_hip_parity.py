@@ -126,7 +126,9 @@ def test_jets_residual_loss_and_gradient(tag, engine, dev):
 
 def test_build_info_and_fallback_units(dev):
     """pinn_build_info() names every wide-kernel unit that had to be built in the default MFMA form; each such unit
-    still has to meet the parity bar (run one of them: wave needs stream set (2, 2))."""
+    still has to meet the parity bar (run one of them when none fell back: wave needs stream set (2, 2)).  Every call
+    asserts through pinn_kernel_for that the unit runs: the reverse sweep at width 64 (at 128 it takes the layer-major
+    engine for K >= 5 streams), the forward at width 128.  tests/test_wide_variants_gpu.py runs all their variants."""
     from pinnrl_amd import _lib
 
     from hip_helpers import pde_desc_from_spec, program_from_spec
@@ -140,26 +142,39 @@ def test_build_info_and_fallback_units(dev):
     pde_of = {(1, 1): "heat", (1, 2): "burgers", (1, 3): "kdv", (1, 4): "cahn_hilliard", (2, 2): "wave", (2, 0): "pendulum"}
     act_of = {v: k for k, v in _lib.ACT.items()}
     for nt, nx, act in units:
-        # width 128 is where the two MFMA forms differ most in register pressure; fourier covers encoder + MLP units
-        if act_of[int(act)] == "sin":  # the sine units are SIREN's
-            spec = O.ArchSpec("siren", hidden_dim=128, num_layers=3, omega_0=4.0)
-        else:
-            spec = O.ArchSpec("fourier", hidden_dim=128, num_layers=3, mapping_size=32, scale=3.0, activation=act_of[int(act)])
-        pde = O.PdeSpec(name=pde_of[(int(nt), int(nx))], parameters={"c": 1.3, "alpha": 0.05, "epsilon": 0.05})
-        sd = O.init_state_dict(spec, seed=int(nt) * 100 + int(nx) * 10 + int(act))
-        torch.manual_seed(7)
-        x, t = O.sample_uniform(pde, 400)
-        r_o, L_o, g_o = O.residual_loss_and_grad(pde, spec, {k: v.double() for k, v in sd.items()}, x.double(), t.double())
-        prog, names = program_from_spec(spec, sd, dev)
-        flat = E.new_flat_grad(prog, dev)
-        r, s = E.residual_loss_grad(prog, pde_desc_from_spec(pde), x.to(dev), t.to(dev), 1.0 / x.shape[0], flat, want_residual=True)
-        tol = TOL if act_of[int(act)] != "relu" else 1e-4  # relu kinks: a point within fp32 of 0 flips a branch
-        assert rel_l2(r.cpu(), r_o) <= tol, (nt, nx, act, rel_l2(r.cpu(), r_o))
-        by_name = {n: g for n, g in zip(names, E.split_flat_grad(prog, flat)) if g is not None}
-        keys = [k for k in g_o if k in by_name]
-        got = torch.cat([by_name[k].flatten().cpu() for k in keys])
-        want = torch.cat([g_o[k].flatten() for k in keys])
-        assert rel_l2(got, want) <= tol, (nt, nx, act, rel_l2(got, want))
+        nt, nx, act = int(nt), int(nx), int(act)
+        pde = O.PdeSpec(name=pde_of[(nt, nx)], parameters={"c": 1.3, "alpha": 0.05, "epsilon": 0.05})
+        tol = TOL if act_of[act] != "relu" else 1e-4  # relu kinks: a point within fp32 of 0 flips a branch
+        for width in (64, 128):
+            if act_of[act] == "sin":  # the sine units are SIREN's
+                spec = O.ArchSpec("siren", hidden_dim=width, num_layers=3, omega_0=4.0)
+            else:  # fourier covers encoder + MLP units
+                spec = O.ArchSpec("fourier", hidden_dim=width, num_layers=3, mapping_size=32, scale=3.0, activation=act_of[act])
+            sd = O.init_state_dict(spec, seed=nt * 100 + nx * 10 + act)
+            torch.manual_seed(7)
+            x, t = O.sample_uniform(pde, 400)
+            r_o, L_o, g_o = O.residual_loss_and_grad(pde, spec, {k: v.double() for k, v in sd.items()}, x.double(), t.double())
+            prog, names = program_from_spec(spec, sd, dev)
+            pd = pde_desc_from_spec(pde)
+            for bwd in (0, 1):
+                route = _lib.kernel_for(prog, x.shape[0], nt, nx, bwd)
+                if bwd and width == 128 and 1 + nt + nx >= 5:
+                    assert route["engine"] == "layer_major", route
+                    continue
+                assert route["engine"] == "tile_major" and route["act_family"] == act, route
+                assert route["hmax"] == width and route["default_mfma_form"] == (f"jet_wide_{nt}_{nx}_{act}:" in info), route
+                if not bwd:
+                    r, s = E.residual_forward(prog, pd, x.to(dev), t.to(dev))
+                    assert rel_l2(r.cpu(), r_o) <= tol, (nt, nx, act, width, rel_l2(r.cpu(), r_o))
+                    continue
+                flat = E.new_flat_grad(prog, dev)
+                r, s = E.residual_loss_grad(prog, pd, x.to(dev), t.to(dev), 1.0 / x.shape[0], flat, want_residual=True)
+                assert rel_l2(r.cpu(), r_o) <= tol, (nt, nx, act, width, rel_l2(r.cpu(), r_o))
+                by_name = {n: g for n, g in zip(names, E.split_flat_grad(prog, flat)) if g is not None}
+                keys = [k for k in g_o if k in by_name]
+                got = torch.cat([by_name[k].flatten().cpu() for k in keys])
+                want = torch.cat([g_o[k].flatten() for k in keys])
+                assert rel_l2(got, want) <= tol, (nt, nx, act, width, rel_l2(got, want))
 
 
 @pytest.mark.parametrize("tag", ["burgers_fourier_3x32", "burgers_feedforward_3x32", "kdv_siren_3x32"])
