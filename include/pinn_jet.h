@@ -58,6 +58,8 @@ extern "C" {
                                      bit-reproducible either way) */
 #define PINN_FLAG_LAYER_MAJOR 4   /* engine hint: run the layer-major engine even where the fused tile-major kernel
                                      applies (same results to rounding; tests run both) */
+#define PINN_FLAG_WIDE_TILE32 8   /* engine hint: reverse launches of the fused tile-major kernel keep the 32-point kernel
+                                     where the 16-point one would run (A/B runs and tests; same results to rounding) */
 
 typedef enum PinnStatus {
   PINN_OK = 0,
@@ -161,6 +163,11 @@ typedef struct PinnKernelInfo {
 } PinnKernelInfo;
 int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
                     PinnKernelInfo* out);
+/* Name of the kernel such a call takes, written NUL-terminated into buf (at most len bytes): "jet_kernel_u16" (fused
+ * tile-major, 16-point units, reverse launches), "jet_kernel_wide" (fused tile-major, 32-point tiles) or "layer_major".
+ * PINN_OK, or the PinnStatus pinn_kernel_for returns for the same arguments. */
+int pinn_kernel_name(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
+                     char* buf, size_t len);
 
 /* Every compute entry point: `weights` (and `weight_grads`) are tables of `num_tensors` device pointers in the
  * reference's state_dict order; the count is validated against the descriptor BEFORE any entry is read.

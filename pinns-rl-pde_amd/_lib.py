@@ -17,6 +17,7 @@ PINN_MAX_STREAMS = 7
 PINN_FLAG_LAYER_NORM = 1
 PINN_FLAG_DETERMINISTIC = 2
 PINN_FLAG_LAYER_MAJOR = 4
+PINN_FLAG_WIDE_TILE32 = 8
 
 ARCH = {"feedforward": 0, "fourier": 1, "siren": 2, "resnet": 3, "attention": 4}
 ACT = {"tanh": 0, "sin": 1, "gelu": 2, "sigmoid": 3, "relu": 4, "leaky_relu": 5, "identity": 6}
@@ -30,7 +31,7 @@ EXPORTS = (
     "pinn_abi_version", "pinn_last_error", "pinn_build_info", "pinn_num_tensors", "pinn_pde_streams",
     "pinn_workspace_bytes", "pinn_jet_forward", "pinn_jet_backward", "pinn_residual_forward", "pinn_residual_backward",
     "pinn_residual_loss_grad", "pinn_residual_loss_grad_coef", "pinn_point_losses", "pinn_jet_losses", "pinn_adam_clip_step",
-    "pinn_jet_backward_inputs", "pinn_kernel_for",
+    "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name",
 )
 
 
@@ -114,6 +115,8 @@ def load():
         sz = ctypes.c_size_t
         lib.pinn_kernel_for.restype = ctypes.c_int
         lib.pinn_kernel_for.argtypes = [P(PinnNetDesc), i64, i32, i32, i32, P(PinnKernelInfo)]
+        lib.pinn_kernel_name.restype = ctypes.c_int
+        lib.pinn_kernel_name.argtypes = [P(PinnNetDesc), i64, i32, i32, i32, ctypes.c_char_p, sz]
         lib.pinn_jet_forward.restype = ctypes.c_int
         lib.pinn_jet_forward.argtypes = [P(PinnNetDesc), P(vp), i32, vp, vp, i64, i32, i32, P(vp), vp, sz, vp]
         lib.pinn_jet_backward.restype = ctypes.c_int
@@ -163,6 +166,14 @@ def kernel_for(prog, N: int, nt: int, nx: int, backward: int) -> dict:
     out["flush"] = FLUSH.get(info.flush)
     out["default_mfma_form"] = bool(info.default_mfma_form)
     return out
+
+
+def kernel_name(prog, N: int, nt: int, nx: int, backward: int) -> str:
+    """Name of the kernel such a call takes (pinn_kernel_name): "jet_kernel_u16" (fused tile-major, 16-point units,
+    reverse launches), "jet_kernel_wide" (fused tile-major, 32-point tiles) or "layer_major"."""
+    buf = ctypes.create_string_buffer(64)
+    check(load().pinn_kernel_name(ctypes.byref(prog.desc), int(N), int(nt), int(nx), int(backward), buf, len(buf)))
+    return buf.value.decode("ascii")
 
 
 def check(rc: int) -> None:

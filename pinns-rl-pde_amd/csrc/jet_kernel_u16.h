@@ -1,0 +1,638 @@
+// Fused forward + reverse tile-major kernel on 16-point units: eight waves per workgroup, v_mfma_f32_16x16x4_f32,
+// tape held in LDS.  It serves reverse launches of the store-flush class of jet_kernel_wide.h
+// (plain MLPs whose MFMA layers all keep their weight gradients in registers: 1 <= n_layers <= kPersist) at image
+// height 128, and the forward-only launches of the same networks (BWD = false), so that both give bit-identical
+// per-point results; every other call keeps the 32-point kernel.
+//
+//   * One 512-thread workgroup per CU, two waves per SIMD.  Wave w owns feature rows 16w .. 16w+15 of every layer:
+//     forward z = W a, reverse abar = W^T zbar (its input-feature rows) and dW += zbar a^T (its output rows), so the
+//     persistent weight-gradient tiles are split eight ways (80 VGPRs for the headline network instead of 160).
+//   * Workgroup b takes 16-point units b, b + grid, ... of ceil(N / 16): the grid stays min(CUs, ceil(N / 32)), so
+//     every workgroup does about two units per 32-point tile of the older kernel, and the last round is half as long.
+//   * Activation images are [stream][point][feature] with a row of kUP = 132 floats.  In the forward and abar GEMMs
+//     lane group g = lane >> 4 takes features 16b + 4g + m at MFMA step m = 0..3, so one ds_read_b128 of four
+//     consecutive features feeds four 16x16x4 MFMAs, and a producer lane, which holds rows 4g .. 4g+3 of its
+//     accumulator for point lane & 15, writes them back with one ds_write_b128.  The 4-float row pad (instead of an
+//     XOR swizzle) keeps every LDS access base register + immediate offset; it leaves one 2-way bank conflict in
+//     one of the four lane groups of a b128 read.  The dW GEMM sums over points and reads both operands with
+//     conflict-free ds_read_b32.
+//   * The pre-activation records that the reverse sweep replays (layers 0 .. n_layers - 2) stay in two LDS images,
+//     and the last layer's record is parked in the wave's own columns of the idle a_{l-1} image: no tape in global
+//     memory, no workspace besides the store-flush slab.
+//   * No atomics: per-lane partial sums (db, dw_out, db_out, loss) and the weight-gradient tiles are written once per
+//     workgroup into row blockIdx.x of the slab, and units run in a fixed order, so results are bitwise
+//     reproducible from run to run.
+#pragma once
+#include "jet_kernel_wide.h"
+
+namespace pinn {
+
+constexpr int kU = 16;          // points per unit
+constexpr int kUP = 132;        // LDS row of an image: 128 features + 4 floats of pad
+constexpr int kUThreads = 512;  // 8 waves
+constexpr int kUWaves = 8;
+constexpr int kUH = 128;        // image height (features)
+constexpr int kUImgS = kU * kUP;  // floats per stream of an image
+
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// pre-activation jets of encoding feature j at point n of the unit (xin: [c][kU])
+template <int NT, int NX>
+__device__ __forceinline__ void u16_enc_preact(const float* ep, int din, const float* xin, int j, int n, float* z) {
+  constexpr int K = 1 + NT + NX;
+#pragma unroll
+  for (int s = 0; s < K; ++s) z[s] = 0.0f;
+  float v = ep[kMaxDin * kUH + j];
+  float wt = 0.0f;
+#pragma unroll
+  for (int c = 0; c < kMaxDin; ++c) {
+    const float w = ep[c * kUH + j];  // zero beyond din
+    v = fmaf(xin[c * kU + n], w, v);
+    wt = c == din - 1 ? w : wt;
+  }
+  z[0] = v;
+  if constexpr (NT >= 1) z[1] = wt;
+  if constexpr (NX >= 1) z[1 + NT] = ep[j];
+}
+
+// encoding into an image dst[s][n][f]; thread -> (point tid & 15, feature tid >> 4 + 32 i)
+template <int ACT, int NT, int NX>
+__device__ __forceinline__ void u16_encode(const NetDev& net, const float* ep, const float* xin, float* dst, int tid) {
+  constexpr int K = 1 + NT + NX;
+  const int n = tid & 15;
+  const int din = net.din;
+  float* row = dst + n * kUP;
+  if (net.enc == ENC_FOURIER) {
+    const int M = net.enc_out >> 1;
+#pragma unroll 1
+    for (int m = tid >> 4; m < M; m += kUThreads / kU) {
+      float z[K], ys[K], yc[K];
+      u16_enc_preact<NT, NX>(ep, din, xin, m, n, z);
+      float sn, cs;
+      fast_sincosf(z[0], &sn, &cs);
+      const float fs[6] = {sn, cs, -sn, -cs, sn, cs};
+      const float fc[6] = {cs, -sn, -cs, sn, cs, -sn};
+      ys[0] = sn;
+      yc[0] = cs;
+      dir_fwd<NT>(fs, z + 1, ys + 1);
+      dir_fwd<NX>(fs, z + 1 + NT, ys + 1 + NT);
+      dir_fwd<NT>(fc, z + 1, yc + 1);
+      dir_fwd<NX>(fc, z + 1 + NT, yc + 1 + NT);
+#pragma unroll
+      for (int s = 0; s < K; ++s) {
+        row[s * kUImgS + m] = ys[s];
+        row[s * kUImgS + M + m] = yc[s];
+      }
+    }
+  } else {
+    const int H = net.enc_out;
+#pragma unroll 1
+    for (int f = tid >> 4; f < H; f += kUThreads / kU) {
+      float z[K], y[K];
+      u16_enc_preact<NT, NX>(ep, din, xin, f, n, z);
+      act_fwd<ACT, NT, NX>(net.enc_param, z, y);
+#pragma unroll
+      for (int s = 0; s < K; ++s) row[s * kUImgS + f] = y[s];
+    }
+  }
+}
+
+// Weight operand of block b (16 k): rows form (z = W a) one 16-byte load of W[16w + c][16b + 4g .. +3]; columns form
+// (abar = W^T zbar) four loads W[16b + 4g + m][16w + c].  W is wave-uniform (scalar base), the lane part is a 32-bit
+// byte offset (u16_rows_off / u16_cols_off): no per-lane 64-bit addresses, which the optimizer hoists out of the unit
+// loop and then spills.
+__device__ __forceinline__ unsigned u16_rows_off(int row0, int ld, int c, int g) {
+  return static_cast<unsigned>((row0 + c) * ld + 4 * g) * 4u;
+}
+__device__ __forceinline__ unsigned u16_cols_off(int col0, int ld, int c, int g) {
+  return static_cast<unsigned>(4 * g * ld + col0 + c) * 4u;
+}
+template <bool COLS>
+__device__ __forceinline__ f32x4 u16_wload(const float* W, int ld, unsigned off, int b) {
+  if constexpr (COLS) {
+    f32x4 v;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) v[m] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(W + (long long)(16 * b + m) * ld) + off);
+    return v;
+  } else {
+    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(W + 16 * b) + off);
+  }
+}
+
+// acc[s] += W-slice . X[s][c][:] over depth 16 NB; xl = X + c kUP + 4g.  Weights are requested two blocks ahead of
+// their MFMAs (blocks 0 and 1 by the caller, a phase earlier), image operands one block ahead.
+template <int K, int NB, bool COLS>
+__device__ __forceinline__ void u16_gemm_n(f32x4 (&acc)[K], const float* W, int ld, unsigned off, f32x4 w0, f32x4 w1, const float* xl) {
+  f32x4 wq[3];
+  wq[0] = w0;
+  wq[1] = w1;
+  f32x4 bc[K], bn[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s) bc[s] = *reinterpret_cast<const f32x4*>(xl + s * kUImgS);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    if (b + 2 < NB) wq[(b + 2) % 3] = u16_wload<COLS>(W, ld, off, b + 2);
+    if (b + 1 < NB) {
+#pragma unroll
+      for (int s = 0; s < K; ++s) bn[s] = *reinterpret_cast<const f32x4*>(xl + s * kUImgS + 16 * (b + 1));
+    }
+    // keep the operand requests of block b+1 ahead of the MFMAs of block b
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int s = 0; s < K; ++s) acc[s] = mfma16(wq[b % 3][m], bc[s][m], acc[s]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (b + 1 < NB) {
+#pragma unroll
+      for (int s = 0; s < K; ++s) bc[s] = bn[s];
+    }
+  }
+}
+
+// depth = 16 nb (nb wave-uniform)
+template <int K, bool COLS>
+__device__ __forceinline__ void u16_gemm(f32x4 (&acc)[K], const float* W, int ld, unsigned off, f32x4 w0, f32x4 w1, int nb, const float* xl) {
+  switch (nb) {
+    case 8: u16_gemm_n<K, 8, COLS>(acc, W, ld, off, w0, w1, xl); return;
+    case 4: u16_gemm_n<K, 4, COLS>(acc, W, ld, off, w0, w1, xl); return;
+    default: break;
+  }
+#pragma unroll 1
+  for (int b = 0; b < nb; ++b) {
+    const f32x4 w = b == 0 ? w0 : b == 1 ? w1 : u16_wload<COLS>(W, ld, off, b);
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int s = 0; s < K; ++s) acc[s] = mfma16(w[m], xl[s * kUImgS + 16 * b + m], acc[s]);
+  }
+}
+
+// pt[OFF + t] += sum_s Z_s[own rows][points] A_s[16t + j][points]^T, t < NA.  Point order: lane group g takes point
+// 4g + m at step m; zl = Z + 4g kUP + 16w + c, al = A + 4g kUP + c (ds_read_b32, conflict-free)
+template <int K, int NA, int OFF, int NPT>
+__device__ __forceinline__ void u16_outer_n(f32x4 (&pt)[NPT], const float* zl, const float* al) {
+  float zc, zn, ac[NA], an[NA];
+  zc = zl[0];
+#pragma unroll
+  for (int t = 0; t < NA; ++t) ac[t] = al[16 * t];
+#pragma unroll
+  for (int st = 0; st < 4 * K; ++st) {  // step = (stream s, point m)
+    if (st + 1 < 4 * K) {
+      const int s = (st + 1) >> 2, m = (st + 1) & 3;
+      zn = zl[s * kUImgS + m * kUP];
+#pragma unroll
+      for (int t = 0; t < NA; ++t) an[t] = al[s * kUImgS + m * kUP + 16 * t];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < NA; ++t) pt[OFF + t] = mfma16(zc, ac[t], pt[OFF + t]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (st + 1 < 4 * K) {
+      zc = zn;
+#pragma unroll
+      for (int t = 0; t < NA; ++t) ac[t] = an[t];
+    }
+  }
+}
+
+// na = in_dim / 16 (wave-uniform).  A narrower layer than NMAX runs the NMAX form when na is not NMAX / 2: the
+// extra tiles read image columns beyond in_dim and are never flushed.
+template <int K, int OFF, int NMAX, int NPT>
+__device__ __forceinline__ void u16_outer(f32x4 (&pt)[NPT], int na, const float* zl, const float* al) {
+  if constexpr (NMAX >= 8) {
+    if (na * 2 == NMAX) { u16_outer_n<K, NMAX / 2, OFF, NPT>(pt, zl, al); return; }
+  }
+  u16_outer_n<K, NMAX, OFF, NPT>(pt, zl, al);
+}
+
+// forward activation jets of the accumulator (rows 16w + 4g + r, point c); rec gets the tape record
+template <int ACT, int NT, int NX>
+__device__ __forceinline__ void u16_ew_forward(f32x4 (&v)[1 + NT + NX], float w, f32x4 (&rec)[1 + NT + NX]) {
+  constexpr int K = 1 + NT + NX;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float z[K], y[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) z[s] = v[s][r];
+    act_fwd<ACT, NT, NX>(w, z, y);
+    rec[0][r] = ActTape<ACT>::value_is_output ? y[0] : z[0];
+#pragma unroll
+    for (int s = 1; s < K; ++s) rec[s][r] = z[s];
+#pragma unroll
+    for (int s = 0; s < K; ++s) v[s][r] = y[s];
+  }
+}
+
+template <int K>
+__device__ __forceinline__ void u16_put(float* il, const f32x4 (&v)[K]) {  // il = image + c kUP + 16w + 4g
+#pragma unroll
+  for (int s = 0; s < K; ++s) *reinterpret_cast<f32x4*>(il + s * kUImgS) = v[s];
+}
+template <int K>
+__device__ __forceinline__ void u16_get(const float* il, f32x4 (&v)[K]) {
+#pragma unroll
+  for (int s = 0; s < K; ++s) v[s] = *reinterpret_cast<const f32x4*>(il + s * kUImgS);
+}
+
+// activation adjoint of the accumulator rows with record rec
+template <int ACT, int NT, int NX>
+__device__ __forceinline__ void u16_ew_backward(f32x4 (&ab)[1 + NT + NX], float w, const f32x4 (&rec)[1 + NT + NX]) {
+  constexpr int K = 1 + NT + NX;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float z[K], abv[K], zb[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      z[s] = rec[s][r];
+      abv[s] = ab[s][r];
+    }
+    act_bwd_tape<ACT, NT, NX>(w, z, abv, zb);
+#pragma unroll
+    for (int s = 0; s < K; ++s) ab[s][r] = zb[s];
+  }
+}
+
+// sum over the 64 lanes of a wave of lanes with (lane & 15) == 0 .. 15 folded: every lane gets the sum over its
+// 16-lane row (row16_sum) — used for per-feature sums over the points of a unit
+__device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = row16_sum(v[r]);
+  return v;
+}
+
+// NA0: 16-feature k-tiles of the first MFMA layer's weight-gradient accumulators (4: at most 64 input features)
+// BWD = false: the forward-only launch of the same networks.  It runs the forward code of the reverse launch unchanged,
+// so a forward-only call and a fused call give bit-identical per-point results.
+template <int ACT, int NT, int NX, bool BWD, int NA0>
+__global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs a) {
+  constexpr int K = 1 + NT + NX;
+  constexpr int NKT = kUH / 16;
+  constexpr int NPT = NA0 + (kPersist - 1) * NKT;
+  static_assert(kPersist == 3, "the layer -> tile-offset table below is written for three persistent layers");
+  constexpr int img = K * kUImgS;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const NetDev& net = a.net;
+  float* X = smem;                    // forward activations; zbar in the reverse sweep
+  float* A2 = X + img;                // reverse sweep: a_{l-1}; forward: the last layer's parked record
+  float* REC = A2 + img;              // records of layers 0, 1 (replayed in the reverse sweep)
+  float* UP = REC + 2 * img;          // kUWaves * K * kU: per-wave partial sums of the output layer
+  float* xin = UP + kUWaves * K * kU;  // kMaxDin * kU
+  float* wb = xin + kMaxDin * kU;      // (1 + n_layers) * 128: w_out, then the hidden-layer biases
+  float* ep = wb + (1 + kPersist) * kUH;  // (kMaxDin + 1) * 128: encoding parameters
+  float* pl = ep + (kMaxDin + 1) * kUH;   // (kPersist + kMaxDin + 1) * 128: per-feature db of the MFMA layers, then the
+                                          // first-Linear gradient partials (thread tid < 128 owns feature tid)
+
+  const int tid = threadIdx.x;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int g = lane >> 4, c = lane & 15;
+  const int din = net.din;
+  const int nl = net.n_layers;
+  const long long nunits = (a.N + kU - 1) / kU;
+  const int frow = 16 * wv + 4 * g;  // first of this lane's four accumulator rows
+  const int ioff = c * kUP + frow;   // this lane's 16-byte word of an image (point c, rows frow .. frow+3)
+
+  for (int k = tid; k < kUH; k += kUThreads) {
+    wb[k] = k < net.h_last ? net.w_out[k] : 0.0f;
+    for (int l = 0; l < nl; ++l) wb[(1 + l) * kUH + k] = k < net.layer[l].out_dim ? net.layer[l].b[k] : 0.0f;
+  }
+  stage_enc_params<kUH>(net, ep, tid);
+#pragma unroll
+  for (int i = 0; i < kPersist + kMaxDin + 1; ++i)
+    if (tid < kUH) pl[i * kUH + tid] = 0.0f;
+  const float b_out0 = net.b_out[0];
+
+  f32x4 pt[NPT];
+#pragma unroll
+  for (int t = 0; t < NPT; ++t) pt[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 pdw = {0.0f, 0.0f, 0.0f, 0.0f};  // per-lane partial dw_out
+  float pdb_out = 0.0f, ploss = 0.0f;
+
+  float xr[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
+  auto fetch_coords = [&](long long u) {
+    if (tid < kU) {
+      const long long p = u * kU + tid;
+      const bool ok = u < nunits && p < a.N;
+#pragma unroll
+      for (int cc = 0; cc < kMaxDin; ++cc) {
+        if (cc < din - 1) xr[cc] = ok ? a.x[p * (din - 1) + cc] : 0.0f;
+        if (cc == din - 1) xr[cc] = ok ? a.t[p] : 0.0f;
+      }
+    }
+  };
+  fetch_coords(blockIdx.x);
+
+  for (long long u = blockIdx.x; u < nunits; u += gridDim.x) {
+    const long long p0 = u * kU;
+    __syncthreads();  // previous unit's readers of xin / X / A2 / UP are done
+    if (tid < kU) {
+#pragma unroll
+      for (int cc = 0; cc < kMaxDin; ++cc) xin[cc * kU + tid] = xr[cc];
+    }
+    fetch_coords(u + gridDim.x);
+    f32x4 w0, w1;  // first two weight blocks of the next GEMM, requested a phase ahead
+    {
+      const LayerDev L0 = uniform_layer(net.layer[0]);
+      const unsigned off = u16_rows_off(16 * wv < L0.out_dim ? 16 * wv : 0, L0.ld, c, g);
+      w0 = u16_wload<false>(L0.W, L0.ld, off, 0);
+      w1 = u16_wload<false>(L0.W, L0.ld, off, L0.in_dim > 16 ? 1 : 0);
+    }
+    __syncthreads();
+    u16_encode<ACT, NT, NX>(net, ep, xin, X, tid);
+    __syncthreads();
+
+    // ---- hidden layers ----
+    f32x4 acc[K];
+    for (int l = 0; l < nl; ++l) {
+      const LayerDev Ly = uniform_layer(net.layer[l]);
+      const bool on = 16 * wv < Ly.out_dim;
+      const bool last = l + 1 == nl;
+#pragma unroll
+      for (int s = 0; s < K; ++s) acc[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (on) {
+        u16_gemm<K, false>(acc, Ly.W, Ly.ld, u16_rows_off(16 * wv, Ly.ld, c, g), w0, w1, Ly.in_dim >> 4, X + c * kUP + 4 * g);
+        acc[0] += *reinterpret_cast<const f32x4*>(wb + (1 + l) * kUH + frow);
+      }
+      if (!last) {
+        {
+          const LayerDev Ln = uniform_layer(net.layer[l + 1]);
+          const unsigned off = u16_rows_off(16 * wv < Ln.out_dim ? 16 * wv : 0, Ln.ld, c, g);
+          w0 = u16_wload<false>(Ln.W, Ln.ld, off, 0);  // latency hides under the jets
+          w1 = u16_wload<false>(Ln.W, Ln.ld, off, Ln.in_dim > 16 ? 1 : 0);
+        }
+        if (on) {  // the record goes to this wave's own columns: nobody else reads them in the forward sweep
+          f32x4 rec[K];
+          u16_ew_forward<ACT, NT, NX>(acc, Ly.act_param, rec);
+          if constexpr (BWD) u16_put<K>(REC + l * img + ioff, rec);
+        }
+        __syncthreads();  // every wave has finished reading X: overwrite in place
+        if (on) u16_put<K>(X + ioff, acc);
+        __syncthreads();
+      } else if (on) {  // last hidden layer: activations stay in acc, the record is parked in this wave's columns of A2
+        f32x4 rec[K];
+        u16_ew_forward<ACT, NT, NX>(acc, Ly.act_param, rec);
+        if constexpr (BWD) u16_put<K>(A2 + ioff, rec);
+      }
+    }
+
+    // ---- output layer (H_last -> 1): lane partials -> wave partials in LDS -> every lane sums ----
+    {
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(wb + frow);
+      float po[K];
+#pragma unroll
+      for (int s = 0; s < K; ++s) {
+        po[s] = fmaf(w4[0], acc[s][0], fmaf(w4[1], acc[s][1], fmaf(w4[2], acc[s][2], w4[3] * acc[s][3])));
+        po[s] += __shfl_xor(po[s], 16);
+        po[s] += __shfl_xor(po[s], 32);
+      }
+      if (g == 0) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) UP[(wv * K + s) * kU + c] = po[s];
+      }
+    }
+    __syncthreads();
+
+    // ---- epilogue, evaluated by every lane for its point c (32 lanes per point, same values) ----
+    float ub[K];
+    {
+      const long long p = p0 + c;
+      const bool ok = p < a.N;
+      const bool writer = tid < kU;
+      float j[K];
+#pragma unroll
+      for (int s = 0; s < K; ++s) {
+        float v = s == 0 ? b_out0 : 0.0f;
+#pragma unroll
+        for (int w = 0; w < kUWaves; ++w) v += UP[(w * K + s) * kU + c];
+        j[s] = v;
+      }
+      if (a.mode == MODE_JETS) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+          if (writer && ok && a.jets_out[s]) a.jets_out[s][p] = j[s];
+          ub[s] = (BWD && ok && a.jets_bar[s]) ? a.jets_bar[s][p] : 0.0f;
+        }
+      } else {
+        float d[K];
+        const float r = pde_residual<NT, NX>(a.pde, j, xin[c], d);
+        float dl;
+        float lt = loss_term(a.pde, r, &dl);
+        if (!ok) {
+          lt = 0.0f;
+          dl = 0.0f;
+        }
+        if (writer && ok && a.residual_out) a.residual_out[p] = r;
+        if (writer) ploss += lt;
+        const float rb = !BWD ? 0.0f : a.res_bar ? (ok ? a.res_bar[p] : 0.0f) : a.grad_scale * dl;
+#pragma unroll
+        for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
+      }
+    }
+
+    if constexpr (!BWD) continue;
+    // ---- B0: output layer.  dw_out partials stay per lane; abar = w_out (x) ub, then the last layer's adjoint ----
+    if (tid < kU) pdb_out += ub[0];
+    f32x4 ab[K];
+    {
+      const LayerDev Lz = uniform_layer(net.layer[nl - 1]);
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(wb + frow);
+#pragma unroll
+      for (int s = 0; s < K; ++s) ab[s] = w4 * ub[s];
+      if (16 * wv < Lz.out_dim) {
+        f32x4 rec[K];
+        u16_get<K>(A2 + ioff, rec);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float z[K], y[K];
+#pragma unroll
+          for (int s = 0; s < K; ++s) z[s] = rec[s][r];
+          act_fwd_tape<ACT, NT, NX>(Lz.act_param, z, y);
+          float gg = 0.0f;
+#pragma unroll
+          for (int s = 0; s < K; ++s) gg = fmaf(ub[s], y[s], gg);
+          pdw[r] += gg;
+        }
+        u16_ew_backward<ACT, NT, NX>(ab, Lz.act_param, rec);
+      }
+    }
+
+    for (int l = nl - 1; l >= 0; --l) {
+      const LayerDev Ly = uniform_layer(net.layer[l]);
+      const bool on = 16 * wv < Ly.out_dim;
+      const bool need_abar = l > 0 || net.enc == ENC_LINEAR;
+      const bool kon = 16 * wv < Ly.in_dim;  // this wave owns input-feature rows of the layer
+      // the GEMMs of layer l+1 have finished reading X (zbar) and A2; with a single MFMA layer the barrier keeps
+      // u16_encode (all columns of A2, below) from overwriting another wave's parked record before its B0 has read it
+      if (l + 1 < nl || nl == 1) __syncthreads();
+      if (on) u16_put<K>(X + ioff, ab);
+      float pw = 0.0f;  // act_param of layer l-1
+      if (l > 0) {
+        const LayerDev P = uniform_layer(net.layer[l - 1]);
+        pw = P.act_param;
+        if (kon) {  // replay a_{l-1} from its record into this wave's columns of A2
+          f32x4 rec[K], y[K];
+          u16_get<K>(REC + (l - 1) * img + ioff, rec);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float z[K], yy[K];
+#pragma unroll
+            for (int s = 0; s < K; ++s) z[s] = rec[s][r];
+            act_fwd_tape<ACT, NT, NX>(pw, z, yy);
+#pragma unroll
+            for (int s = 0; s < K; ++s) y[s][r] = yy[s];
+          }
+          u16_put<K>(A2 + ioff, y);
+        }
+      } else {
+        u16_encode<ACT, NT, NX>(net, ep, xin, A2, tid);
+      }
+      const unsigned coff = u16_cols_off(kon ? 16 * wv : 0, Ly.ld, c, g);
+      if (need_abar) {  // requests hide under the barrier
+        w0 = u16_wload<true>(Ly.W, Ly.ld, coff, 0);
+        w1 = u16_wload<true>(Ly.W, Ly.ld, coff, 1);
+      }
+      __syncthreads();
+      if (Ly.db && tid < Ly.out_dim) {
+        float gsum = 0.0f;
+#pragma unroll
+        for (int n = 0; n < kU; ++n) gsum += X[n * kUP + tid];
+        pl[l * kUH + tid] += gsum;
+      }
+      // abar_{l-1} = W^T zbar for all streams
+      if (need_abar) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) ab[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (kon) u16_gemm<K, true>(ab, Ly.W, Ly.ld, coff, w0, w1, Ly.out_dim >> 4, X + c * kUP + 4 * g);
+      }
+      // dW (persistent), then the activation adjoint of layer l-1
+      if (on && Ly.dW) {
+        const float* zl = X + 4 * g * kUP + 16 * wv + c;
+        const float* al = A2 + 4 * g * kUP + c;
+        const int na = Ly.in_dim >> 4;
+        if (l == 0) u16_outer<K, 0, NA0, NPT>(pt, na, zl, al);
+        else if (l == 1) u16_outer<K, NA0, NKT, NPT>(pt, na, zl, al);
+        else u16_outer<K, NA0 + NKT, NKT, NPT>(pt, na, zl, al);
+      }
+      if (l > 0 && kon) {
+        f32x4 rec[K];
+        u16_get<K>(REC + (l - 1) * img + ioff, rec);
+        u16_ew_backward<ACT, NT, NX>(ab, pw, rec);
+      }
+    }
+
+    // ---- encoding backward (first Linear of feedforward / SIREN) ----
+    if (net.enc == ENC_LINEAR && net.d_encW) {
+      const int H = net.enc_out;
+      __syncthreads();
+      if (16 * wv < H) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float z[K], abv[K], zb[K];
+          u16_enc_preact<NT, NX>(ep, din, xin, frow + r, c, z);
+#pragma unroll
+          for (int s = 0; s < K; ++s) abv[s] = ab[s][r];
+          act_bwd<ACT, NT, NX>(net.enc_param, z, abv, zb);
+#pragma unroll
+          for (int s = 0; s < K; ++s) ab[s][r] = zb[s];
+        }
+        u16_put<K>(X + ioff, ab);
+      }
+      __syncthreads();
+      if (tid < H) {
+        float gb = 0.0f, gt = 0.0f, gx = 0.0f;
+        float gw[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 4
+        for (int n = 0; n < kU; ++n) {
+          const float vv = X[n * kUP + tid];
+          gb += vv;
+#pragma unroll
+          for (int cc = 0; cc < kMaxDin; ++cc)
+            if (cc < din) gw[cc] = fmaf(vv, xin[cc * kU + n], gw[cc]);
+          if constexpr (NT >= 1) gt += X[1 * kUImgS + n * kUP + tid];
+          if constexpr (NX >= 1) gx += X[(1 + NT) * kUImgS + n * kUP + tid];
+        }
+#pragma unroll
+        for (int cc = 0; cc < kMaxDin; ++cc) pl[(kPersist + cc) * kUH + tid] += gw[cc] + (cc == din - 1 ? gt : 0.0f) + (cc == 0 ? gx : 0.0f);
+        pl[(kPersist + kMaxDin) * kUH + tid] += gb;
+      }
+    }
+  }
+
+  // ---- one flush per workgroup: reverse launches store into row blockIdx.x of the slab (a.flush_store: every address
+  // written once); a forward-only launch adds its loss sum as the 32-point kernel does ----
+  const long long doff = det_row_offset(a);
+  if (a.mode == MODE_PDE && a.loss_sum && wv == 0) {
+    float sacc = tid < kU ? ploss : 0.0f;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) sacc += __shfl_xor(sacc, o);
+    if (tid == 0) grad_put(a.loss_sum, sacc, doff, a.flush_store != 0);
+  }
+  if constexpr (!BWD) return;
+  if (net.db_out && wv == 0) {
+    float gsum = tid < kU ? pdb_out : 0.0f;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) gsum += __shfl_xor(gsum, o);
+    if (tid == 0) net.db_out[doff] = gsum;
+  }
+  if (net.enc == ENC_LINEAR && net.d_encW && tid < net.enc_out) {
+#pragma unroll
+    for (int cc = 0; cc < kMaxDin; ++cc)
+      if (cc < din) net.d_encW[doff + tid * din + cc] = pl[(kPersist + cc) * kUH + tid];
+    if (net.d_encb) net.d_encb[doff + tid] = pl[(kPersist + kMaxDin) * kUH + tid];
+  }
+  pdw = row16_sum4(pdw);
+  if (net.dw_out && c == 0 && frow < net.h_last) *reinterpret_cast<f32x4*>(net.dw_out + doff + frow) = pdw;
+#pragma unroll
+  for (int p = 0; p < kPersist; ++p) {
+    if (p < nl) {
+      const LayerDev Lp = uniform_layer(net.layer[p]);
+      if (Lp.db && tid < Lp.out_dim) Lp.db[doff + tid] = pl[p * kUH + tid];
+      if (16 * wv >= Lp.out_dim) continue;
+      if (Lp.dW) {
+        const int na = Lp.in_dim >> 4;
+        const int off = p == 0 ? 0 : p == 1 ? NA0 : NA0 + NKT;
+        float* base = Lp.dW + doff + (long long)frow * Lp.ld + c;
+#pragma unroll
+        for (int t = 0; t < NPT; ++t) {
+          if (t >= off && t - off < na && (p != 0 || t < NA0) && (p != 1 || t < NA0 + NKT)) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) base[(long long)r * Lp.ld + 16 * (t - off)] = pt[t][r];
+          }
+        }
+      }
+    }
+  }
+}
+
+inline size_t jet_u16_lds_bytes(int K) {
+  return sizeof(float) * ((size_t)4 * K * kUImgS + kUWaves * K * kU + kMaxDin * kU + (1 + kPersist) * kUH +
+                          (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH);
+}
+
+
+// The 16-point kernel can run the reverse launch of this network, and then runs its forward-only launches too (the
+// stream set / unit / flush checks are the caller's).  Only the variant
+// with four first-layer dW tiles (first MFMA layer reads at most 64 features, e.g. 64 Fourier features) is compiled:
+// with eight, the persistent tiles take 96 VGPRs and the kernel spills.
+inline bool jet_u16_fits(const NetDev& n, int K) {
+  if (K > 4 || n.n_layers < 1 || n.n_layers > kPersist || jet_wide_hmax(n.hmax) != 128) return false;
+  if (n.layer[0].in_dim > 64) return false;
+  for (int l = 0; l < n.n_layers; ++l)
+    if (n.layer[l].in_dim % 16 || n.layer[l].out_dim % 16 || n.layer[l].in_dim > kUH || n.layer[l].out_dim > kUH) return false;
+  return jet_u16_lds_bytes(K) <= 160 * 1024;
+}
+
+template <int ACT, int NT, int NX>
+hipError_t launch_jet_u16_act(const KernelArgs& a, bool bwd, int grid, hipStream_t stream) {
+  constexpr int K = 1 + NT + NX;
+  auto kern = bwd ? jet_kernel_u16<ACT, NT, NX, true, 4> : jet_kernel_u16<ACT, NT, NX, false, 4>;
+  hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16_lds_bytes(K), stream, a);
+  return hipGetLastError();
+}
+
+}  // namespace pinn

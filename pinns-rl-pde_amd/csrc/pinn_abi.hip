@@ -14,7 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "jet_kernel_wide.h"
+#include "jet_kernel_u16.h"
 #include "lm_engine.h"
 
 namespace pinn {
@@ -28,6 +28,19 @@ PINN_DECL(1, 4)
 PINN_DECL(2, 0)
 PINN_DECL(2, 2)
 #undef PINN_DECL
+#define PINN_DECLU1(nt, nx, a) hipError_t launch_jetu_##nt##_##nx##_a##a(const KernelArgs&, bool, int, hipStream_t);
+#ifdef PINN_DEV /* make dev: one stream set, tanh */
+#define PINN_DECLU(nt, nx) PINN_DECLU1(nt, nx, 0)
+#else
+#define PINN_DECLU(nt, nx) PINN_DECLU1(nt, nx, 0) PINN_DECLU1(nt, nx, 1) PINN_DECLU1(nt, nx, 2) PINN_DECLU1(nt, nx, 3) PINN_DECLU1(nt, nx, 4)
+#endif
+PINN_DECLU(0, 0)
+PINN_DECLU(1, 0)
+PINN_DECLU(1, 1)
+PINN_DECLU(1, 2)
+PINN_DECLU(2, 0)
+#undef PINN_DECLU
+#undef PINN_DECLU1
 
 #ifdef PINN_STAMPS
 static unsigned long long* g_stamps = nullptr;  // diagnostic builds only: device buffer for in-kernel phase timing
@@ -305,6 +318,57 @@ static bool use_wide(const PinnNetDesc* d, const float* const* w, float* const* 
   return jet_wide_fits(K, n->hmax, bwd, n->n_layers);
 }
 
+// The 16-point kernel (jet_kernel_u16.h) runs the reverse launches of the store-flush class at image height 128, K <= 4,
+// of a stream set whose unit of this activation family was built without scratch, PINN_FLAG_WIDE_TILE32 not set.  The
+// forward-only launches of such a descriptor take it too: per-point results then do not depend on whether the call
+// has a reverse sweep (bit for bit).
+static bool u16_set_compiled(int nt, int nx) {
+#ifdef PINN_DEV
+  return nt == PINN_DEV_NT && nx == PINN_DEV_NX;
+#else
+  static const int sets[][2] = {{0, 0}, {1, 0}, {1, 1}, {1, 2}, {2, 0}};
+  for (auto& s : sets)
+    if (s[0] == nt && s[1] == nx) return true;
+  return false;
+#endif
+}
+
+static bool use_u16(const PinnNetDesc* d, const NetDev& n, int nt, int nx, bool bwd) {
+  (void)bwd;
+  if ((d->flags & PINN_FLAG_WIDE_TILE32) || !u16_set_compiled(nt, nx)) return false;
+  if (wide_flush(d, n, 0, true) != FLUSH_STORE || !jet_u16_fits(n, 1 + nt + nx)) return false;
+  const int fam = jet_wide_act_family(n);
+#ifdef PINN_DEV
+  if (fam != PINN_ACT_TANH) return false;
+#endif
+  char unit[64];  // pinn_build_info() lists the u16 units that need scratch or the default MFMA form: not routed
+  snprintf(unit, sizeof(unit), "jet_u16_%d_%d_%d:", nt, nx, fam);
+  return strstr(pinn_build_info(), unit) == nullptr;
+}
+
+static hipError_t dispatch_u16(int nt, int nx, const KernelArgs& a, bool bwd, int grid, hipStream_t st) {
+  const int fam = jet_wide_act_family(a);
+#define PINN_UCASE1(NT_, NX_, A_) \
+  if (nt == NT_ && nx == NX_ && fam == A_) return launch_jetu_##NT_##_##NX_##_a##A_(a, bwd, grid, st);
+#ifdef PINN_DEV
+#define PINN_UCASE(NT_, NX_) PINN_UCASE1(NT_, NX_, 0)
+  PINN_UCASE(PINN_DEV_NT, PINN_DEV_NX)
+#else
+#define PINN_UCASE(NT_, NX_) PINN_UCASE1(NT_, NX_, 0) PINN_UCASE1(NT_, NX_, 1) PINN_UCASE1(NT_, NX_, 2) PINN_UCASE1(NT_, NX_, 3) PINN_UCASE1(NT_, NX_, 4)
+  PINN_UCASE(0, 0) PINN_UCASE(1, 0) PINN_UCASE(1, 1) PINN_UCASE(1, 2) PINN_UCASE(2, 0)
+#endif
+#undef PINN_UCASE
+#undef PINN_UCASE1
+  return hipErrorInvalidValue;
+}
+
+// floats of the global tape a launch of the fused kernel uses: the 32-point kernel's reverse sweep re-reads its
+// records from the workspace, the 16-point kernel keeps them in LDS and puts the flush slab at the workspace's start
+static size_t wide_tape_floats(const PinnNetDesc* d, const NetDev& n, int nt, int nx, bool bwd, int grid) {
+  if (!bwd || use_u16(d, n, nt, nx, bwd)) return 0;
+  return (size_t)jet_tape_floats_per_wg(1 + nt + nx, n.n_layers, 1) * grid;
+}
+
 static int wide_grid(const NetDev& n, int K, long long N, bool bwd) {
   (void)n;
   (void)K;
@@ -399,7 +463,8 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
     const bool two_level = flush == FLUSH_TWO_LEVEL;
     const bool det = flush != FLUSH_DIRECT;
     const int slab_rows = wide_slab_rows(flush, grid);
-    const size_t tape_floats = bwd ? (size_t)jet_tape_floats_per_wg(K, a.net.n_layers, 1) * grid : 0;
+    const bool u16 = use_u16(net, a.net, nt, nx, bwd);
+    const size_t tape_floats = wide_tape_floats(net, a.net, nt, nx, bwd, grid);
     size_t need = tape_floats * sizeof(float);
     DetTable dt;
     dt.n = 0;
@@ -413,7 +478,7 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
     if (need > 0 && (!workspace || ws_bytes < need))
       return fail(PINN_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
     if (need > 0 && (reinterpret_cast<uintptr_t>(workspace) & 15)) return fail(PINN_ERR_MISALIGNED, "workspace is not 16-byte aligned");
-    if (bwd) {
+    if (tape_floats > 0) {
       a.tape_stride = jet_tape_floats_per_wg(K, a.net.n_layers, 1);
       a.tape = static_cast<float*>(workspace);
     }
@@ -431,7 +496,8 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
         if (em != hipSuccess) return fail(PINN_ERR_HIP, "HIP error %d: %s", (int)em, hipGetErrorString(em));
       }
     }
-    hipError_t e = dispatch_wide(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream));
+    hipError_t e = u16 ? dispatch_u16(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream))
+                       : dispatch_wide(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(PINN_ERR_HIP, "HIP error %d: %s", (int)e, hipGetErrorString(e));
     if (det && dt.n > 0 && store_flush) {
       hipLaunchKernelGGL(wide_rows_reduce, dim3(136, dt.n), dim3(256), 0, static_cast<hipStream_t>(stream), dt, slab, slab_rows);
@@ -528,6 +594,8 @@ size_t pinn_workspace_bytes(const PinnNetDesc* net, int64_t N, int32_t time_orde
   NetDev n;
   if (backward != 2 && use_wide(net, nullptr, nullptr, K, bwd, &n)) {  // 2: pinn_jet_backward_inputs, always layer-major
     const int grid = wide_grid(n, K, N, bwd);
+    // the 32-point kernel's size even where the 16-point kernel runs (it needs only the slab): a caller can switch
+    // between the two with PINN_FLAG_WIDE_TILE32 on the same workspace
     size_t bytes = bwd ? (size_t)jet_tape_floats_per_wg(K, n.n_layers, 1) * sizeof(float) * grid : 0;
     const int rows = wide_slab_rows(wide_flush(net, n, grid, bwd), grid);
     if (rows > 0) {
@@ -573,6 +641,22 @@ int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32
     r.default_mfma_form = strstr(pinn_build_info(), unit) != nullptr;
   }
   *out = r;
+  return PINN_OK;
+}
+
+int pinn_kernel_name(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
+                     char* buf, size_t len) {
+  if (!buf || len == 0) return fail(PINN_ERR_BAD_DESC, "null or empty name buffer");
+  PinnKernelInfo r;
+  const int rc = pinn_kernel_for(net, N, time_order, space_order, backward, &r);
+  if (rc) return rc;
+  const char* name = "layer_major";
+  if (r.engine == 1) {
+    NetDev n;
+    build_wide(net, nullptr, nullptr, &n);
+    name = use_u16(net, n, time_order, space_order, backward == 1) ? "jet_kernel_u16" : "jet_kernel_wide";
+  }
+  snprintf(buf, len, "%s", name);
   return PINN_OK;
 }
 
