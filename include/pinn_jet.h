@@ -226,6 +226,23 @@ int pinn_residual_loss_grad_coef(const PinnNetDesc* net, const float* const* wei
                                  float* residual_out, float* loss_sum_out, float* const* weight_grads, float* coef_grads,
                                  void* workspace, size_t ws_bytes, void* stream);
 
+/* Inverse problems on the fused kernels: pinn_residual_loss_grad with the four PDE coefficients read at LAUNCH time from
+ * `coef_values` (device pointer to 4 floats, owned by the caller; pde->coef is ignored), so that a call captured in a HIP
+ * graph follows whatever the optimiser writes there, and coef_grads[k] += grad_scale * d(sum_n l(r_n))/d(c_k), k = 0, 1
+ * (device pointer to >= 2 floats, nullable), from the same launch.  Descriptors of the plain-MLP family take the fused
+ * tile-major kernels (their COEF units: jet_kernel_u16 / jet_kernel_wide, chosen as pinn_residual_loss_grad chooses
+ * them); a stream set without such a unit (KdV's (1,3), the (1,0) of >= 2-D descriptors) and every other descriptor take
+ * the layer-major engine.  Null coef_values: PINN_ERR_BAD_DESC.  Size the workspace with pinn_inverse_workspace_bytes;
+ * for descriptors that take a tile-major unit it equals pinn_workspace_bytes(net, N, nt, nx, 1). */
+int pinn_residual_loss_grad_inverse(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors,
+                                    const PinnPdeDesc* pde, const float* coef_values, const float* x, const float* t,
+                                    int64_t N, float grad_scale, float* residual_out, float* loss_sum_out,
+                                    float* const* weight_grads, float* coef_grads, void* workspace, size_t ws_bytes,
+                                    void* stream);
+size_t pinn_inverse_workspace_bytes(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N);
+/* "jet_kernel_u16" | "jet_kernel_wide" | "layer_major": the kernel such a call takes (as pinn_kernel_name). */
+int pinn_inverse_kernel_name(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N, char* buf, size_t len);
+
 /* weight_grads += d(sum_n residual_cotangent[n] * r_n)/d(weights): the backward of pinn_residual_forward for an
  * arbitrary downstream graph (loss.backward() through `residual`, trainer.py:689; LRW's per-component
  * backward passes, trainer.py:607-626). */

@@ -31,7 +31,8 @@ EXPORTS = (
     "pinn_abi_version", "pinn_last_error", "pinn_build_info", "pinn_num_tensors", "pinn_pde_streams",
     "pinn_workspace_bytes", "pinn_jet_forward", "pinn_jet_backward", "pinn_residual_forward", "pinn_residual_backward",
     "pinn_residual_loss_grad", "pinn_residual_loss_grad_coef", "pinn_point_losses", "pinn_jet_losses", "pinn_adam_clip_step",
-    "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name",
+    "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name", "pinn_residual_loss_grad_inverse",
+    "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name",
 )
 
 
@@ -135,6 +136,13 @@ def load():
         lib.pinn_residual_loss_grad_coef.restype = ctypes.c_int
         lib.pinn_residual_loss_grad_coef.argtypes = [P(PinnNetDesc), P(vp), i32, P(PinnPdeDesc), vp, vp, i64, f32, vp, vp,
                                                      P(vp), vp, vp, sz, vp]
+        lib.pinn_residual_loss_grad_inverse.restype = ctypes.c_int
+        lib.pinn_residual_loss_grad_inverse.argtypes = [P(PinnNetDesc), P(vp), i32, P(PinnPdeDesc), vp, vp, vp, i64, f32, vp, vp,
+                                                        P(vp), vp, vp, sz, vp]
+        lib.pinn_inverse_workspace_bytes.restype = ctypes.c_size_t
+        lib.pinn_inverse_workspace_bytes.argtypes = [P(PinnNetDesc), P(PinnPdeDesc), i64]
+        lib.pinn_inverse_kernel_name.restype = ctypes.c_int
+        lib.pinn_inverse_kernel_name.argtypes = [P(PinnNetDesc), P(PinnPdeDesc), i64, ctypes.c_char_p, sz]
         lib.pinn_point_losses.restype = ctypes.c_int
         lib.pinn_point_losses.argtypes = [vp, i32, i32, P(i32), P(i32), P(vp), P(f32), i32, f32, vp, vp, vp, f32, f32, i32, vp, vp]
         lib.pinn_jet_losses.restype = ctypes.c_int

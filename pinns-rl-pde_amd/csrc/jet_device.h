@@ -257,7 +257,21 @@ struct PdeDev {
   float c0, c1, c2, c3;
   float huber_delta;
   float* dcoef;  // reverse sweeps, nullable: dcoef[k] += sum_n rbar_n dr_n/dc_k (inverse problems: trainable coefficients)
+  const float* coef_dev;  // nullable: four floats on the device that replace c0..c3 at launch time (pinn_residual_loss_grad_inverse);
+                          // read by the COEF kernel variants and the layer-major head only
 };
+
+// the coefficients a launch computes with: the device array when one is given (uniform loads), the by-value ones otherwise
+__device__ __forceinline__ PdeDev pde_live_coefs(const PdeDev& p) {
+  PdeDev q = p;
+  if (p.coef_dev) {
+    q.c0 = p.coef_dev[0];
+    q.c1 = p.coef_dev[1];
+    q.c2 = p.coef_dev[2];
+    q.c3 = p.coef_dev[3];
+  }
+  return q;
+}
 
 template <int NT, int NX>
 __device__ __forceinline__ float pde_residual(const PdeDev& p, const float* j, float x0, float* d) {

@@ -266,7 +266,13 @@ __device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
 // NA0: 16-feature k-tiles of the first MFMA layer's weight-gradient accumulators (4: at most 64 input features)
 // BWD = false: the forward-only launch of the same networks.  It runs the forward code of the reverse launch unchanged,
 // so a forward-only call and a fused call give bit-identical per-point results.
-template <int ACT, int NT, int NX, bool BWD, int NA0>
+// COEF = true (reverse launches only, jet_u16c_* units): inverse problems.  The PDE coefficients come from the device
+// array a.pde.coef_dev, read once at kernel start, and the writer lanes also sum rbar dr/dc_0, rbar dr/dc_1; the two
+// sums go to a.pde.dcoef in this workgroup's slab row (the padding of the loss-sum slot).  The reverse kernel has no
+// VGPR to spare (254 without COEF), so neither the coefficients nor the two running sums live in registers across the
+// unit loop: both sit in the 4-float row pad of the stream-0 rows of image X, which no GEMM, put or encode touches —
+// X[n][128], X[n][129]: the sums of writer lane n; X[k][130], k < 4: coefficient c_k.
+template <int ACT, int NT, int NX, bool BWD, int NA0, bool COEF = false>
 __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs a) {
   constexpr int K = 1 + NT + NX;
   constexpr int NKT = kUH / 16;
@@ -304,6 +310,14 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   for (int i = 0; i < kPersist + kMaxDin + 1; ++i)
     if (tid < kUH) pl[i * kUH + tid] = 0.0f;
   const float b_out0 = net.b_out[0];
+  static_assert(!COEF || BWD, "coefficient cotangents belong to the reverse launch");
+  if constexpr (COEF) {
+    if (tid < kU) {
+      X[tid * kUP + kUH] = 0.0f;
+      X[tid * kUP + kUH + 1] = 0.0f;
+    }
+    if (tid < 4) X[tid * kUP + kUH + 2] = a.pde.coef_dev[tid];  // visible after the unit loop's first barrier
+  }
 
   f32x4 pt[NPT];
 #pragma unroll
@@ -417,9 +431,18 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         }
       } else {
         float d[K];
-        const float r = pde_residual<NT, NX>(a.pde, j, xin[c], d);
+        PdeDev pde_c;
+        if constexpr (COEF) {
+          pde_c = a.pde;
+          pde_c.c0 = X[0 * kUP + kUH + 2];
+          pde_c.c1 = X[1 * kUP + kUH + 2];
+          pde_c.c2 = X[2 * kUP + kUH + 2];
+          pde_c.c3 = X[3 * kUP + kUH + 2];
+        }
+        const PdeDev& pde = COEF ? pde_c : a.pde;
+        const float r = pde_residual<NT, NX>(pde, j, xin[c], d);
         float dl;
-        float lt = loss_term(a.pde, r, &dl);
+        float lt = loss_term(pde, r, &dl);
         if (!ok) {
           lt = 0.0f;
           dl = 0.0f;
@@ -429,6 +452,14 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         const float rb = !BWD ? 0.0f : a.res_bar ? (ok ? a.res_bar[p] : 0.0f) : a.grad_scale * dl;
 #pragma unroll
         for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
+        if constexpr (COEF) {
+          float dc0, dc1;
+          pde_coef_grads<NT, NX>(pde, j, xin[c], dc0, dc1);
+          if (writer) {  // lane-private LDS slots (tid < kU: c == tid)
+            X[c * kUP + kUH] += rb * dc0;
+            X[c * kUP + kUH + 1] += rb * dc1;
+          }
+        }
       }
     }
 
@@ -571,6 +602,20 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     if (tid == 0) grad_put(a.loss_sum, sacc, doff, a.flush_store != 0);
   }
   if constexpr (!BWD) return;
+  if constexpr (COEF) {
+    if (a.mode == MODE_PDE && a.pde.dcoef && wv == 0) {
+      float s0 = tid < kU ? X[tid * kUP + kUH] : 0.0f, s1 = tid < kU ? X[tid * kUP + kUH + 1] : 0.0f;
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o);
+        s1 += __shfl_xor(s1, o);
+      }
+      if (tid == 0) {
+        a.pde.dcoef[doff] = s0;
+        a.pde.dcoef[doff + 1] = s1;
+      }
+    }
+  }
   if (net.db_out && wv == 0) {
     float gsum = tid < kU ? pdb_out : 0.0f;
 #pragma unroll
@@ -629,6 +674,17 @@ template <int ACT, int NT, int NX>
 hipError_t launch_jet_u16_act(const KernelArgs& a, bool bwd, int grid, hipStream_t stream) {
   constexpr int K = 1 + NT + NX;
   auto kern = bwd ? jet_kernel_u16<ACT, NT, NX, true, 4> : jet_kernel_u16<ACT, NT, NX, false, 4>;
+  hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16_lds_bytes(K), stream, a);
+  return hipGetLastError();
+}
+
+// the COEF variant (reverse launch only): jet_u16c_* units
+template <int ACT, int NT, int NX>
+hipError_t launch_jet_u16_coef(const KernelArgs& a, int grid, hipStream_t stream) {
+  constexpr int K = 1 + NT + NX;
+  auto kern = jet_kernel_u16<ACT, NT, NX, true, 4, true>;
   hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16_lds_bytes(K), stream, a);

@@ -424,7 +424,13 @@ __device__ __forceinline__ void flush_rows(const f32x16 (&pt)[NPT], const LayerD
 // became a loop-invariant address VGPR, and the register allocator spilled them (2.3 KB of scratch per lane).
 // NA0: k-tiles (32 input features) of the FIRST MFMA layer's weight-gradient accumulators — 2 for the headline
 // network (64 Fourier features -> 128), HMAX / 32 in general.
-template <int ACT, int NT, int NX, bool BWD, int HMAX, int NA0>
+// COEF = true (reverse launches only, jet_widec_* units): inverse problems.  The PDE coefficients come from the device
+// array a.pde.coef_dev, read once at kernel start, and the writer lanes also sum rbar dr/dc_0, rbar dr/dc_1; the two
+// sums are flushed to a.pde.dcoef like the loss sum.  Neither the coefficients nor the two running sums are held in
+// registers across the tile loop (the reverse kernel has none to spare): both sit in the 4-float row pad (columns
+// 32 .. 35) of the first rows of image X, which no GEMM or put_tile touches — X[n][32], X[n][33]: the sums of writer
+// lane n; X[k][34], k < 4: coefficient c_k.
+template <int ACT, int NT, int NX, bool BWD, int HMAX, int NA0, bool COEF = false>
 __global__ __launch_bounds__(kThreads, 1) void jet_kernel_wide(const KernelArgs a) {
   constexpr int K = 1 + NT + NX;
   constexpr int NKT = HMAX / 32;                       // k-tiles of a full-width layer
@@ -465,6 +471,14 @@ __global__ __launch_bounds__(kThreads, 1) void jet_kernel_wide(const KernelArgs 
   dwo[tid] = 0.0f;
   stage_enc_params<HMAX>(net, ep, tid);
   const float b_out0 = net.b_out[0];
+  static_assert(!COEF || BWD, "coefficient cotangents belong to the reverse launch");
+  if constexpr (COEF) {
+    if (tid < kT) {
+      X[tid * kTP + kT] = 0.0f;
+      X[tid * kTP + kT + 1] = 0.0f;
+    }
+    if (tid < 4) X[tid * kTP + kT + 2] = a.pde.coef_dev[tid];  // visible after the tile loop's first barrier
+  }
   float* dwo_row = dwo + (tid >> 4) * 16;  // this lane's 16-lane row: [r]
   const bool row_lead = (tid & 15) == 0;
   const int row4 = ft * 32 + 4 * L.lh;  // rows 8q + 4h + i of this lane's tile: wb[.. + row4 + 8q + i]
@@ -617,9 +631,18 @@ __global__ __launch_bounds__(kThreads, 1) void jet_kernel_wide(const KernelArgs 
         }
       } else {
         float d[K];
-        const float r = pde_residual<NT, NX>(a.pde, j, xin[L.ln], d);
+        PdeDev pde_c;
+        if constexpr (COEF) {
+          pde_c = a.pde;
+          pde_c.c0 = X[0 * kTP + kT + 2];
+          pde_c.c1 = X[1 * kTP + kT + 2];
+          pde_c.c2 = X[2 * kTP + kT + 2];
+          pde_c.c3 = X[3 * kTP + kT + 2];
+        }
+        const PdeDev& pde = COEF ? pde_c : a.pde;
+        const float r = pde_residual<NT, NX>(pde, j, xin[L.ln], d);
         float dl;
-        float lt = loss_term(a.pde, r, &dl);
+        float lt = loss_term(pde, r, &dl);
         if (!ok) {
           lt = 0.0f;
           dl = 0.0f;
@@ -629,6 +652,14 @@ __global__ __launch_bounds__(kThreads, 1) void jet_kernel_wide(const KernelArgs 
         const float rb = !BWD ? 0.0f : (a.res_bar ? (ok ? a.res_bar[p] : 0.0f) : a.grad_scale * dl);
 #pragma unroll
         for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
+        if constexpr (COEF) {
+          float dc0, dc1;
+          pde_coef_grads<NT, NX>(pde, j, xin[L.ln], dc0, dc1);
+          if (writer) {  // lane-private LDS slots (tid < kT: ln == tid)
+            X[L.ln * kTP + kT] += rb * dc0;
+            X[L.ln * kTP + kT + 1] += rb * dc1;
+          }
+        }
       }
     }
     PINN_STAMP(ST_EPI);
@@ -809,6 +840,20 @@ __global__ __launch_bounds__(kThreads, 1) void jet_kernel_wide(const KernelArgs 
     for (int o = 16; o > 0; o >>= 1) sacc += __shfl_xor(sacc, o);
     if (tid == 0) grad_put(a.loss_sum, sacc, doff, st);
   }
+  if constexpr (COEF) {
+    if (a.mode == MODE_PDE && a.pde.dcoef && L.wave == 0) {
+      float s0 = L.lh == 0 ? X[L.ln * kTP + kT] : 0.0f, s1 = L.lh == 0 ? X[L.ln * kTP + kT + 1] : 0.0f;
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o);
+        s1 += __shfl_xor(s1, o);
+      }
+      if (tid == 0) {
+        grad_put(a.pde.dcoef, s0, doff, st);
+        grad_put(a.pde.dcoef + 1, s1, doff, st);
+      }
+    }
+  }
   if constexpr (BWD) {
     if (net.db_out && L.wave == 0) {
       float g = L.lh == 0 ? pdb_out : 0.0f;
@@ -897,6 +942,22 @@ hipError_t launch_jet_wide_act(const KernelArgs& a, bool bwd, int grid, hipStrea
   } while (0)
   if (bwd) PINN_WLAUNCH1(true); else PINN_WLAUNCH1(false);
 #undef PINN_WLAUNCH1
+  return hipGetLastError();
+}
+
+// the COEF variant of one activation's reverse kernels: jet_widec_* units
+template <int ACT, int NT, int NX>
+hipError_t launch_jet_wide_coef(const KernelArgs& a, int grid, hipStream_t stream) {
+  constexpr int K = 1 + NT + NX;
+  int hm, na0;
+  jet_wide_variant(a.net, true, &hm, &na0);
+  const size_t lds = jet_wide_lds_bytes(K, hm, true, a.net.n_layers);
+  auto kern = hm == 64 ? jet_kernel_wide<ACT, NT, NX, true, 64, 2, true>
+              : na0 == 2 ? jet_kernel_wide<ACT, NT, NX, true, 128, 2, true>
+                         : jet_kernel_wide<ACT, NT, NX, true, 128, 4, true>;
+  const hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, a);
   return hipGetLastError();
 }
 

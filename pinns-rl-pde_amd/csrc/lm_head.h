@@ -50,6 +50,7 @@ __global__ __launch_bounds__(1024) void lm_head(const HeadArgs a) {
 #pragma unroll
   for (int i = 0; i < FPT; ++i) w[i] = vec_ld(a.w_out, a.G * i, goff);  // zero on padding features
   const float b0 = a.b_out[0];
+  const PdeDev pde = pde_live_coefs(a.pde);  // inverse problems: coefficients from the device array when one is given
   float ploss = 0.0f, pdb = 0.0f, pdc0 = 0.0f, pdc1 = 0.0f;
   for (long long uu = 2LL * blockIdx.x; uu < 2 * a.ntiles; uu += (uu & 1) ? 2LL * gridDim.x - 1 : 1) {
     // both 16-point halves of a tile back to back in the SAME workgroup: a 128-byte record row is then fetched from HBM
@@ -87,9 +88,9 @@ __global__ __launch_bounds__(1024) void lm_head(const HeadArgs a) {
     } else {
       const float x0 = (ok && a.din > 1) ? a.x[p * (a.din - 1)] : 0.0f;
       float d[K];
-      const float r = pde_residual<NT, NX>(a.pde, j, x0, d);
+      const float r = pde_residual<NT, NX>(pde, j, x0, d);
       float dl;
-      float lt = loss_term(a.pde, r, &dl);
+      float lt = loss_term(pde, r, &dl);
       if (!ok) {
         lt = 0.0f;
         dl = 0.0f;
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(1024) void lm_head(const HeadArgs a) {
       for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
       if (a.bwd && a.pde.dcoef && g == 0) {  // inverse problems: rbar dr/dc_k
         float dc0, dc1;
-        pde_coef_grads<NT, NX>(a.pde, j, x0, dc0, dc1);
+        pde_coef_grads<NT, NX>(pde, j, x0, dc0, dc1);
         pdc0 += rb * dc0;
         pdc1 += rb * dc1;
       }

@@ -41,6 +41,20 @@ PINN_DECLU(1, 2)
 PINN_DECLU(2, 0)
 #undef PINN_DECLU
 #undef PINN_DECLU1
+#ifndef PINN_DEV /* inverse problems: COEF units (jet_widec_*, jet_u16c_*), reverse launches only */
+#define PINN_DECLC1(p, nt, nx, a) hipError_t launch_jet##p##_##nt##_##nx##_a##a(const KernelArgs&, int, hipStream_t);
+#define PINN_DECLC(p, nt, nx) PINN_DECLC1(p, nt, nx, 0) PINN_DECLC1(p, nt, nx, 1) PINN_DECLC1(p, nt, nx, 2) PINN_DECLC1(p, nt, nx, 3) PINN_DECLC1(p, nt, nx, 4)
+PINN_DECLC(wc, 1, 1)
+PINN_DECLC(wc, 1, 2)
+PINN_DECLC(wc, 1, 4)
+PINN_DECLC(wc, 2, 0)
+PINN_DECLC(wc, 2, 2)
+PINN_DECLC(uc, 1, 1)
+PINN_DECLC(uc, 1, 2)
+PINN_DECLC(uc, 2, 0)
+#undef PINN_DECLC
+#undef PINN_DECLC1
+#endif
 
 #ifdef PINN_STAMPS
 static unsigned long long* g_stamps = nullptr;  // diagnostic builds only: device buffer for in-kernel phase timing
@@ -183,6 +197,8 @@ struct DetTable {
   int n;
   float* user[2 * PINN_MAX_LINEAR + 8];
   unsigned off[2 * PINN_MAX_LINEAR + 8], cnt[2 * PINN_MAX_LINEAR + 8];
+  unsigned lead[2 * PINN_MAX_LINEAR + 8];  // floats at the start of the slot that belong to another target (the coefficient
+                                           // sums sit in the padding of the loss-sum slot); off stays 16-byte aligned
   unsigned stride;
 };
 
@@ -190,7 +206,7 @@ __global__ void wide_det_reduce(const DetTable tab, const float* slab, int rows)
   const unsigned it = blockIdx.y;
   for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < tab.cnt[it]; e += gridDim.x * blockDim.x) {
     float s = 0.0f;
-    for (int b = 0; b < rows; ++b) s += slab[(size_t)b * tab.stride + tab.off[it] + e];
+    for (int b = 0; b < rows; ++b) s += slab[(size_t)b * tab.stride + tab.off[it] + tab.lead[it] + e];
     tab.user[it][e] += s;
   }
 }
@@ -201,7 +217,8 @@ __global__ void wide_det_reduce(const DetTable tab, const float* slab, int rows)
 __global__ __launch_bounds__(256) void wide_rows_reduce(const DetTable tab, const float* slab, int rows) {
   __shared__ float part[8][128];
   const unsigned it = blockIdx.y;
-  const unsigned cnt4 = (tab.cnt[it] + 3u) & ~3u;  // rows are padded to 4 floats per target (det_slot)
+  const unsigned lead = tab.lead[it], end = lead + tab.cnt[it];
+  const unsigned cnt4 = (end + 3u) & ~3u;  // rows are padded to 4 floats per target (det_slot)
   const int el = threadIdx.x & 31, rg = threadIdx.x >> 5;
   for (unsigned e0 = blockIdx.x * 128u; e0 < cnt4; e0 += gridDim.x * 128u) {
     const unsigned e = e0 + 4u * el;
@@ -219,11 +236,11 @@ __global__ __launch_bounds__(256) void wide_rows_reduce(const DetTable tab, cons
     part[rg][4 * el + 2] = s2;
     part[rg][4 * el + 3] = s3;
     __syncthreads();
-    if (threadIdx.x < 128 && e0 + threadIdx.x < tab.cnt[it]) {
+    if (threadIdx.x < 128 && e0 + threadIdx.x >= lead && e0 + threadIdx.x < end) {
       float t = 0.0f;
 #pragma unroll
       for (int g = 0; g < 8; ++g) t += part[g][threadIdx.x];
-      tab.user[it][e0 + threadIdx.x] += t;
+      tab.user[it][e0 + threadIdx.x - lead] += t;
     }
     __syncthreads();
   }
@@ -279,8 +296,16 @@ static void det_redirect(NetDev& n, float*& loss_sum, float*& dcoef, float* slab
   }
   slot(n.dw_out, (unsigned)n.h_last, sizing);
   slot(n.db_out, 1u, sizing);
+  const unsigned loss_off = t.stride;  // the loss-sum slot is 1 float padded to 4: floats 1, 2 hold the coefficient sums
   slot(loss_sum, 1u, sizing);
-  (void)dcoef;
+  if (slab && dcoef) {
+    const int i = t.n++;
+    t.user[i] = dcoef;
+    t.off[i] = loss_off;
+    t.lead[i] = 1;
+    t.cnt[i] = 2;
+    dcoef = slab + loss_off + 1;
+  }
   if (t.stride == 0) t.stride = 4;
 }
 
@@ -333,17 +358,55 @@ static bool u16_set_compiled(int nt, int nx) {
 #endif
 }
 
-static bool use_u16(const PinnNetDesc* d, const NetDev& n, int nt, int nx, bool bwd) {
+// stream sets of the COEF units (inverse problems): the PDEs that have a coefficient
+static bool widec_set_compiled(int nt, int nx) {
+#ifdef PINN_DEV
+  return false;
+#else
+  static const int sets[][2] = {{1, 1}, {1, 2}, {1, 4}, {2, 0}, {2, 2}};
+  for (auto& s : sets)
+    if (s[0] == nt && s[1] == nx) return true;
+  return false;
+#endif
+}
+static bool u16c_set_compiled(int nt, int nx) {
+#ifdef PINN_DEV
+  return false;
+#else
+  return (nt == 1 && (nx == 1 || nx == 2)) || (nt == 2 && nx == 0);
+#endif
+}
+
+// coef: the jet_u16c_* unit of a pinn_residual_loss_grad_inverse call instead of the jet_u16_* one
+static bool use_u16(const PinnNetDesc* d, const NetDev& n, int nt, int nx, bool bwd, bool coef = false) {
   (void)bwd;
-  if ((d->flags & PINN_FLAG_WIDE_TILE32) || !u16_set_compiled(nt, nx)) return false;
+  if ((d->flags & PINN_FLAG_WIDE_TILE32) || !(coef ? u16c_set_compiled(nt, nx) : u16_set_compiled(nt, nx))) return false;
   if (wide_flush(d, n, 0, true) != FLUSH_STORE || !jet_u16_fits(n, 1 + nt + nx)) return false;
   const int fam = jet_wide_act_family(n);
 #ifdef PINN_DEV
   if (fam != PINN_ACT_TANH) return false;
 #endif
   char unit[64];  // pinn_build_info() lists the u16 units that need scratch or the default MFMA form: not routed
-  snprintf(unit, sizeof(unit), "jet_u16_%d_%d_%d:", nt, nx, fam);
+  snprintf(unit, sizeof(unit), coef ? "jet_u16c_%d_%d_%d:" : "jet_u16_%d_%d_%d:", nt, nx, fam);
   return strstr(pinn_build_info(), unit) == nullptr;
+}
+
+// reverse launch of a COEF unit: the 16-point kernel (u16) or the 32-point one
+static hipError_t dispatch_coef(bool u16, int nt, int nx, const KernelArgs& a, int grid, hipStream_t st) {
+#ifndef PINN_DEV
+  const int fam = jet_wide_act_family(a);
+#define PINN_CCASE1(P_, NT_, NX_, A_) \
+  if (nt == NT_ && nx == NX_ && fam == A_) return launch_jet##P_##_##NT_##_##NX_##_a##A_(a, grid, st);
+#define PINN_CCASE(P_, NT_, NX_) PINN_CCASE1(P_, NT_, NX_, 0) PINN_CCASE1(P_, NT_, NX_, 1) PINN_CCASE1(P_, NT_, NX_, 2) PINN_CCASE1(P_, NT_, NX_, 3) PINN_CCASE1(P_, NT_, NX_, 4)
+  if (u16) {
+    PINN_CCASE(uc, 1, 1) PINN_CCASE(uc, 1, 2) PINN_CCASE(uc, 2, 0)
+  } else {
+    PINN_CCASE(wc, 1, 1) PINN_CCASE(wc, 1, 2) PINN_CCASE(wc, 1, 4) PINN_CCASE(wc, 2, 0) PINN_CCASE(wc, 2, 2)
+  }
+#undef PINN_CCASE
+#undef PINN_CCASE1
+#endif
+  return hipErrorInvalidValue;
 }
 
 static hipError_t dispatch_u16(int nt, int nx, const KernelArgs& a, bool bwd, int grid, hipStream_t st) {
@@ -364,8 +427,8 @@ static hipError_t dispatch_u16(int nt, int nx, const KernelArgs& a, bool bwd, in
 
 // floats of the global tape a launch of the fused kernel uses: the 32-point kernel's reverse sweep re-reads its
 // records from the workspace, the 16-point kernel keeps them in LDS and puts the flush slab at the workspace's start
-static size_t wide_tape_floats(const PinnNetDesc* d, const NetDev& n, int nt, int nx, bool bwd, int grid) {
-  if (!bwd || use_u16(d, n, nt, nx, bwd)) return 0;
+static size_t wide_tape_floats(const PinnNetDesc* d, const NetDev& n, int nt, int nx, bool bwd, int grid, bool coef = false) {
+  if (!bwd || use_u16(d, n, nt, nx, bwd, coef)) return 0;
   return (size_t)jet_tape_floats_per_wg(1 + nt + nx, n.n_layers, 1) * grid;
 }
 
@@ -393,7 +456,8 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
                const PinnPdeDesc* pde, const float* x, const float* t, int64_t N, int nt, int nx, int mode,
                float grad_scale, float* const* jets_out, const float* const* jets_bar, float* residual_out,
                float* loss_sum, void* workspace, size_t ws_bytes, bool bwd, void* stream, const float* res_bar = nullptr,
-               float* coef_grads = nullptr, float* x_grad = nullptr, float* t_grad = nullptr, bool lm_only = false) {
+               float* coef_grads = nullptr, float* x_grad = nullptr, float* t_grad = nullptr, bool lm_only = false,
+               const float* coef_dev = nullptr) {
   int rc = validate_table(net, weights, num_tensors, "weights");
   if (rc) return rc;
   if (bwd && grads && (rc = validate_table(net, grads, num_tensors, "weight_grads"))) return rc;  // null only where the entry point allows it
@@ -417,7 +481,9 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
     pd.c3 = pde->coef[3];
     pd.huber_delta = pde->huber_delta;
     pd.dcoef = bwd ? coef_grads : nullptr;
+    pd.coef_dev = coef_dev;
   }
+  const bool inverse = coef_dev != nullptr;  // pinn_residual_loss_grad_inverse: COEF units, coefficients from the device
   KernelArgs a;
   memset(&a, 0, sizeof(a));
   int misaligned = -1;
@@ -425,13 +491,14 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
   // tile-major kernel the extra per-tile code cost the headline configuration scratch (SGPR spills to memory) even with the
   // feature off, so such calls take the layer-major engine — which the caller selects (PINN_FLAG_LAYER_MAJOR) so that
   // pinn_workspace_bytes sizes the workspace for it.
-  if (coef_grads && !(net->flags & PINN_FLAG_LAYER_MAJOR) && !force_lm() && use_wide(net, nullptr, nullptr, K, bwd, &a.net))
+  if (!inverse && coef_grads && !(net->flags & PINN_FLAG_LAYER_MAJOR) && !force_lm() && use_wide(net, nullptr, nullptr, K, bwd, &a.net))
     return fail(PINN_ERR_UNSUPPORTED, "coefficient gradients run on the layer-major engine: set PINN_FLAG_LAYER_MAJOR in the "
                 "descriptor for this call and for its pinn_workspace_bytes query");
-  const bool wide = !lm_only && use_wide(net, weights, grads, K, bwd, &a.net, &misaligned);
+  bool wide = !lm_only && use_wide(net, weights, grads, K, bwd, &a.net, &misaligned);
   if (!wide && misaligned >= 0)  // pinn_workspace_bytes sized this descriptor for the fused kernel: say what is wrong instead of "workspace too small"
     return fail(PINN_ERR_MISALIGNED, "weight tensor %d is not 16-byte aligned: the fused kernel of this descriptor reads hidden-layer "
                 "weights with 16-byte loads (pass aligned tensors, or set PINN_FLAG_LAYER_MAJOR to take the packing engine)", misaligned);
+  if (inverse && !widec_set_compiled(nt, nx)) wide = false;  // no COEF unit of this stream set: layer-major engine
   if (wide) {
     const int grid = wide_grid(a.net, K, N, bwd);
     a.pde = pd;
@@ -463,8 +530,8 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
     const bool two_level = flush == FLUSH_TWO_LEVEL;
     const bool det = flush != FLUSH_DIRECT;
     const int slab_rows = wide_slab_rows(flush, grid);
-    const bool u16 = use_u16(net, a.net, nt, nx, bwd);
-    const size_t tape_floats = wide_tape_floats(net, a.net, nt, nx, bwd, grid);
+    const bool u16 = use_u16(net, a.net, nt, nx, bwd, inverse);
+    const size_t tape_floats = wide_tape_floats(net, a.net, nt, nx, bwd, grid, inverse);
     size_t need = tape_floats * sizeof(float);
     DetTable dt;
     dt.n = 0;
@@ -496,8 +563,9 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
         if (em != hipSuccess) return fail(PINN_ERR_HIP, "HIP error %d: %s", (int)em, hipGetErrorString(em));
       }
     }
-    hipError_t e = u16 ? dispatch_u16(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream))
-                       : dispatch_wide(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream));
+    hipError_t e = inverse ? dispatch_coef(u16, nt, nx, a, grid, static_cast<hipStream_t>(stream))
+                   : u16   ? dispatch_u16(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream))
+                           : dispatch_wide(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(PINN_ERR_HIP, "HIP error %d: %s", (int)e, hipGetErrorString(e));
     if (det && dt.n > 0 && store_flush) {
       hipLaunchKernelGGL(wide_rows_reduce, dim3(136, dt.n), dim3(256), 0, static_cast<hipStream_t>(stream), dt, slab, slab_rows);
@@ -735,6 +803,73 @@ int pinn_residual_loss_grad_coef(const PinnNetDesc* net, const float* const* wei
   if (rc) return rc;
   return run(net, weights, weight_grads, num_tensors, pde, x, t, N, nt, nx, MODE_PDE, grad_scale, nullptr, nullptr,
              residual_out, loss_sum_out, workspace, ws_bytes, true, stream, nullptr, coef_grads);
+}
+
+// 0 layer-major, 1 jet_kernel_wide, 2 jet_kernel_u16: the engine a pinn_residual_loss_grad_inverse call takes (run()'s
+// decisions with the COEF units in place of the plain ones); n receives the wide program when the answer is not 0
+static int inverse_route(const PinnNetDesc* net, int nt, int nx, NetDev* n) {
+  if (!widec_set_compiled(nt, nx) || !use_wide(net, nullptr, nullptr, 1 + nt + nx, true, n)) return 0;
+  return use_u16(net, *n, nt, nx, true, true) ? 2 : 1;
+}
+
+static int inverse_query(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N, int32_t* nt, int32_t* nx) {
+  if (!net || !pde) return fail(PINN_ERR_BAD_DESC, "null descriptor");
+  if (N <= 0) return fail(PINN_ERR_BAD_DESC, "N = %lld: a call on no points launches nothing", (long long)N);
+  int rc = pinn_pde_streams(pde, nt, nx);
+  if (rc) return rc;
+  if (!stream_set_compiled(*nt, *nx)) return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", *nt, *nx);
+  char lerr[256] = "";
+  if ((rc = lm::lm_check(net, lerr, sizeof(lerr)))) return fail(rc, "%s", lerr);
+  return PINN_OK;
+}
+
+int pinn_residual_loss_grad_inverse(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors,
+                                    const PinnPdeDesc* pde, const float* coef_values, const float* x, const float* t,
+                                    int64_t N, float grad_scale, float* residual_out, float* loss_sum_out,
+                                    float* const* weight_grads, float* coef_grads, void* workspace, size_t ws_bytes,
+                                    void* stream) {
+  if (!weight_grads) return fail(PINN_ERR_BAD_DESC, "weight_grads is null");
+  if (!coef_values) return fail(PINN_ERR_BAD_DESC, "coef_values is null: the coefficients of this call live on the device");
+  int32_t nt, nx;
+  int rc = pinn_pde_streams(pde, &nt, &nx);
+  if (rc) return rc;
+  PinnPdeDesc p = *pde;  // pde->coef is ignored: every value comes from coef_values at launch time
+  p.coef[0] = p.coef[1] = p.coef[2] = p.coef[3] = 0.0f;
+  return run(net, weights, weight_grads, num_tensors, &p, x, t, N, nt, nx, MODE_PDE, grad_scale, nullptr, nullptr,
+             residual_out, loss_sum_out, workspace, ws_bytes, true, stream, nullptr, coef_grads, nullptr, nullptr, false,
+             coef_values);
+}
+
+size_t pinn_inverse_workspace_bytes(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N) {
+  int32_t nt, nx;
+  if (inverse_query(net, pde, N, &nt, &nx) != PINN_OK) return 0;
+  NetDev n;
+  if (inverse_route(net, nt, nx, &n) == 0)
+    return lm::lm_workspace_bytes(net, N, nt, nx, true, (net->flags & PINN_FLAG_DETERMINISTIC) != 0);
+  // as pinn_workspace_bytes(net, N, nt, nx, 1): the 32-point kernel's size even where the 16-point kernel runs
+  const int K = 1 + nt + nx;
+  const int grid = wide_grid(n, K, N, true);
+  size_t bytes = (size_t)jet_tape_floats_per_wg(K, n.n_layers, 1) * sizeof(float) * grid;
+  const int rows = wide_slab_rows(wide_flush(net, n, grid, true), grid);
+  if (rows > 0) {
+    DetTable dt;
+    float* lprobe = nullptr;
+    float* cprobe = nullptr;
+    det_redirect(n, lprobe, cprobe, nullptr, dt);
+    bytes += (size_t)dt.stride * rows * sizeof(float);
+  }
+  return bytes;
+}
+
+int pinn_inverse_kernel_name(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N, char* buf, size_t len) {
+  if (!buf || len == 0) return fail(PINN_ERR_BAD_DESC, "null or empty name buffer");
+  int32_t nt, nx;
+  const int rc = inverse_query(net, pde, N, &nt, &nx);
+  if (rc) return rc;
+  NetDev n;
+  const int route = inverse_route(net, nt, nx, &n);
+  snprintf(buf, len, "%s", route == 2 ? "jet_kernel_u16" : route == 1 ? "jet_kernel_wide" : "layer_major");
+  return PINN_OK;
 }
 
 int pinn_residual_backward(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors,

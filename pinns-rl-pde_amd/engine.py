@@ -298,8 +298,9 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
                        want_residual: bool = False, loss_sum: Optional[Tensor] = None,
                        coef_grads: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor]:
     """One launch: flat_grad += grad_scale * d(sum_n l(r_n))/d(theta); returns (residual | None, loss_sum).
-    `coef_grads` (>= 2 floats on the device, accumulated): the same derivative w.r.t. the PDE coefficients pd.coef[0..1]
-    (inverse problems), from the same launch."""
+    `coef_grads` (>= 2 floats on the device, accumulated): the same derivative w.r.t. the by-value coefficients
+    pd.coef[0..1] through `pinn_residual_loss_grad_coef`, which runs on the layer-major engine only: the descriptor must
+    carry PINN_FLAG_LAYER_MAJOR (`set_layer_major`).  Inverse problems use `residual_loss_grad_inverse`."""
     lib = _lib.load()
     dev = _require_device(x, t, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
@@ -307,30 +308,54 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
     s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
     if N:
         nt, nx = pde_streams(pd)
-        flags0 = prog.desc.flags
-        if coef_grads is not None:  # the coefficient reduction lives in the layer-major engine (sizing and call alike)
-            prog.desc.flags = flags0 | _lib.PINN_FLAG_LAYER_MAJOR
-        try:
-            ws, wptr, wn = _scratch(prog, dev, N, nt, nx, True)
-        except Exception:
-            prog.desc.flags = flags0
-            raise
+        ws, wptr, wn = _scratch(prog, dev, N, nt, nx, True)
         with torch.cuda.device(dev):
-            if coef_grads is not None:
+            if coef_grads is not None:  # by-value coefficients: the layer-major engine (a descriptor with PINN_FLAG_LAYER_MAJOR)
                 assert coef_grads.is_cuda and coef_grads.dtype == torch.float32 and coef_grads.numel() >= 2
-                try:
-                    _lib.check(lib.pinn_residual_loss_grad_coef(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors,
-                                                                ctypes.byref(pd), x.data_ptr(), t.data_ptr(), N, float(grad_scale),
-                                                                r.data_ptr() if want_residual else None, s.data_ptr(),
-                                                                _grad_ptrs(prog, flat_grad), coef_grads.data_ptr(), wptr, wn,
-                                                                _stream(dev)))
-                finally:
-                    prog.desc.flags = flags0
+                _lib.check(lib.pinn_residual_loss_grad_coef(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors,
+                                                            ctypes.byref(pd), x.data_ptr(), t.data_ptr(), N, float(grad_scale),
+                                                            r.data_ptr() if want_residual else None, s.data_ptr(),
+                                                            _grad_ptrs(prog, flat_grad), coef_grads.data_ptr(), wptr, wn,
+                                                            _stream(dev)))
             else:
                 _lib.check(lib.pinn_residual_loss_grad(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors,
                                                        ctypes.byref(pd), x.data_ptr(), t.data_ptr(), N, float(grad_scale),
                                                        r.data_ptr() if want_residual else None, s.data_ptr(),
                                                        _grad_ptrs(prog, flat_grad), wptr, wn, _stream(dev)))
+    return r, s
+
+
+def inverse_kernel_name(prog: NetProgram, pd, N: int) -> str:
+    """Kernel a `residual_loss_grad_inverse` call on N points takes: "jet_kernel_u16" | "jet_kernel_wide" | "layer_major"."""
+    buf = ctypes.create_string_buffer(64)
+    _lib.check(_lib.load().pinn_inverse_kernel_name(ctypes.byref(prog.desc), ctypes.byref(pd), int(N), buf, len(buf)))
+    return buf.value.decode("ascii")
+
+
+def residual_loss_grad_inverse(prog: NetProgram, pd, coef_values: Tensor, x: Tensor, t: Tensor, grad_scale: float,
+                               flat_grad: Tensor, coef_grads: Optional[Tensor], loss_sum: Optional[Tensor] = None,
+                               want_residual: bool = False) -> Tuple[Optional[Tensor], Tensor]:
+    """`residual_loss_grad` for inverse problems, one launch: the four PDE coefficients are read at launch time from
+    `coef_values` (4 floats on the device; pd.coef is ignored — no host copy, so a captured graph follows the optimiser),
+    and coef_grads[k] += grad_scale * d(sum_n l(r_n))/d(c_k), k = 0, 1 (>= 2 floats on the device, or None)."""
+    lib = _lib.load()
+    dev = _require_device(x, t, flat_grad, coef_values, coef_grads, *prog.tensors)
+    if coef_values.dtype != torch.float32 or not coef_values.is_contiguous() or coef_values.numel() < 4:
+        raise ValueError("coef_values: 4 contiguous float32 values on the device")
+    if coef_grads is not None and (coef_grads.dtype != torch.float32 or not coef_grads.is_contiguous() or coef_grads.numel() < 2):
+        raise ValueError("coef_grads: at least 2 contiguous float32 values on the device")
+    x, t, N = _prep_points(prog, x, t)
+    r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
+    s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
+    if N:
+        nbytes = lib.pinn_inverse_workspace_bytes(ctypes.byref(prog.desc), ctypes.byref(pd), N)
+        ws = _workspace(dev, nbytes) if nbytes else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.pinn_residual_loss_grad_inverse(
+                ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors, ctypes.byref(pd), coef_values.data_ptr(),
+                x.data_ptr(), t.data_ptr(), N, float(grad_scale), r.data_ptr() if want_residual else None, s.data_ptr(),
+                _grad_ptrs(prog, flat_grad), coef_grads.data_ptr() if coef_grads is not None else None,
+                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev)))
     return r, s
 
 
@@ -591,16 +616,20 @@ class ResidualLossCoefFunction(torch.autograd.Function):
     """`ResidualLossFunction` for inverse problems: the PDE coefficients `coefs` (tensors in the order of PinnPdeDesc.coef,
     some of which require grad: live `nn.Parameter`s of `PDEBase._trainable_params`, pde_base.py:246-279) are inputs of the
     node, and their gradients come from the SAME launch as the weight gradient (fused `sum_n rbar_n dr_n/dc_k` reduction in the
-    residual epilogue) — no jets + torch epilogue, no second pass."""
+    residual epilogue, `residual_loss_grad_inverse`) — no jets + torch epilogue, no second pass.  The coefficient values
+    are stacked on the device and read by the kernel at launch time: no host copy, no descriptor rewrite."""
 
     @staticmethod
     def forward(ctx, prog: NetProgram, make_pd, x: Tensor, t: Tensor, n_total: int, n_coef: int, *coefs_and_params: Tensor):
         coefs = coefs_and_params[:n_coef]
-        pd = make_pd([float(c.detach()) for c in coefs])
+        pd = make_pd([])  # kind, dimension, loss; the coefficient slots of the descriptor are not read
         dev = x.device
+        cv = torch.zeros(4, dtype=torch.float32, device=dev)
+        for k, c in enumerate(coefs):
+            cv[k : k + 1].copy_(c.detach().reshape(1))  # device-to-device (and dtype conversion), no sync
         flat = new_flat_grad(prog, dev)
         cg = torch.zeros(4, dtype=torch.float32, device=dev)
-        _, s = residual_loss_grad(prog, pd, x, t, 1.0 / float(n_total), flat, coef_grads=cg)
+        _, s = residual_loss_grad_inverse(prog, pd, cv, x, t, 1.0 / float(n_total), flat, cg)
         ctx.flat, ctx.cg, ctx.prog, ctx.n_coef = flat, cg, prog, n_coef
         ctx.coef_meta = [(c.shape, c.dtype) for c in coefs]
         return (s / float(n_total)).reshape(())

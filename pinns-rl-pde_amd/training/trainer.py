@@ -356,14 +356,45 @@ class PDETrainer:
             return f"{type(self.pde).__name__} overrides compute_loss without a launch-list form (_manual_chain)"
         if own_loss and (self.pde._loss_weights() or {}).get("smoothness", 0.0) > 0:
             return "smoothness term"
-        if self.pde.dimension != 1 or self.pde._has_trainable_coefficients() or self.pde._training_mode() != "forward":
-            return "multi-dimensional, inverse or data-driven mode"
-        if getattr(self.pde, "observation_data", None):
+        if self.pde.dimension != 1:
+            return "multi-dimensional problem"
+        mode = self.pde._training_mode()
+        if mode == "data_only":
+            return "data_only mode"
+        if mode not in ("forward", "inverse", "data_augmented"):
+            return f"unknown training mode '{mode}'"
+        inverse = bool(len(getattr(self.pde, "_trainable_params", {}))) or self.pde._has_trainable_coefficients()
+        if inverse:
+            if self._coefficient_slots() is None:
+                return ("trainable parameters that are not themselves kernel coefficients (the residual reads a function "
+                        "of them: needs a chain rule)")
+            if self.rl_agent is not None or getattr(tc, "collocation_distribution", "uniform") == "residual_based":
+                return "residual-based or RL sampling with trainable coefficients (the sampler's launch takes coefficients by value)"
+        if self.process_group is not None and (inverse or mode != "forward"):
+            return "inverse or data-driven mode under a process group"
+        if getattr(self.pde, "observation_data", None) and mode == "forward":
             return "observation data term"
         ic = getattr(self.pde.config, "initial_condition", None) or {}
         if ic.get("type") == "random":
             return "random initial condition"
         return None
+
+    def _coefficient_slots(self):
+        """{slot k of `pde._coefficients()`: its nn.Parameter} when every trainable parameter of the PDE IS one of the (at
+        most two differentiated) kernel coefficients; None when some trainable parameter reaches the residual through a
+        function (pendulum's c0 = g / L) or not at all."""
+        params = list(getattr(self.pde, "_trainable_params", {}).values())
+        coefs = list(self.pde._coefficients())
+        slots = {}
+        for k, c in enumerate(coefs):
+            if isinstance(c, torch.Tensor) and c.requires_grad:
+                hit = [p for p in params if p is c]
+                if not hit or k >= 2 or c.numel() != 1:
+                    return None
+                slots[k] = hit[0]
+        if len(slots) != len(params):
+            return None
+        return slots
 
     def _build_flat_state(self):
         """Move the parameters into ONE flat fp32 buffer (each `nn.Parameter` becomes a view of it, same layout as the
@@ -401,6 +432,37 @@ class PDETrainer:
             "summary": torch.zeros(4, dtype=torch.float32, device=dev),
             "betas": g["betas"], "eps": g["eps"], "wd": g["weight_decay"],
         }
+        slots = self._coefficient_slots() if len(getattr(self.pde, "_trainable_params", {})) else None
+        if slots:
+            # inverse problems: the PDE coefficients live in a 4-float device buffer in `_coefficients()` order (what
+            # pinn_residual_loss_grad_inverse reads at launch time); each trainable nn.Parameter becomes a view of its slot,
+            # with its own Adam moments and step counter.  Non-trainable entries hold their constants.
+            F = self._flat
+            coef = torch.zeros(4, dtype=torch.float32, device=dev)
+            cm, cv = torch.zeros_like(coef), torch.zeros_like(coef)
+            csteps = 0.0
+            with torch.no_grad():
+                for k, c in enumerate(self.pde._coefficients()):
+                    if k in slots:
+                        p = slots[k]
+                        coef[k : k + 1].copy_(p.data.reshape(1))
+                        st = self.optimizer.state.get(p, {})
+                        if "exp_avg" in st:
+                            cm[k : k + 1].copy_(st["exp_avg"].reshape(1))
+                            cv[k : k + 1].copy_(st["exp_avg_sq"].reshape(1))
+                            csteps = float(st["step"])
+                        p.data = coef[k]
+                    else:
+                        coef[k] = float(c)
+            lo, hi = min(slots), max(slots) + 1  # at most two coefficients: the trainable ones are a contiguous slice
+            F["grad"] = torch.zeros(n + 8, dtype=torch.float32, device=dev)  # [gradient | loss sum, pad | coefficient gradients]
+            F.update({"coef": coef, "coef_m": cm, "coef_v": cv, "coef_grad": F["grad"][n + 4 : n + 8], "coef_slice": (lo, hi),
+                      "coef_step": torch.tensor([csteps], dtype=torch.float32, device=dev),
+                      "coef_scratch": torch.zeros(64, dtype=torch.float32, device=dev),
+                      "pd_inverse": _E.pde_desc(self.pde.KIND, self.pde.dimension, [], self.pde._loss_function_name(),
+                                                self.pde._huber_delta())})
+        F = self._flat
+        F["extra"] = torch.zeros(2, dtype=torch.float32, device=dev)  # {initial, data} when the chain carries a data term
         return self._flat
 
     def _chain(self, n_batch: int, world: int = 1):
@@ -413,6 +475,22 @@ class PDETrainer:
         if ch is None:
             ch = dict(self.pde._manual_chain(int(n_batch)))
             dev = self.device
+            obs = getattr(self.pde, "observation_data", None)
+            ch["has_data"] = False
+            if obs and self.pde._training_mode() in ("inverse", "data_augmented"):
+                # the data term l(model(obs) - u_obs) (pde_base.py:281-291): one more point range and one more term of the chain
+                dw = self.pde._data_loss_weight(1.0)
+                if dw <= 0.0:
+                    dw = 1.0
+                if len(ch["terms"]) + 1 > 8:
+                    raise NotImplementedError("more than 8 loss terms in the boundary / initial / data chain")
+                lo = ch["x"].shape[0]
+                xo = obs["x"].to(dev).float().reshape(-1, ch["x"].shape[1])
+                to = obs["t"].to(dev).float().reshape(-1, 1)
+                ch["x"] = torch.cat([ch["x"], xo], 0).contiguous()
+                ch["t"] = torch.cat([ch["t"], to], 0).contiguous()
+                ch["terms"] = list(ch["terms"]) + [(lo, lo + xo.shape[0], 0, 0, obs["u"].to(dev).float().reshape(-1).contiguous(), float(dw))]
+                ch["has_data"] = True
             K, npts = 1 + ch["nt"] + ch["nx"], ch["x"].shape[0]
             ch["term_losses"] = torch.zeros(len(ch["terms"]), dtype=torch.float32, device=dev)
             ch["cot"] = torch.zeros(K, npts, dtype=torch.float32, device=dev)
@@ -432,13 +510,20 @@ class PDETrainer:
         after the join, so no two launches ever write the same buffer concurrently."""
         F = self._flat
         prog = self.model.program()
-        pd = self.pde._pde_desc()
+        pd = None if "coef" in F else self.pde._pde_desc()  # trainable coefficients are never read on the host
         n, N = F["n"], x.shape[0]
         loss_name, delta = self.pde._loss_function_name(), self.pde._huber_delta()
         if self.process_group is not None:
             return self._manual_launches_dp(x, t, F, prog, pd, n, N, loss_name, delta)
 
         ch = self._chain(N)
+
+        def residual_launch():
+            if "coef" in F:  # trainable coefficients: read from the device buffer, cotangents into their gradient slots
+                _E.residual_loss_grad_inverse(prog, F["pd_inverse"], F["coef"], x, t, F["rw"] / float(N), F["grad"][:n],
+                                              F["coef_grad"], loss_sum=F["grad"][n : n + 1])
+            else:
+                _E.residual_loss_grad(prog, pd, x, t, F["rw"] / float(N), F["grad"][:n], loss_sum=F["grad"][n : n + 1])
 
         def boundary_chain(grad, summary):
             u = _E.jets_forward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"])
@@ -450,7 +535,7 @@ class PDETrainer:
 
         F["grad"].zero_()
         if side is None:
-            _E.residual_loss_grad(prog, pd, x, t, F["rw"] / float(N), F["grad"][:n], loss_sum=F["grad"][n : n + 1])
+            residual_launch()
             boundary_chain(F["grad"][:n], True)
         else:
             main = torch.cuda.current_stream(self.device)
@@ -458,7 +543,7 @@ class PDETrainer:
             with torch.cuda.stream(side):
                 F["grad_side"].zero_()
                 u = boundary_chain(F["grad_side"], False)
-            _E.residual_loss_grad(prog, pd, x, t, F["rw"] / float(N), F["grad"][:n], loss_sum=F["grad"][n : n + 1])
+            residual_launch()
             main.wait_stream(side)
             if not torch.cuda.is_current_stream_capturing():
                 u.record_stream(main)
@@ -467,9 +552,22 @@ class PDETrainer:
             # kernel runs once more here; it rewrites the same cotangents
             _E.jet_losses(u, ch["terms"], loss_name, delta, ch["term_losses"], ch["cot"], residual_sum=F["grad"][n : n + 1],
                           residual_scale=1.0 / float(N), residual_weight=F["rw"], n_boundary_terms=ch["n_bc"], summary4=F["summary"])
+        F["has_data"] = ch["has_data"]
+        if ch["has_data"]:
+            # summary4's `initial` is "all terms after the boundary ones": split the data term (the last one) out of it
+            tl = ch["term_losses"]
+            F["extra"][0:1].copy_(tl[ch["n_bc"] : -1].sum(0, keepdim=True))
+            F["extra"][1:2].copy_(tl[-1:])
         _E.adam_clip_step(F["theta"], F["grad"], F["m"], F["v"], F["lr"], F["step"], F["scratch"], beta1=F["betas"][0],
                           beta2=F["betas"][1], eps=F["eps"], weight_decay=F["wd"],
                           max_norm=float(self.config.training.gradient_clipping))
+        if "coef" in F:
+            # the reference clips model.parameters() only (trainer.py:690-694) and steps everything with one Adam: the same
+            # update rule on the trainable coefficient slice, unclipped, with its own step counter
+            lo, hi = F["coef_slice"]
+            _E.adam_clip_step(F["coef"][lo:hi], F["coef_grad"][lo:hi], F["coef_m"][lo:hi], F["coef_v"][lo:hi], F["lr"],
+                              F["coef_step"], F["coef_scratch"], beta1=F["betas"][0], beta2=F["betas"][1], eps=F["eps"],
+                              weight_decay=F["wd"], max_norm=0.0)
 
     def _manual_launches_dp(self, x, t, F, prog, pd, n, N, loss_name, delta):
         """The same launch list under a process group (one process per GPU): this rank's contiguous shard of the
@@ -498,9 +596,15 @@ class PDETrainer:
         summary buffer (what a captured graph refreshes in place); otherwise independent copies, so that a caller may
         keep one per step (`train()` averages them per epoch)."""
         s = self._flat["summary"]
+        e = self._flat["extra"]
         if not static:
-            s = s.clone()
-        return {"residual": s[0], "boundary": s[1], "initial": s[2], "total": s[3]}
+            s, e = s.clone(), e.clone()
+        out = {"residual": s[0], "boundary": s[1], "initial": s[2], "total": s[3]}
+        if self._flat.get("has_data"):
+            out["initial"], out["data"] = e[0], e[1]
+        elif self.pde._training_mode() in ("inverse", "data_augmented"):
+            out["data"] = torch.zeros((), dtype=torch.float32, device=s.device)
+        return out
 
     def get_training_history(self):  # trainer.py:966-972
         return self.history
