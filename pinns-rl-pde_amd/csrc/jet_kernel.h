@@ -85,7 +85,7 @@ struct KernelArgs {
   const float* res_bar;                     // MODE_PDE backward, nullable: external cotangent of r (N floats)
   float* tape;                              // BWD workspace
   long long tape_stride;                    // floats per workgroup
-  unsigned long long* stamps;               // diagnostic builds (-DPINN_STAMPS) only: [grid][4 waves][kNumStamps] cycles
+  unsigned long long* stamps;               // diagnostic builds (-DPINN_STAMPS) only: [grid][waves of the workgroup][kNumStamps] cycles
   long long det_stride;                     // deterministic mode: the gradient / loss pointers above point into row 0 of a
                                             // [grid][det_stride] slab and workgroup b adds (plainly) into row b; 0 = atomics
   int det_mask;                             // two-level flush (det_stride < 0): rows - 1, a power of two minus one
@@ -129,7 +129,7 @@ inline hipError_t allow_full_lds(const void* kern) {
 // In-kernel phase timing for diagnostic builds; in normal builds these expand to nothing.
 constexpr int kNumStamps = 16;
 enum { ST_STAGE = 0, ST_ENCODE, ST_FWD_GEMM, ST_FWD_EW, ST_OUT, ST_EPI, ST_B0, ST_BWD_EW, ST_BWD_STREAM, ST_BWD_FLUSH,
-       ST_ENC_BWD, ST_TOTAL, ST_BWD_DX, ST_BWD_PUT };
+       ST_ENC_BWD, ST_TOTAL, ST_BWD_DX, ST_BWD_PUT, ST_BARRIER, ST_BWD_DB };
 #ifdef PINN_STAMPS
 #define PINN_STAMP_DECL unsigned long long st_acc[kNumStamps] = {}; unsigned long long st_prev = pinn_now(); const unsigned long long st_begin = st_prev;
 #define PINN_STAMP(idx) do { const unsigned long long st_now = pinn_now(); st_acc[idx] += st_now - st_prev; st_prev = st_now; } while (0)

@@ -19,6 +19,16 @@
 //   * The pre-activation records that the reverse sweep replays (layers 0 .. n_layers - 2) stay in two LDS images,
 //     and the last layer's record is parked in the wave's own columns of the idle a_{l-1} image: no tape in global
 //     memory, no workspace besides the store-flush slab.
+//   * Barriers.  The forward sweep ping-pongs between the images X and A2 (one barrier per layer boundary); the
+//     encoding goes to the image that makes the last layer read X, so the reverse sweep always has zbar in X and
+//     a_{l-1} in A2.  The coordinates of the workgroup's next unit are stored into the other half of a double buffer
+//     during the current unit, so a unit starts with one barrier.  In the reverse sweep the two waves of a SIMD
+//     (w and w + 4) run a layer's two GEMMs in opposite order, so that the activation adjoint of each (VALU) runs
+//     beside a GEMM of the other.  Ten barriers per unit for three MFMA layers behind Fourier features.
+//   * Registers.  The reverse kernel sits at the 256-VGPR limit of two waves per SIMD, and what the optimizer hoists
+//     out of the unit loop is spilled.  So running sums that one phase alone touches (dw_out per lane, loss, db_out)
+//     and the PDE coefficients live in LDS, and addresses used once per unit or once per kernel are formed from an
+//     opaque copy of the thread index where they are used (u16_opaque).
 //   * No atomics: per-lane partial sums (db, dw_out, db_out, loss) and the weight-gradient tiles are written once per
 //     workgroup into row blockIdx.x of the slab, and units run in a fixed order, so results are bitwise
 //     reproducible from run to run.
@@ -26,6 +36,14 @@
 #include "jet_kernel_wide.h"
 
 namespace pinn {
+
+// workgroup barrier; the diagnostic build books the time up to it on phase idx and the wait itself on ST_BARRIER
+#define U16_BARRIER(idx)     \
+  do {                       \
+    PINN_STAMP(idx);         \
+    __syncthreads();         \
+    PINN_STAMP(ST_BARRIER);  \
+  } while (0)
 
 constexpr int kU = 16;          // points per unit
 constexpr int kUP = 132;        // LDS row of an image: 128 features + 4 floats of pad
@@ -36,6 +54,12 @@ constexpr int kUImgS = kU * kUP;  // floats per stream of an image
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// a value the optimizer cannot trace back to its source: what is derived from it is computed where it is used
+__device__ __forceinline__ int u16_opaque(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
 }
 
 // pre-activation jets of encoding feature j at point n of the unit (xin: [c][kU])
@@ -269,9 +293,11 @@ __device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
 // COEF = true (reverse launches only, jet_u16c_* units): inverse problems.  The PDE coefficients come from the device
 // array a.pde.coef_dev, read once at kernel start, and the writer lanes also sum rbar dr/dc_0, rbar dr/dc_1; the two
 // sums go to a.pde.dcoef in this workgroup's slab row (the padding of the loss-sum slot).  The reverse kernel has no
-// VGPR to spare (254 without COEF), so neither the coefficients nor the two running sums live in registers across the
-// unit loop: both sit in the 4-float row pad of the stream-0 rows of image X, which no GEMM, put or encode touches —
-// X[n][128], X[n][129]: the sums of writer lane n; X[k][130], k < 4: coefficient c_k.
+// VGPR to spare, so neither the coefficients nor the two running sums live in registers across the unit loop: both
+// sit in the 4-float row pad of the stream-0 rows of image X, which no GEMM, put or encode touches —
+// X[n][128], X[n][129]: the sums of writer lane n (COEF only); X[k][130], k < 4: coefficient c_k (every variant: the
+// by-value coefficients are staged there too, so that products of them are formed in the epilogue and not held in
+// VGPRs across the unit loop).
 template <int ACT, int NT, int NX, bool BWD, int NA0, bool COEF = false>
 __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs a) {
   constexpr int K = 1 + NT + NX;
@@ -281,16 +307,20 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   constexpr int img = K * kUImgS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const NetDev& net = a.net;
-  float* X = smem;                    // forward activations; zbar in the reverse sweep
-  float* A2 = X + img;                // reverse sweep: a_{l-1}; forward: the last layer's parked record
+  float* X = smem;                    // forward activations (ping-pong with A2); zbar in the reverse sweep
+  float* A2 = X + img;                // forward activations; the last layer's parked record; reverse sweep: a_{l-1}
   float* REC = A2 + img;              // records of layers 0, 1 (replayed in the reverse sweep)
   float* UP = REC + 2 * img;          // kUWaves * K * kU: per-wave partial sums of the output layer
-  float* xin = UP + kUWaves * K * kU;  // kMaxDin * kU
-  float* wb = xin + kMaxDin * kU;      // (1 + n_layers) * 128: w_out, then the hidden-layer biases
+  float* xin2 = UP + kUWaves * K * kU;  // 2 * kMaxDin * kU: coordinates of this unit and of the workgroup's next one
+  float* wb = xin2 + 2 * kMaxDin * kU;     // (1 + n_layers) * 128: w_out, then the hidden-layer biases
   float* ep = wb + (1 + kPersist) * kUH;  // (kMaxDin + 1) * 128: encoding parameters
   float* pl = ep + (kMaxDin + 1) * kUH;   // (kPersist + kMaxDin + 1) * 128: per-feature db of the MFMA layers, then the
                                           // first-Linear gradient partials (thread tid < 128 owns feature tid)
+  float* pdwl = pl + (kPersist + kMaxDin + 1) * kUH;  // kUThreads * 4: per-lane partial dw_out (reverse launches; no
+                                                      // VGPRs to spare for a running sum that B0 alone touches)
+  float* psl = pdwl + 4 * kUThreads;  // 2 * kU: running loss and db_out sums of the writer lanes (tid < kU), same reason
 
+  PINN_STAMP_DECL
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
@@ -316,14 +346,19 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       X[tid * kUP + kUH] = 0.0f;
       X[tid * kUP + kUH + 1] = 0.0f;
     }
-    if (tid < 4) X[tid * kUP + kUH + 2] = a.pde.coef_dev[tid];  // visible after the unit loop's first barrier
+  }
+  // the coefficients of every launch sit in the row pad (below): values formed from them are then formed in the
+  // epilogue, where registers are free, instead of being held (and spilled) across the unit loop
+  if (tid < 4) {  // visible after the unit loop's first barrier
+    const float cv = tid == 0 ? a.pde.c0 : tid == 1 ? a.pde.c1 : tid == 2 ? a.pde.c2 : a.pde.c3;
+    X[tid * kUP + kUH + 2] = COEF ? a.pde.coef_dev[tid] : cv;
   }
 
   f32x4 pt[NPT];
 #pragma unroll
   for (int t = 0; t < NPT; ++t) pt[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  f32x4 pdw = {0.0f, 0.0f, 0.0f, 0.0f};  // per-lane partial dw_out
-  float pdb_out = 0.0f, ploss = 0.0f;
+  if constexpr (BWD) *reinterpret_cast<f32x4*>(pdwl + 4 * tid) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};  // lane-private
+  if (tid < 2 * kU) psl[tid] = 0.0f;  // lane-private from here on: slot tid and slot kU + tid of lane tid < kU
 
   float xr[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
   auto fetch_coords = [&](long long u) {
@@ -337,15 +372,24 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       }
     }
   };
+  auto put_coords = [&](float* dst) {
+    if (tid < kU) {
+#pragma unroll
+      for (int cc = 0; cc < kMaxDin; ++cc) dst[cc * kU + tid] = xr[cc];
+    }
+  };
   fetch_coords(blockIdx.x);
+  put_coords(xin2);
+  int xpar = 0;
 
   for (long long u = blockIdx.x; u < nunits; u += gridDim.x) {
     const long long p0 = u * kU;
-    __syncthreads();  // previous unit's readers of xin / X / A2 / UP are done
-    if (tid < kU) {
-#pragma unroll
-      for (int cc = 0; cc < kMaxDin; ++cc) xin[cc * kU + tid] = xr[cc];
-    }
+    // previous unit's readers of X / A2 / UP are done; this unit's coordinates (stored during the previous unit, into
+    // the half of xin2 that unit did not read) are visible
+    U16_BARRIER(ST_BWD_FLUSH);
+    const float* xin = xin2 + xpar * (kMaxDin * kU);
+    float* xin_next = xin2 + (xpar ^ 1) * (kMaxDin * kU);
+    xpar ^= 1;
     fetch_coords(u + gridDim.x);
     f32x4 w0, w1;  // first two weight blocks of the next GEMM, requested a phase ahead
     {
@@ -354,9 +398,14 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       w0 = u16_wload<false>(L0.W, L0.ld, off, 0);
       w1 = u16_wload<false>(L0.W, L0.ld, off, L0.in_dim > 16 ? 1 : 0);
     }
-    __syncthreads();
-    u16_encode<ACT, NT, NX>(net, ep, xin, X, tid);
-    __syncthreads();
+    PINN_STAMP(ST_STAGE);
+    // The forward sweep ping-pongs between X and A2: layer l reads one image and puts its activations into the other,
+    // so a layer boundary is one barrier.  The encoding goes where the parity of n_layers makes the LAST layer read X:
+    // its record is then parked in A2 and the reverse sweep finds zbar -> X, a_{l-1} -> A2 for every n_layers.
+    float* src = (nl & 1) ? X : A2;
+    float* dst = (nl & 1) ? A2 : X;
+    u16_encode<ACT, NT, NX>(net, ep, xin, src, u16_opaque(tid));  // opaque: addresses formed here, not held over the loop
+    U16_BARRIER(ST_ENCODE);
 
     // ---- hidden layers ----
     f32x4 acc[K];
@@ -367,9 +416,11 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
 #pragma unroll
       for (int s = 0; s < K; ++s) acc[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       if (on) {
-        u16_gemm<K, false>(acc, Ly.W, Ly.ld, u16_rows_off(16 * wv, Ly.ld, c, g), w0, w1, Ly.in_dim >> 4, X + c * kUP + 4 * g);
+        u16_gemm<K, false>(acc, Ly.W, Ly.ld, u16_rows_off(16 * wv, Ly.ld, c, g), w0, w1, Ly.in_dim >> 4, src + c * kUP + 4 * g);
         acc[0] += *reinterpret_cast<const f32x4*>(wb + (1 + l) * kUH + frow);
       }
+      if (l == 0) put_coords(xin_next);  // the loads had the encoding and a GEMM to land; last read two barriers ago
+      PINN_STAMP(ST_FWD_GEMM);
       if (!last) {
         {
           const LayerDev Ln = uniform_layer(net.layer[l + 1]);
@@ -382,15 +433,19 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           u16_ew_forward<ACT, NT, NX>(acc, Ly.act_param, rec);
           if constexpr (BWD) u16_put<K>(REC + l * img + ioff, rec);
         }
-        __syncthreads();  // every wave has finished reading X: overwrite in place
-        if (on) u16_put<K>(X + ioff, acc);
-        __syncthreads();
+        // dst was last read a barrier ago (by the GEMMs of layer l-1, or by the previous unit's reverse sweep)
+        if (on) u16_put<K>(dst + ioff, acc);
+        U16_BARRIER(ST_FWD_EW);
+        float* const t = src;
+        src = dst;
+        dst = t;
       } else if (on) {  // last hidden layer: activations stay in acc, the record is parked in this wave's columns of A2
         f32x4 rec[K];
         u16_ew_forward<ACT, NT, NX>(acc, Ly.act_param, rec);
         if constexpr (BWD) u16_put<K>(A2 + ioff, rec);
       }
     }
+    PINN_STAMP(ST_FWD_EW);
 
     // ---- output layer (H_last -> 1): lane partials -> wave partials in LDS -> every lane sums ----
     {
@@ -407,7 +462,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         for (int s = 0; s < K; ++s) UP[(wv * K + s) * kU + c] = po[s];
       }
     }
-    __syncthreads();
+    U16_BARRIER(ST_OUT);
 
     // ---- epilogue, evaluated by every lane for its point c (32 lanes per point, same values) ----
     float ub[K];
@@ -431,15 +486,11 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         }
       } else {
         float d[K];
-        PdeDev pde_c;
-        if constexpr (COEF) {
-          pde_c = a.pde;
-          pde_c.c0 = X[0 * kUP + kUH + 2];
-          pde_c.c1 = X[1 * kUP + kUH + 2];
-          pde_c.c2 = X[2 * kUP + kUH + 2];
-          pde_c.c3 = X[3 * kUP + kUH + 2];
-        }
-        const PdeDev& pde = COEF ? pde_c : a.pde;
+        PdeDev pde = a.pde;
+        pde.c0 = X[0 * kUP + kUH + 2];
+        pde.c1 = X[1 * kUP + kUH + 2];
+        pde.c2 = X[2 * kUP + kUH + 2];
+        pde.c3 = X[3 * kUP + kUH + 2];
         const float r = pde_residual<NT, NX>(pde, j, xin[c], d);
         float dl;
         float lt = loss_term(pde, r, &dl);
@@ -448,7 +499,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           dl = 0.0f;
         }
         if (writer && ok && a.residual_out) a.residual_out[p] = r;
-        if (writer) ploss += lt;
+        if (writer) psl[c] += lt;
         const float rb = !BWD ? 0.0f : a.res_bar ? (ok ? a.res_bar[p] : 0.0f) : a.grad_scale * dl;
 #pragma unroll
         for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
@@ -463,9 +514,10 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       }
     }
 
+    PINN_STAMP(ST_EPI);
     if constexpr (!BWD) continue;
     // ---- B0: output layer.  dw_out partials stay per lane; abar = w_out (x) ub, then the last layer's adjoint ----
-    if (tid < kU) pdb_out += ub[0];
+    if (tid < kU) psl[kU + c] += ub[0];
     f32x4 ab[K];
     {
       const LayerDev Lz = uniform_layer(net.layer[nl - 1]);
@@ -475,6 +527,8 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       if (16 * wv < Lz.out_dim) {
         f32x4 rec[K];
         u16_get<K>(A2 + ioff, rec);
+        float* const pdwp = pdwl + 4 * u16_opaque(tid);
+        f32x4 pdw = *reinterpret_cast<const f32x4*>(pdwp);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float z[K], y[K];
@@ -486,9 +540,11 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           for (int s = 0; s < K; ++s) gg = fmaf(ub[s], y[s], gg);
           pdw[r] += gg;
         }
+        *reinterpret_cast<f32x4*>(pdwp) = pdw;
         u16_ew_backward<ACT, NT, NX>(ab, Lz.act_param, rec);
       }
     }
+    PINN_STAMP(ST_B0);
 
     for (int l = nl - 1; l >= 0; --l) {
       const LayerDev Ly = uniform_layer(net.layer[l]);
@@ -497,7 +553,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       const bool kon = 16 * wv < Ly.in_dim;  // this wave owns input-feature rows of the layer
       // the GEMMs of layer l+1 have finished reading X (zbar) and A2; with a single MFMA layer the barrier keeps
       // u16_encode (all columns of A2, below) from overwriting another wave's parked record before its B0 has read it
-      if (l + 1 < nl || nl == 1) __syncthreads();
+      if (l + 1 < nl || nl == 1) U16_BARRIER(ST_BWD_EW);
       if (on) u16_put<K>(X + ioff, ab);
       float pw = 0.0f;  // act_param of layer l-1
       if (l > 0) {
@@ -518,46 +574,61 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           u16_put<K>(A2 + ioff, y);
         }
       } else {
-        u16_encode<ACT, NT, NX>(net, ep, xin, A2, tid);
+        u16_encode<ACT, NT, NX>(net, ep, xin, A2, u16_opaque(tid));
       }
       const unsigned coff = u16_cols_off(kon ? 16 * wv : 0, Ly.ld, c, g);
       if (need_abar) {  // requests hide under the barrier
         w0 = u16_wload<true>(Ly.W, Ly.ld, coff, 0);
         w1 = u16_wload<true>(Ly.W, Ly.ld, coff, 1);
       }
-      __syncthreads();
+      U16_BARRIER(ST_BWD_PUT);
       if (Ly.db && tid < Ly.out_dim) {
         float gsum = 0.0f;
 #pragma unroll
         for (int n = 0; n < kU; ++n) gsum += X[n * kUP + tid];
         pl[l * kUH + tid] += gsum;
       }
-      // abar_{l-1} = W^T zbar for all streams
-      if (need_abar) {
+      PINN_STAMP(ST_BWD_DB);
+      // The two GEMMs of the layer read only LDS and weights and do not depend on each other, and the activation
+      // adjoint of layer l-1 needs only abar and the wave's own record columns.  The SIMD partners (waves w and w + 4)
+      // take them in opposite order, so that each one's adjoint (VALU) runs beside a GEMM of the other:
+      //   waves 0-3: abar, adjoint, dW        waves 4-7: dW, abar, adjoint
+      // No accumulator changes its summation order.
+      const bool dw_first = wv >= 4;
 #pragma unroll
-        for (int s = 0; s < K; ++s) ab[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (kon) u16_gemm<K, true>(ab, Ly.W, Ly.ld, coff, w0, w1, Ly.out_dim >> 4, X + c * kUP + 4 * g);
-      }
-      // dW (persistent), then the activation adjoint of layer l-1
-      if (on && Ly.dW) {
-        const float* zl = X + 4 * g * kUP + 16 * wv + c;
-        const float* al = A2 + 4 * g * kUP + c;
-        const int na = Ly.in_dim >> 4;
-        if (l == 0) u16_outer<K, 0, NA0, NPT>(pt, na, zl, al);
-        else if (l == 1) u16_outer<K, NA0, NKT, NPT>(pt, na, zl, al);
-        else u16_outer<K, NA0 + NKT, NKT, NPT>(pt, na, zl, al);
-      }
-      if (l > 0 && kon) {
-        f32x4 rec[K];
-        u16_get<K>(REC + (l - 1) * img + ioff, rec);
-        u16_ew_backward<ACT, NT, NX>(ab, pw, rec);
+      for (int half = 0; half < 2; ++half) {
+        // dW (persistent tiles): first for waves 4-7, last for waves 0-3
+        if ((half == 0) == dw_first && on && Ly.dW) {
+          const float* zl = X + 4 * g * kUP + 16 * wv + c;
+          const float* al = A2 + 4 * g * kUP + c;
+          const int na = Ly.in_dim >> 4;
+          if (l == 0) u16_outer<K, 0, NA0, NPT>(pt, na, zl, al);
+          else if (l == 1) u16_outer<K, NA0, NKT, NPT>(pt, na, zl, al);
+          else u16_outer<K, NA0 + NKT, NKT, NPT>(pt, na, zl, al);
+        }
+        if ((half == 0) == dw_first) PINN_STAMP(ST_BWD_STREAM);
+        if (half == 1) break;
+        // abar_{l-1} = W^T zbar for all streams
+        if (need_abar) {
+#pragma unroll
+          for (int s = 0; s < K; ++s) ab[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          if (kon) u16_gemm<K, true>(ab, Ly.W, Ly.ld, coff, w0, w1, Ly.out_dim >> 4, X + c * kUP + 4 * g);
+        }
+        PINN_STAMP(ST_BWD_DX);
+        // activation adjoint of layer l-1; the record is read here, not ahead of a GEMM
+        if (l > 0 && kon) {
+          f32x4 rec[K];
+          u16_get<K>(REC + (l - 1) * img + ioff, rec);
+          u16_ew_backward<ACT, NT, NX>(ab, pw, rec);
+        }
+        PINN_STAMP(ST_BWD_EW);
       }
     }
 
     // ---- encoding backward (first Linear of feedforward / SIREN) ----
     if (net.enc == ENC_LINEAR && net.d_encW) {
       const int H = net.enc_out;
-      __syncthreads();
+      U16_BARRIER(ST_ENC_BWD);
       if (16 * wv < H) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -571,75 +642,90 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         }
         u16_put<K>(X + ioff, ab);
       }
-      __syncthreads();
-      if (tid < H) {
+      U16_BARRIER(ST_ENC_BWD);
+      const int te = u16_opaque(tid);  // keeps the pl addresses below out of the unit loop's live registers
+      if (te < H) {
         float gb = 0.0f, gt = 0.0f, gx = 0.0f;
         float gw[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 4
         for (int n = 0; n < kU; ++n) {
-          const float vv = X[n * kUP + tid];
+          const float vv = X[n * kUP + te];
           gb += vv;
 #pragma unroll
           for (int cc = 0; cc < kMaxDin; ++cc)
             if (cc < din) gw[cc] = fmaf(vv, xin[cc * kU + n], gw[cc]);
-          if constexpr (NT >= 1) gt += X[1 * kUImgS + n * kUP + tid];
-          if constexpr (NX >= 1) gx += X[(1 + NT) * kUImgS + n * kUP + tid];
+          if constexpr (NT >= 1) gt += X[1 * kUImgS + n * kUP + te];
+          if constexpr (NX >= 1) gx += X[(1 + NT) * kUImgS + n * kUP + te];
         }
 #pragma unroll
-        for (int cc = 0; cc < kMaxDin; ++cc) pl[(kPersist + cc) * kUH + tid] += gw[cc] + (cc == din - 1 ? gt : 0.0f) + (cc == 0 ? gx : 0.0f);
-        pl[(kPersist + kMaxDin) * kUH + tid] += gb;
+        for (int cc = 0; cc < kMaxDin; ++cc) pl[(kPersist + cc) * kUH + te] += gw[cc] + (cc == din - 1 ? gt : 0.0f) + (cc == 0 ? gx : 0.0f);
+        pl[(kPersist + kMaxDin) * kUH + te] += gb;
       }
+      PINN_STAMP(ST_ENC_BWD);
     }
   }
 
   // ---- one flush per workgroup: reverse launches store into row blockIdx.x of the slab (a.flush_store: every address
   // written once); a forward-only launch adds its loss sum as the 32-point kernel does ----
+  // The flush addresses are derived from an opaque copy of the thread index: computed from tid itself they are
+  // hoisted above the unit loop, where the kernel has no VGPR to spare, and spilled.
+  const int tf = u16_opaque(tid);
+  const int cf = tf & 15, frowf = 16 * wv + 4 * ((tf & 63) >> 4);
   const long long doff = det_row_offset(a);
   if (a.mode == MODE_PDE && a.loss_sum && wv == 0) {
-    float sacc = tid < kU ? ploss : 0.0f;
+    float sacc = tf < kU ? psl[tf] : 0.0f;
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) sacc += __shfl_xor(sacc, o);
-    if (tid == 0) grad_put(a.loss_sum, sacc, doff, a.flush_store != 0);
+    if (tf == 0) grad_put(a.loss_sum, sacc, doff, a.flush_store != 0);
   }
+#ifdef PINN_STAMPS
+  auto write_stamps = [&]() {  // [grid][8 waves][kNumStamps]
+    if (a.stamps && (tf & 63) == 0) {
+      st_acc[ST_TOTAL] = pinn_now() - st_begin;
+      for (int i = 0; i < kNumStamps; ++i) a.stamps[((long long)blockIdx.x * kUWaves + wv) * kNumStamps + i] = st_acc[i];
+    }
+  };
+  if constexpr (!BWD) write_stamps();
+#endif
   if constexpr (!BWD) return;
   if constexpr (COEF) {
     if (a.mode == MODE_PDE && a.pde.dcoef && wv == 0) {
-      float s0 = tid < kU ? X[tid * kUP + kUH] : 0.0f, s1 = tid < kU ? X[tid * kUP + kUH + 1] : 0.0f;
+      float s0 = tf < kU ? X[tf * kUP + kUH] : 0.0f, s1 = tf < kU ? X[tf * kUP + kUH + 1] : 0.0f;
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) {
         s0 += __shfl_xor(s0, o);
         s1 += __shfl_xor(s1, o);
       }
-      if (tid == 0) {
+      if (tf == 0) {
         a.pde.dcoef[doff] = s0;
         a.pde.dcoef[doff + 1] = s1;
       }
     }
   }
   if (net.db_out && wv == 0) {
-    float gsum = tid < kU ? pdb_out : 0.0f;
+    float gsum = tf < kU ? psl[kU + tf] : 0.0f;
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) gsum += __shfl_xor(gsum, o);
-    if (tid == 0) net.db_out[doff] = gsum;
+    if (tf == 0) net.db_out[doff] = gsum;
   }
-  if (net.enc == ENC_LINEAR && net.d_encW && tid < net.enc_out) {
+  if (net.enc == ENC_LINEAR && net.d_encW && tf < net.enc_out) {
 #pragma unroll
     for (int cc = 0; cc < kMaxDin; ++cc)
-      if (cc < din) net.d_encW[doff + tid * din + cc] = pl[(kPersist + cc) * kUH + tid];
-    if (net.d_encb) net.d_encb[doff + tid] = pl[(kPersist + kMaxDin) * kUH + tid];
+      if (cc < din) net.d_encW[doff + tf * din + cc] = pl[(kPersist + cc) * kUH + tf];
+    if (net.d_encb) net.d_encb[doff + tf] = pl[(kPersist + kMaxDin) * kUH + tf];
   }
-  pdw = row16_sum4(pdw);
-  if (net.dw_out && c == 0 && frow < net.h_last) *reinterpret_cast<f32x4*>(net.dw_out + doff + frow) = pdw;
+  const f32x4 pdw = row16_sum4(*reinterpret_cast<const f32x4*>(pdwl + 4 * tf));
+  if (net.dw_out && cf == 0 && frowf < net.h_last) *reinterpret_cast<f32x4*>(net.dw_out + doff + frowf) = pdw;
 #pragma unroll
   for (int p = 0; p < kPersist; ++p) {
     if (p < nl) {
       const LayerDev Lp = uniform_layer(net.layer[p]);
-      if (Lp.db && tid < Lp.out_dim) Lp.db[doff + tid] = pl[p * kUH + tid];
+      if (Lp.db && tf < Lp.out_dim) Lp.db[doff + tf] = pl[p * kUH + tf];
       if (16 * wv >= Lp.out_dim) continue;
       if (Lp.dW) {
         const int na = Lp.in_dim >> 4;
         const int off = p == 0 ? 0 : p == 1 ? NA0 : NA0 + NKT;
-        float* base = Lp.dW + doff + (long long)frow * Lp.ld + c;
+        float* base = Lp.dW + doff + (long long)frowf * Lp.ld + cf;
 #pragma unroll
         for (int t = 0; t < NPT; ++t) {
           if (t >= off && t - off < na && (p != 0 || t < NA0) && (p != 1 || t < NA0 + NKT)) {
@@ -650,11 +736,15 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       }
     }
   }
+#ifdef PINN_STAMPS
+  PINN_STAMP(ST_BWD_FLUSH);
+  write_stamps();
+#endif
 }
 
 inline size_t jet_u16_lds_bytes(int K) {
-  return sizeof(float) * ((size_t)4 * K * kUImgS + kUWaves * K * kU + kMaxDin * kU + (1 + kPersist) * kUH +
-                          (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH);
+  return sizeof(float) * ((size_t)4 * K * kUImgS + kUWaves * K * kU + 2 * kMaxDin * kU + (1 + kPersist) * kUH +
+                          (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH + 4 * kUThreads + 2 * kU);
 }
 
 
