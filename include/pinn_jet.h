@@ -252,10 +252,10 @@ int pinn_residual_backward(const PinnNetDesc* net, const float* const* weights, 
                            size_t ws_bytes, void* stream);
 
 /* ---- training step (pinnrl/training/trainer.py:686-698, pinnrl/pdes/pde_base.py:1101-1165) -------------------------
- * With these two entry points a whole optimiser step is a handful of launches with no autograd in it (and can be
+ * With these entry points a whole optimiser step is a handful of launches with no autograd in it (and can be
  * captured in a HIP graph): pinn_residual_loss_grad for the residual term, pinn_jet_forward / pinn_jet_backward
  * (orders 0, 0) for the network values on the boundary / initial points, pinn_point_losses for their loss terms,
- * pinn_adam_clip_step for clip_grad_norm_ + Adam. */
+ * pinn_adam_clip_step for clip_grad_norm_ + Adam — or, with adaptive loss weights, pinn_adaptive_adam_step. */
 #define PINN_MAX_POINT_TERMS 8
 
 /* Term k (k < n_terms) covers points [lo[k], hi[k]) of u and has its own target array of hi[k] - lo[k] floats:
@@ -289,6 +289,37 @@ int pinn_jet_losses(const float* jets, int32_t n_streams, int32_t n_total, int32
 int pinn_adam_clip_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr,
                         float beta1, float beta2, float eps, float weight_decay, float max_norm, float* step,
                         float* scratch64, float* grad_norm_out, void* stream);
+
+/* Adaptive loss weights (pinnrl/components/adaptive_weights.py:35-107, the trainer block trainer.py:586-684) fused with the
+ * optimiser step: weight update + combination of the component gradients + clip_grad_norm_ + Adam, all on the device.
+ * The weights are detached numbers, so the gradient of  total = sum_c w_c L_c  is  sum_c w_c grad(L_c).
+ *   comp_grads   n_components (<= 4) rows of `ld` >= n floats: row c = gradient of the UNweighted component c
+ *                (the trainer: residual, boundary, initial);
+ *   comp_losses  HOST table of n_components device pointers, one float each; L_c = comp_losses[c][0] * loss_scales[c]
+ *                (loss_scales: host, nullable = ones; e.g. a residual launch's loss sum with scale 1 / N);
+ *   strategy     PINN_ADAPTIVE_RBW: v = L (loss magnitudes), PINN_ADAPTIVE_LRW: v_c = |grad(L_c)|_2;
+ *   initial_weights  host, n_components floats, nullable = ones: the weights of the first call;
+ *   state16      16 device floats owned by the caller, zero before the first call:
+ *                {running[4], prev_weights[4], weights[4], calls, has_prev, -, -};
+ *   weights4_out (nullable) the weights of this step, padded with 0;  summary4 (nullable) {L_0, L_1, L_2, sum_c w_c L_c};
+ *   grad_norm_out (nullable) the norm of the combined gradient before clipping;  grad_out (nullable) the combined
+ *                gradient before clipping, n floats — it is not written to memory otherwise;
+ *   scratch      PINN_ADAPTIVE_SCRATCH_FLOATS floats, 8-byte aligned;  the rest as pinn_adam_clip_step (`step` is incremented).
+ * The rule: first call running = v, weights = initial_weights; later calls running = alpha running + (1 - alpha) v and
+ * LRW  w = inv / sum(inv), inv = 1 / (running + aw_eps);  RBW  w = running / (sum(running) + aw_eps), smoothed with the
+ * previous RBW weights from the third call on (w = alpha prev + (1 - alpha) w).
+ * Three launches: a Gram pass <g_a, g_b> over a fixed grid (partials and their sum in double, fixed order), one workgroup
+ * for the rule and the clip norm sqrt(w^T G w) (the only launch that writes the state), the update pass.  No atomics:
+ * bit-identical across runs.  16-byte loads where params / moments / rows (base and ld) are 16-byte aligned, else scalar. */
+#define PINN_ADAPTIVE_RBW 0
+#define PINN_ADAPTIVE_LRW 1
+#define PINN_ADAPTIVE_SCRATCH_FLOATS 1296
+int pinn_adaptive_adam_step(float* params, const float* comp_grads, int64_t ld, int32_t n_components,
+                            const float* const* comp_losses, const float* loss_scales, int32_t strategy, double alpha,
+                            double aw_eps, const float* initial_weights, float* state16, float* weights4_out, float* summary4,
+                            float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr, float beta1, float beta2, float eps,
+                            float weight_decay, float max_norm, float* step, float* scratch, float* grad_norm_out,
+                            float* grad_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,13 +26,15 @@ PDE = {
     "black_scholes": 7, "pendulum": 8, "heat_laplacian": 9,
 }
 LOSS = {"mse": 0, "mae": 1, "huber": 2}
+ADAPTIVE = {"rbw": 0, "lrw": 1}
+PINN_ADAPTIVE_SCRATCH_FLOATS = 1296
 
 EXPORTS = (
     "pinn_abi_version", "pinn_last_error", "pinn_build_info", "pinn_num_tensors", "pinn_pde_streams",
     "pinn_workspace_bytes", "pinn_jet_forward", "pinn_jet_backward", "pinn_residual_forward", "pinn_residual_backward",
     "pinn_residual_loss_grad", "pinn_residual_loss_grad_coef", "pinn_point_losses", "pinn_jet_losses", "pinn_adam_clip_step",
     "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name", "pinn_residual_loss_grad_inverse",
-    "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name",
+    "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step",
 )
 
 
@@ -150,6 +152,10 @@ def load():
                                         i32, vp, vp]
         lib.pinn_adam_clip_step.restype = ctypes.c_int
         lib.pinn_adam_clip_step.argtypes = [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp]
+        f64 = ctypes.c_double
+        lib.pinn_adaptive_adam_step.restype = ctypes.c_int
+        lib.pinn_adaptive_adam_step.argtypes = [vp, vp, i64, i32, P(vp), P(f32), i32, f64, f64, P(f32), vp, vp, vp, vp, vp, i64, vp,
+                                                f32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:
             raise JetLibraryError(f"libpinnjet.so ABI {lib.pinn_abi_version()} != expected {PINN_ABI_VERSION}: rebuild")
         _lib = lib

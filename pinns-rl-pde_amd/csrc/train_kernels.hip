@@ -1,10 +1,12 @@
 // Small kernels of the captured training step (include/pinn_jet.h, "training step" section): the point-wise loss
 // terms of PDEBase.compute_loss on the boundary / initial points, and gradient clipping + Adam over ONE flat
 // parameter buffer.  Everything else of a step is the jet engine's residual launch; with these two the whole step is
-// free of autograd and runs as a handful of launches inside a HIP graph.
+// free of autograd and runs as a handful of launches inside a HIP graph.  With adaptive loss weights (RBW / LRW) the last
+// part is pinn_adaptive_adam_step instead: weight update + weighted combination of the component gradients + clip + Adam.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 
 #include "../../include/pinn_jet.h"
@@ -185,6 +187,237 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
 
 __global__ void step_inc_kernel(float* step) { step[0] += 1.0f; }
 
+// ---- adaptive loss weights (pinnrl/components/adaptive_weights.py:35-107, pinnrl/training/trainer.py:586-684) ----------------
+// The weights are detached numbers, so grad(total) = sum_c w_c grad(L_c): from the C component gradients one Gram pass gives
+// every norm the step needs (LRW's per-component norms on its diagonal, the clip norm of the combined gradient as the
+// quadratic form w^T G w), one workgroup runs the EMA rule, and the update pass combines, clips and applies Adam without the
+// combined gradient ever going through memory.
+constexpr int kMaxComp = 4, kMaxPairs = kMaxComp * (kMaxComp + 1) / 2;
+// res[] (after the Gram partials in the scratch): what the update pass reads — written by the one-workgroup launch only
+enum { kResW = 0, kResCoef = 4, kResStepSize = 5, kResRs2 = 6, kResFloats = 8 };
+
+struct CompLosses {
+  const float* ptr[kMaxComp];
+  float scale[kMaxComp];
+  float init[kMaxComp];
+};
+
+// partial[pair * kNormBlocks + block] = this block's share of <g_a, g_b>, pairs in the order (0,0) (0,1) .. (1,1) ..;
+// products of two floats are exact in double, and every sum runs in a fixed order: deterministic.
+// vec: rows are 16-byte aligned (base and ld): float4 loads over n / 4 vectors, the last n % 4 elements by block 0.
+template <int C>
+__global__ __launch_bounds__(256) void gram_kernel(const float* g, long long ld, long long n, int vec, double* partial) {
+  constexpr int NP = C * (C + 1) / 2;
+  __shared__ double red[256];
+  double acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) acc[p] = 0.0;
+  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)kNormBlocks * 256;
+  auto add = [&](const float* e) {
+    int p = 0;
+#pragma unroll
+    for (int a = 0; a < C; ++a)
+#pragma unroll
+      for (int b = a; b < C; ++b, ++p) acc[p] = fma((double)e[a], (double)e[b], acc[p]);
+  };
+  if (vec) {
+    const long long nv = n >> 2;
+    for (long long i = first; i < nv; i += stride) {
+      float4 q[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) q[c] = reinterpret_cast<const float4*>(g + c * ld)[i];
+      float e[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) e[c] = q[c].x;
+      add(e);
+#pragma unroll
+      for (int c = 0; c < C; ++c) e[c] = q[c].y;
+      add(e);
+#pragma unroll
+      for (int c = 0; c < C; ++c) e[c] = q[c].z;
+      add(e);
+#pragma unroll
+      for (int c = 0; c < C; ++c) e[c] = q[c].w;
+      add(e);
+    }
+    const long long i = (nv << 2) + threadIdx.x;  // scalar tail
+    if (blockIdx.x == 0 && threadIdx.x < 4 && i < n) {
+      float e[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) e[c] = g[c * ld + i];
+      add(e);
+    }
+  } else {
+    for (long long i = first; i < n; i += stride) {
+      float e[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) e[c] = g[c * ld + i];
+      add(e);
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    red[threadIdx.x] = acc[p];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[p * kNormBlocks + blockIdx.x] = red[0];
+    __syncthreads();
+  }
+}
+
+// One workgroup: the only launch that writes the weight state.  state16 = {running[4], prev_weights[4], weights[4], calls,
+// has_prev, -, -}.  Also the scalars of the Adam update (as adam_kernel forms them) and the step counter's increment: the
+// update pass reads res[] and never `step`, so no block of it depends on what another block writes.
+__global__ __launch_bounds__(64) void adaptive_update_kernel(const double* partial, CompLosses cl, int C, int strategy, double alpha,
+                                                             double aw_eps, int has_init, float* state, float* weights_out,
+                                                             float* summary4, float max_norm, const float* lr, float beta1,
+                                                             float beta2, float* step, float* res, float* norm_out) {
+  __shared__ double G[kMaxPairs];
+  const int NP = C * (C + 1) / 2;
+  if ((int)threadIdx.x < NP) {
+    double tot = 0.0;
+    for (int b = 0; b < kNormBlocks; ++b) tot += partial[threadIdx.x * kNormBlocks + b];
+    G[threadIdx.x] = tot;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double L[kMaxComp], v[kMaxComp], run[kMaxComp], w[kMaxComp];
+  int diag = 0;
+  for (int c = 0; c < C; ++c) {
+    L[c] = (double)(cl.ptr[c][0] * cl.scale[c]);
+    v[c] = strategy == 1 ? sqrt(G[diag]) : L[c];
+    diag += C - c;
+  }
+  const bool first = state[12] == 0.0f;
+  bool has_prev = state[13] != 0.0f;
+  if (first) {
+    for (int c = 0; c < C; ++c) {
+      run[c] = v[c];
+      w[c] = has_init ? (double)cl.init[c] : 1.0;
+    }
+  } else {
+    double sum = 0.0;
+    for (int c = 0; c < C; ++c) {
+      run[c] = alpha * (double)state[c] + (1.0 - alpha) * v[c];
+      sum += strategy == 1 ? 1.0 / (run[c] + aw_eps) : run[c];
+    }
+    for (int c = 0; c < C; ++c) {
+      if (strategy == 1) {
+        w[c] = (1.0 / (run[c] + aw_eps)) / sum;
+      } else {
+        w[c] = run[c] / (sum + aw_eps);
+        if (has_prev) w[c] = alpha * (double)state[4 + c] + (1.0 - alpha) * w[c];
+      }
+    }
+    if (strategy != 1) has_prev = true;
+  }
+  float wf[kMaxComp];
+  double total = 0.0;
+  for (int c = 0; c < kMaxComp; ++c) {
+    wf[c] = c < C ? (float)w[c] : 0.0f;
+    state[c] = c < C ? (float)run[c] : 0.0f;
+    if (!first && strategy != 1) state[4 + c] = wf[c];
+    state[8 + c] = wf[c];
+    res[kResW + c] = wf[c];
+    if (weights_out) weights_out[c] = wf[c];
+    if (c < C) total += (double)wf[c] * L[c];
+  }
+  state[12] += 1.0f;
+  state[13] = has_prev ? 1.0f : 0.0f;
+  if (summary4) {
+    for (int c = 0; c < 3; ++c) summary4[c] = c < C ? (float)L[c] : 0.0f;
+    summary4[3] = (float)total;
+  }
+  // the norm clip_grad_norm_ would take of sum_c w_c g_c, as the quadratic form of the Gram matrix, in double: where two
+  // component gradients nearly cancel the terms are orders of magnitude above their sum
+  double q = 0.0;
+  int p = 0;
+  for (int a = 0; a < C; ++a)
+    for (int b = a; b < C; ++b, ++p) q += (a == b ? 1.0 : 2.0) * (double)wf[a] * (double)wf[b] * G[p];
+  const float norm = (float)sqrt(q > 0.0 ? q : 0.0);
+  float coef = 1.0f;
+  if (max_norm > 0.0f) {
+    coef = max_norm / (norm + 1e-6f);
+    coef = coef < 1.0f ? coef : 1.0f;
+  }
+  const float t = step[0] + 1.0f;
+  const float bc1 = 1.0f - powf(beta1, t), bc2 = 1.0f - powf(beta2, t);
+  res[kResCoef] = coef;
+  res[kResStepSize] = lr[0] / bc1;
+  res[kResRs2] = rsqrtf(bc2);
+  step[0] = t;
+  if (norm_out) norm_out[0] = norm;
+}
+
+struct AdamScalars {
+  float w[kMaxComp], coef, step_size, rs2, beta1, beta2, eps, wd;
+};
+
+// g = sum_c w_c g_c in a fixed order, then the arithmetic of adam_kernel on one element
+template <int C>
+__device__ __forceinline__ void adaptive_adam_elem(const AdamScalars& s, const float* gc, float& p, float& m, float& v, float& g) {
+  g = s.w[0] * gc[0];
+#pragma unroll
+  for (int c = 1; c < C; ++c) g = fmaf(s.w[c], gc[c], g);
+  float gi = g * s.coef;
+  const float pi = p;
+  if (s.wd != 0.0f) gi = fmaf(s.wd, pi, gi);
+  const float mi = fmaf(1.0f - s.beta1, gi - m, m);
+  const float vi = fmaf(s.beta2, v, (1.0f - s.beta2) * gi * gi);
+  m = mi;
+  v = vi;
+  const float denom = sqrtf(vi) * s.rs2 + s.eps;
+  p = pi - s.step_size * (mi / denom);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void adaptive_adam_kernel(float* p, const float* g, long long ld, float* m, float* v, long long n,
+                                                            int vec, const float* res, float beta1, float beta2, float eps, float wd,
+                                                            float* grad_out) {
+  AdamScalars s;
+#pragma unroll
+  for (int c = 0; c < kMaxComp; ++c) s.w[c] = res[kResW + c];
+  s.coef = res[kResCoef];
+  s.step_size = res[kResStepSize];
+  s.rs2 = res[kResRs2];
+  s.beta1 = beta1, s.beta2 = beta2, s.eps = eps, s.wd = wd;
+  const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+  const long long nv = vec ? n >> 2 : 0;
+  for (long long i = first; i < nv; i += stride) {
+    float4 q[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) q[c] = reinterpret_cast<const float4*>(g + c * ld)[i];
+    float4 pp = reinterpret_cast<float4*>(p)[i], mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i], gg;
+    float e[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) e[c] = q[c].x;
+    adaptive_adam_elem<C>(s, e, pp.x, mm.x, vv.x, gg.x);
+#pragma unroll
+    for (int c = 0; c < C; ++c) e[c] = q[c].y;
+    adaptive_adam_elem<C>(s, e, pp.y, mm.y, vv.y, gg.y);
+#pragma unroll
+    for (int c = 0; c < C; ++c) e[c] = q[c].z;
+    adaptive_adam_elem<C>(s, e, pp.z, mm.z, vv.z, gg.z);
+#pragma unroll
+    for (int c = 0; c < C; ++c) e[c] = q[c].w;
+    adaptive_adam_elem<C>(s, e, pp.w, mm.w, vv.w, gg.w);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    if (grad_out) reinterpret_cast<float4*>(grad_out)[i] = gg;
+  }
+  for (long long i = (nv << 2) + first; i < n; i += stride) {  // the scalar tail (everything when the rows are not aligned)
+    float e[C], gi;
+#pragma unroll
+    for (int c = 0; c < C; ++c) e[c] = g[c * ld + i];
+    adaptive_adam_elem<C>(s, e, p[i], m[i], v[i], gi);
+    if (grad_out) grad_out[i] = gi;
+  }
+}
+
 }  // namespace
 
 extern "C" int pinn_internal_fail(int code, const char* msg);  // pinn_abi.hip: sets pinn_last_error()
@@ -195,6 +428,17 @@ static int launched(const char* what) {
   char msg[256];
   snprintf(msg, sizeof(msg), "HIP error %d: %s (%s)", (int)e, hipGetErrorString(e), what);
   return pinn_internal_fail(PINN_ERR_HIP, msg);
+}
+
+template <int C>
+static void launch_adaptive(hipStream_t st, int blocks, float* params, const float* comp_grads, long long ld, float* exp_avg,
+                            float* exp_avg_sq, long long n, int vec, int vec_all, double* partial, const float* res, float beta1,
+                            float beta2, float eps, float wd, float* grad_out, int phase) {
+  if (phase == 0)
+    hipLaunchKernelGGL(gram_kernel<C>, dim3(kNormBlocks), dim3(256), 0, st, comp_grads, ld, n, vec, partial);
+  else
+    hipLaunchKernelGGL(adaptive_adam_kernel<C>, dim3(blocks), dim3(256), 0, st, params, comp_grads, ld, exp_avg, exp_avg_sq, n, vec_all,
+                       res, beta1, beta2, eps, wd, grad_out);
 }
 
 extern "C" {
@@ -270,6 +514,58 @@ int pinn_adam_clip_step(float* params, const float* grads, float* exp_avg, float
   if ((rc = launched("adam_kernel"))) return rc;
   hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, step);
   return launched("step_inc_kernel");
+}
+
+int pinn_adaptive_adam_step(float* params, const float* comp_grads, int64_t ld, int32_t n_components,
+                            const float* const* comp_losses, const float* loss_scales, int32_t strategy, double alpha,
+                            double aw_eps, const float* initial_weights, float* state16, float* weights4_out, float* summary4,
+                            float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr, float beta1, float beta2, float eps,
+                            float weight_decay, float max_norm, float* step, float* scratch, float* grad_norm_out,
+                            float* grad_out, void* stream) {
+  if (!params || !comp_grads || !comp_losses || !state16 || !exp_avg || !exp_avg_sq || !lr || !step || !scratch || n <= 0)
+    return pinn_internal_fail(PINN_ERR_BAD_DESC, "pinn_adaptive_adam_step: null argument or n <= 0");
+  if (n_components < 1 || n_components > kMaxComp || ld < n || (strategy != PINN_ADAPTIVE_RBW && strategy != PINN_ADAPTIVE_LRW))
+    return pinn_internal_fail(PINN_ERR_BAD_DESC, "pinn_adaptive_adam_step: component count, row stride or strategy out of range");
+  if (reinterpret_cast<uintptr_t>(scratch) & 7u)
+    return pinn_internal_fail(PINN_ERR_MISALIGNED, "pinn_adaptive_adam_step: scratch must be 8-byte aligned");
+  static_assert(PINN_ADAPTIVE_SCRATCH_FLOATS >= 2 * kMaxPairs * kNormBlocks + kResFloats, "scratch size");
+  CompLosses cl;
+  for (int c = 0; c < kMaxComp; ++c) {
+    if (c < n_components && !comp_losses[c]) return pinn_internal_fail(PINN_ERR_BAD_DESC, "pinn_adaptive_adam_step: null component loss");
+    cl.ptr[c] = c < n_components ? comp_losses[c] : nullptr;
+    cl.scale[c] = (c < n_components && loss_scales) ? loss_scales[c] : 1.0f;
+    cl.init[c] = (c < n_components && initial_weights) ? initial_weights[c] : 1.0f;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* partial = reinterpret_cast<double*>(scratch);
+  float* res = scratch + 2 * kMaxPairs * kNormBlocks;
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  const int vec = al(comp_grads) && ld % 4 == 0;  // the rows of the component gradients can be read 16 bytes at a time
+  const int vec_all = vec && al(params) && al(exp_avg) && al(exp_avg_sq) && (!grad_out || al(grad_out));
+  int blocks = (int)(((vec_all ? (n + 3) / 4 : n) + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  auto phase = [&](int ph) {
+#define PINN_ADAPTIVE_CASE(C)                                                                                              \
+  case C:                                                                                                                  \
+    launch_adaptive<C>(st, blocks, params, comp_grads, ld, exp_avg, exp_avg_sq, n, vec, vec_all, partial, res, beta1, beta2, \
+                       eps, weight_decay, grad_out, ph);                                                                   \
+    break;
+    switch (n_components) {
+      PINN_ADAPTIVE_CASE(1)
+      PINN_ADAPTIVE_CASE(2)
+      PINN_ADAPTIVE_CASE(3)
+      PINN_ADAPTIVE_CASE(4)
+    }
+#undef PINN_ADAPTIVE_CASE
+  };
+  phase(0);
+  int rc = launched("gram_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(adaptive_update_kernel, dim3(1), dim3(64), 0, st, partial, cl, n_components, strategy, alpha, aw_eps,
+                     initial_weights ? 1 : 0, state16, weights4_out, summary4, max_norm, lr, beta1, beta2, step, res, grad_norm_out);
+  if ((rc = launched("adaptive_update_kernel"))) return rc;
+  phase(1);
+  return launched("adaptive_adam_kernel");
 }
 
 }  // extern "C"

@@ -438,6 +438,50 @@ def adam_clip_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: T
                                            _stream(dev)))
 
 
+def adaptive_adam_step(params: Tensor, comp_grads: Tensor, comp_losses, exp_avg: Tensor, exp_avg_sq: Tensor, lr: Tensor,
+                       step: Tensor, scratch: Tensor, state: Tensor, strategy: str = "rbw", alpha: float = 0.9,
+                       aw_eps: float = 1e-5, initial_weights: Optional[Sequence[float]] = None,
+                       loss_scales: Optional[Sequence[float]] = None, weights_out: Optional[Tensor] = None,
+                       summary4: Optional[Tensor] = None, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                       weight_decay: float = 0.0, max_norm: float = 0.0, grad_norm_out: Optional[Tensor] = None,
+                       grad_out: Optional[Tensor] = None) -> None:
+    """Adaptive loss weights (RBW / LRW) + clip_grad_norm_ + Adam on flat fp32 buffers (`pinn_adaptive_adam_step`).
+    comp_grads: (C, ld) with ld >= n, row c the gradient of the unweighted loss component c; comp_losses: a tensor of C
+    floats, or a sequence of C one-element tensors (L_c = comp_losses[c] * loss_scales[c]); state: 16 floats, zero before
+    the first step.  Writes weights_out (4), summary4 {L_0, L_1, L_2, sum w_c L_c}, grad_norm_out (1) and grad_out (n: the
+    combined gradient before clipping) where given.  Three launches, no atomics, nothing read on the host."""
+    lib = _lib.load()
+    losses = [comp_losses[c : c + 1] for c in range(comp_losses.numel())] if isinstance(comp_losses, Tensor) else list(comp_losses)
+    dev = _require_device(params, comp_grads, exp_avg, exp_avg_sq, lr, step, scratch, state, weights_out, summary4,
+                          grad_norm_out, grad_out, *losses)
+    n, C = params.numel(), len(losses)
+    if strategy not in _lib.ADAPTIVE:
+        raise ValueError(f"adaptive weight strategy '{strategy}' (rbw | lrw)")
+    if comp_grads.dim() != 2 or comp_grads.shape[0] != C or comp_grads.stride(1) != 1 or comp_grads.shape[1] < n or not 1 <= C <= 4:
+        raise ValueError("comp_grads: (C <= 4, ld >= n) with unit stride along a row, one row per component loss")
+    for tns in (params, exp_avg, exp_avg_sq, comp_grads, *losses):
+        if tns.dtype != torch.float32:
+            raise ValueError("adaptive_adam_step: float32 buffers only")
+    assert params.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()
+    assert exp_avg.numel() == n and exp_avg_sq.numel() == n and state.numel() >= 16
+    assert scratch.numel() >= _lib.PINN_ADAPTIVE_SCRATCH_FLOATS and scratch.is_contiguous()
+    assert weights_out is None or weights_out.numel() >= 4
+    assert summary4 is None or summary4.numel() >= 4
+    assert grad_out is None or (grad_out.numel() >= n and grad_out.is_contiguous())
+    if initial_weights is not None and len(initial_weights) != C:
+        raise ValueError(f"initial_weights: {C} entries, one per component")
+    lp = (ctypes.c_void_p * C)(*[t.data_ptr() for t in losses])
+    ls = (ctypes.c_float * C)(*[float(v) for v in loss_scales]) if loss_scales is not None else None
+    iw = (ctypes.c_float * C)(*[float(v) for v in initial_weights]) if initial_weights is not None else None
+    opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_adaptive_adam_step(params.data_ptr(), comp_grads.data_ptr(), comp_grads.stride(0), C, lp, ls,
+                                               _lib.ADAPTIVE[strategy], float(alpha), float(aw_eps), iw, state.data_ptr(),
+                                               opt(weights_out), opt(summary4), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
+                                               lr.data_ptr(), beta1, beta2, eps, weight_decay, max_norm, step.data_ptr(),
+                                               scratch.data_ptr(), opt(grad_norm_out), opt(grad_out), _stream(dev)))
+
+
 # ---------------------------------------------------------------------------------------------
 # autograd splices
 # ---------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@ import torch.optim as optim
 
 from .. import distributed as _D
 from .. import engine as _E
+from .._lib import PINN_ADAPTIVE_SCRATCH_FLOATS
 
 
 class _EmaLossWeights:
@@ -97,6 +98,7 @@ class PDETrainer:
         self.adaptive_weights = (
             _EmaLossWeights(aw.strategy, aw.alpha, aw.eps, aw.initial_weights) if self.use_adaptive_weights else None
         )
+        self._pending_weights: List[torch.Tensor] = []  # device copies of the launch-list steps' weights, see `_flush_loss_weights`
         self.points_history: List[np.ndarray] = []
 
     # ---------------------------------------------------------------- optimizer / scheduler (trainer.py:281-371)
@@ -320,7 +322,10 @@ class PDETrainer:
             return self._lbfgs_step(x, t)
         if getattr(self, "_flat", None) is not None:  # parameters live in the flat buffers: same sequence, not captured
             self._manual_launches(x, t)
-            return self._manual_losses()
+            losses = self._manual_losses()
+            if "weights" in losses:  # one `history["loss_weights"]` row per step, as `_adaptive_total` appends them
+                self._pending_weights.append(losses["weights"])
+            return losses
         if self.process_group is not None:
             self._ensure_dp_buffer()
             self._dp_buf.zero_()  # the .grad views stay attached (zero_grad(set_to_none=True) would drop them)
@@ -345,8 +350,6 @@ class PDETrainer:
         tc = self.config.training
         if self._is_lbfgs or getattr(tc, "optimizer", "adam") != "adam":
             return "optimizer is not Adam"
-        if self.use_adaptive_weights:
-            return "adaptive loss weights"
         if self.rl_agent is not None and not hasattr(self.rl_agent, "action_probabilities"):
             return "RL agent without a device-side action selection"
         if getattr(tc, "collocation_distribution", "uniform") not in ("uniform", "stratified", "residual_based"):
@@ -377,6 +380,29 @@ class PDETrainer:
         ic = getattr(self.pde.config, "initial_condition", None) or {}
         if ic.get("type") == "random":
             return "random initial condition"
+        if self.use_adaptive_weights:
+            return self._adaptive_step_unsupported(mode, inverse)
+        return None
+
+    def _adaptive_step_unsupported(self, mode: str, inverse: bool) -> Optional[str]:
+        """What keeps adaptive loss weights (RBW / LRW) on the eager step: the launch list reweights exactly the three
+        components residual / boundary / initial of a forward problem."""
+        tc = self.config.training
+        aw = tc.adaptive_weights
+        if aw.strategy not in ("rbw", "lrw"):  # as `_adaptive_total` spells them; any other spelling keeps its eager behaviour
+            return f"adaptive loss weights with strategy '{aw.strategy}'"
+        if mode != "forward" or getattr(tc, "mode", "forward") != "forward":
+            return "adaptive loss weights outside forward mode (the data term is added unweighted after the reweighting)"
+        if inverse:
+            return "adaptive loss weights with trainable PDE coefficients"
+        if getattr(self.pde, "observation_data", None):
+            return "adaptive loss weights with an observation-data term"
+        if (getattr(tc, "loss_weights", None) or {}).get("smoothness", 0.0) > 0:
+            return "adaptive loss weights with a smoothness component"
+        if aw.initial_weights is not None and len(aw.initial_weights) != 3:
+            return f"adaptive loss weights with {len(aw.initial_weights)} initial weights (the step has three components)"
+        if self.process_group is not None:
+            return "adaptive loss weights under a process group"
         return None
 
     def _coefficient_slots(self):
@@ -463,6 +489,22 @@ class PDETrainer:
                                                 self.pde._huber_delta())})
         F = self._flat
         F["extra"] = torch.zeros(2, dtype=torch.float32, device=dev)  # {initial, data} when the chain carries a data term
+        if self.use_adaptive_weights:
+            # adaptive loss weights: one gradient row per component [residual, boundary, initial] and the EMA state of
+            # pinn_adaptive_adam_step {running[4], prev_weights[4], weights[4], calls, has_prev}; the state of eager steps
+            # taken so far (`_EmaLossWeights`) comes along
+            aw = self.adaptive_weights
+            state = torch.zeros(16, dtype=torch.float32)
+            if aw.running is not None:
+                state[0:3] = aw.running.detach().float().cpu()[:3]
+                state[8:11] = aw.weights.detach().float().cpu()[:3]
+                state[12] = 1.0
+                if aw.prev_weights is not None:
+                    state[4:7] = aw.prev_weights.detach().float().cpu()[:3]
+                    state[13] = 1.0
+            F.update({"comp_grads": torch.zeros(3, n, dtype=torch.float32, device=dev), "aw_state": state.to(dev),
+                      "weights": state[8:12].clone().to(dev),
+                      "aw_scratch": torch.zeros(PINN_ADAPTIVE_SCRATCH_FLOATS, dtype=torch.float32, device=dev)})
         return self._flat
 
     def _chain(self, n_batch: int, world: int = 1):
@@ -495,6 +537,15 @@ class PDETrainer:
             ch["term_losses"] = torch.zeros(len(ch["terms"]), dtype=torch.float32, device=dev)
             ch["cot"] = torch.zeros(K, npts, dtype=torch.float32, device=dev)
             ch["terms_dp"] = [(lo, hi, st, pr, tg, w / world) for lo, hi, st, pr, tg, w in ch["terms"]]
+            if self.use_adaptive_weights:
+                # the boundary and the initial component separately, unweighted (the weights are the adaptive ones):
+                # pinn_jet_losses overwrites its cotangents, so each half has its own buffers
+                unit = [(lo, hi, st, pr, tg, 1.0) for lo, hi, st, pr, tg, w in ch["terms"]]
+                for half, terms in (("b", unit[: ch["n_bc"]]), ("i", unit[ch["n_bc"]:])):
+                    ch["terms_" + half] = terms
+                    ch["term_losses_" + half] = torch.zeros(len(terms), dtype=torch.float32, device=dev)
+                    ch["cot_" + half] = torch.zeros(K, npts, dtype=torch.float32, device=dev)
+                    ch["summary_" + half] = torch.zeros(4, dtype=torch.float32, device=dev)
             F["chains"][key] = ch
         return ch
 
@@ -517,6 +568,8 @@ class PDETrainer:
             return self._manual_launches_dp(x, t, F, prog, pd, n, N, loss_name, delta)
 
         ch = self._chain(N)
+        if self.use_adaptive_weights:
+            return self._manual_launches_adaptive(x, t, F, prog, pd, ch, side)
 
         def residual_launch():
             if "coef" in F:  # trainable coefficients: read from the device buffer, cotangents into their gradient slots
@@ -569,6 +622,51 @@ class PDETrainer:
                               F["coef_step"], F["coef_scratch"], beta1=F["betas"][0], beta2=F["betas"][1], eps=F["eps"],
                               weight_decay=F["wd"], max_norm=0.0)
 
+    def _manual_launches_adaptive(self, x, t, F, prog, pd, ch, side=None):
+        """The launch list with adaptive loss weights (RBW / LRW, trainer.py:586-684).  The weights are detached numbers, so
+        grad(total) = sum_c w_c grad(L_c): the residual launch (scale 1/N) writes row 0 of the component gradients, the
+        boundary and the initial half of the chain rows 1 and 2 (one forward, two loss-term launches with unit weights, two
+        ten-tile reverse sweeps), and `pinn_adaptive_adam_step` does the rest on the device — Gram matrix of the rows (LRW's
+        norms, the clip norm), the EMA rule, combine + clip + Adam.  The same path serves both strategies; nothing is read
+        on the host, so the step is capturable.  Like the eager `_adaptive_total`, and unlike the reference's LRW branch
+        (which leaves the last component's gradient in `.grad` when `loss.backward()` runs), the update uses grad(total) alone."""
+        n, N = F["n"], x.shape[0]
+        loss_name, delta = self.pde._loss_function_name(), self.pde._huber_delta()
+        G = F["comp_grads"]
+
+        def chain():
+            u = _E.jets_forward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"])
+            _E.jet_losses(u, ch["terms_b"], loss_name, delta, ch["term_losses_b"], ch["cot_b"],
+                          n_boundary_terms=len(ch["terms_b"]), summary4=ch["summary_b"])  # summary_b[1] = boundary loss
+            _E.jet_losses(u, ch["terms_i"], loss_name, delta, ch["term_losses_i"], ch["cot_i"],
+                          n_boundary_terms=0, summary4=ch["summary_i"])  # summary_i[2] = initial loss
+            _E.jets_backward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"], ch["cot_b"], G[1])
+            _E.jets_backward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"], ch["cot_i"], G[2])
+            return u
+
+        G.zero_()
+        F["grad"][n:].zero_()  # the residual launch's loss sum stays where the fixed-weight step keeps it
+        if side is None:
+            _E.residual_loss_grad(prog, pd, x, t, 1.0 / float(N), G[0], loss_sum=F["grad"][n : n + 1])
+            chain()
+        else:  # the chain beside the residual launch, as in the fixed-weight step: the rows are disjoint buffers
+            main = torch.cuda.current_stream(self.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                u = chain()
+            _E.residual_loss_grad(prog, pd, x, t, 1.0 / float(N), G[0], loss_sum=F["grad"][n : n + 1])
+            main.wait_stream(side)
+            if not torch.cuda.is_current_stream_capturing():
+                u.record_stream(main)
+        F["has_data"] = False
+        aw = self.config.training.adaptive_weights
+        _E.adaptive_adam_step(F["theta"], G, [F["grad"][n : n + 1], ch["summary_b"][1:2], ch["summary_i"][2:3]], F["m"], F["v"],
+                              F["lr"], F["step"], F["aw_scratch"], F["aw_state"], strategy=aw.strategy,
+                              alpha=float(aw.alpha), aw_eps=float(aw.eps), initial_weights=aw.initial_weights,
+                              loss_scales=[1.0 / float(N), 1.0, 1.0], weights_out=F["weights"], summary4=F["summary"],
+                              beta1=F["betas"][0], beta2=F["betas"][1], eps=F["eps"], weight_decay=F["wd"],
+                              max_norm=float(self.config.training.gradient_clipping))
+
     def _manual_launches_dp(self, x, t, F, prog, pd, n, N, loss_name, delta):
         """The same launch list under a process group (one process per GPU): this rank's contiguous shard of the
         identically-sampled batch goes through the residual launch with the GLOBAL 1/N, the replicated boundary /
@@ -592,7 +690,8 @@ class PDETrainer:
                           max_norm=float(self.config.training.gradient_clipping))
 
     def _manual_losses(self, static: bool = False):
-        """{residual, boundary, initial, total} of the last manual step.  `static=True` hands out views of the persistent
+        """{residual, boundary, initial, total} of the last manual step — with adaptive loss weights also "weights", the
+        step's four weights (padded with 0), and total = sum_c w_c L_c.  `static=True` hands out views of the persistent
         summary buffer (what a captured graph refreshes in place); otherwise independent copies, so that a caller may
         keep one per step (`train()` averages them per epoch)."""
         s = self._flat["summary"]
@@ -604,9 +703,19 @@ class PDETrainer:
             out["initial"], out["data"] = e[0], e[1]
         elif self.pde._training_mode() in ("inverse", "data_augmented"):
             out["data"] = torch.zeros((), dtype=torch.float32, device=s.device)
+        if "weights" in self._flat:
+            out["weights"] = self._flat["weights"] if static else self._flat["weights"].clone()
         return out
 
+    def _flush_loss_weights(self):
+        """`history["loss_weights"]` rows of the launch-list steps taken since the last flush: `train_step` keeps device
+        copies (no host sync per step), this converts them where the host waits for the device anyway."""
+        if self._pending_weights:
+            self.history["loss_weights"].extend(torch.stack(self._pending_weights).double().cpu().numpy())
+            self._pending_weights.clear()
+
     def get_training_history(self):  # trainer.py:966-972
+        self._flush_loss_weights()
         return self.history
 
     def make_graphed_step(self, batch_size: int, warmup: int = 2):
@@ -618,8 +727,10 @@ class PDETrainer:
         moments; the parameters of the model become views of the flat buffer).  Nothing in it depends on autograd
         nodes of earlier eager steps, so it is safe to call after any number of `train_step`s (round 1's capture of
         `loss.backward()` crashed on a stale AccumulateGrad node).  The learning rate lives in a device scalar that
-        `train` refreshes after each scheduler step.  Steps the fixed sequence does not cover (L-BFGS, adaptive
-        weights, RL / residual-based sampling, data-parallel, PDEs with their own compute_loss) raise."""
+        `train` refreshes after each scheduler step.  Adaptive loss weights (RBW / LRW) of a forward problem are part of
+        the captured step (`_manual_launches_adaptive`: the EMA state lives on the device; `losses["weights"]` is the
+        static 4-vector of the last replay).  Steps the fixed sequence does not cover (`_manual_step_unsupported()`:
+        L-BFGS, adaptive weights in inverse / data modes, >= 2-D problems, data-parallel training) raise."""
         why = self._manual_step_unsupported()
         if why is None and self.process_group is not None:
             why = "data-parallel training (a collective inside the capture)"
@@ -676,6 +787,7 @@ class PDETrainer:
                 if self.log_every_step:
                     self.points_history.append(torch.cat([x, t], dim=1).cpu().numpy())
             avg = float(torch.stack(step_losses).mean().item())  # ZeroDivisionError upstream when there are no steps
+            self._flush_loss_weights()
             self._update_scheduler(avg)
             lr = self.optimizer.param_groups[0]["lr"]
             self.set_learning_rate(lr)

@@ -1,6 +1,7 @@
 """Full training step (SURVEY §8(d) "secondary: full-step pts/s", §8(f) rank 1) on ONE GPU, for context.
 
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
+                               [--adaptive {none,rbw,lrw}] [--repeats 1]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -9,6 +10,10 @@ residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam,
     autograd  `PDETrainer.train_step` with torch autograd around the fused launches (the reference's call sequence)
     manual    the autograd-free launch list (`_manual_launches`: what `PDETrainer.train()` takes by itself)
     graph     the same list captured once in a HIP graph (`make_graphed_step`) and replayed
+
+`--adaptive rbw|lrw` turns on adaptive loss weights (`training.adaptive_weights`, default settings of the configuration):
+the autograd mode then runs `_adaptive_total` (LRW: one backward pass per loss component), the other two the adaptive launch
+list (`pinn_adaptive_adam_step`).  `--repeats R` times the window R times and prints the median with the range.
 """
 import argparse
 import os
@@ -21,12 +26,12 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: E402
 
 import bench_configs as B  # noqa: E402
-from pinnrl_amd.config import Config, TrainingConfig  # noqa: E402
+from pinnrl_amd.config import AdaptiveWeightsConfig, Config, TrainingConfig  # noqa: E402
 from pinnrl_amd.rl import RLAgent  # noqa: E402
 from pinnrl_amd.training import PDETrainer  # noqa: E402
 
 
-def build(tag):
+def build(tag, adaptive="none"):
     name, net, eq, n_req = B.CONFIGS[tag]()
     agent = None
     if tag == "C3":  # BASELINE C3: DQN adaptive sampling
@@ -35,6 +40,8 @@ def build(tag):
     cfg = Config.__new__(Config)
     cfg.device = B.dev
     cfg.training = TrainingConfig()
+    if adaptive != "none":
+        cfg.training.adaptive_weights = AdaptiveWeightsConfig(enabled=True, strategy=adaptive)
     return name, net, eq, agent, cfg, n_req
 
 
@@ -43,13 +50,15 @@ def main():
     ap.add_argument("--configs", default="C1,C2,C3,C4")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--modes", default="autograd,manual,graph")
+    ap.add_argument("--adaptive", choices=["none", "rbw", "lrw"], default="none")
+    ap.add_argument("--repeats", type=int, default=1)
     args = ap.parse_args()
     print("| config | points | sampler | mode | ms/step | points/s | last total loss |")
     print("|---|---|---|---|---|---|---|")
     for tag in [c for c in args.configs.split(",") if c]:
         for mode in args.modes.split(","):
             torch.manual_seed(0)
-            name, net, eq, agent, cfg, n_req = build(tag)
+            name, net, eq, agent, cfg, n_req = build(tag, args.adaptive)
             tr = PDETrainer(net, eq, None, cfg, device=B.dev, rl_agent=agent, fast_step=False)
             if mode != "autograd":
                 why = tr._manual_step_unsupported()
@@ -67,15 +76,21 @@ def main():
             n = int(tr._sample(n_req)[0].shape[0])
             for _ in range(3):
                 out = run()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                out = run()
-            torch.cuda.synchronize()
-            ms = 1e3 * (time.perf_counter() - t0) / args.steps
+            times = []
+            for _ in range(max(args.repeats, 1)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    out = run()
+                torch.cuda.synchronize()
+                times.append(1e3 * (time.perf_counter() - t0) / args.steps)
+            ms = sorted(times)[len(times) // 2]
+            spread = f" ({min(times):.3f}-{max(times):.3f})" if len(times) > 1 else ""
             last = losses if mode == "graph" else out
             sampler = "adaptive (DQN)" if agent is not None else cfg.training.collocation_distribution
-            print(f"| {tag} {name} | {n} | {sampler} | {mode} | {ms:.3f} | {n / ms * 1e3:.3e} | {float(last['total'].detach()):.4e} |", flush=True)
+            if args.adaptive != "none":
+                mode = f"{mode} + {args.adaptive}"
+            print(f"| {tag} {name} | {n} | {sampler} | {mode} | {ms:.3f}{spread} | {n / ms * 1e3:.3e} | {float(last['total'].detach()):.4e} |", flush=True)
             del tr, net, eq
             torch.cuda.empty_cache()
 
