@@ -261,6 +261,9 @@ int pinn_residual_backward(const PinnNetDesc* net, const float* const* weights, 
 /* Term k (k < n_terms) covers points [lo[k], hi[k]) of u and has its own target array of hi[k] - lo[k] floats:
  * term_losses[k] = mean l(u - target_k) with l = PinnLoss `loss` (pde_base.py:309-326), and
  * cotangent[n] = sum_k weights[k] * l'(u[n] - target_k[n]) / (hi[k] - lo[k])  (n_total floats, overwritten).
+ * An empty term (lo[k] == hi[k]) is allowed: term_losses[k] = 0 and it adds no cotangent (torch's mean over nothing
+ * would be NaN); its target must still be non-null.  n_terms = 0 is allowed too: the cotangent is all zero.
+ * Only term_losses[0 .. n_terms) is written.
  * lo / hi / targets / weights are HOST arrays (read before the call returns); u, targets[k], outputs: device.
  * summary4 (nullable, device): {residual, boundary, initial, total} of compute_loss — residual = residual_sum[0] *
  * residual_scale (the residual launch's loss sum / N), boundary = sum of the first n_boundary_terms term losses,

@@ -140,6 +140,10 @@ __global__ __launch_bounds__(256) void jet_loss_kernel(const float* J, int K, Je
 
 constexpr int kNormBlocks = 64;
 
+// 1 - beta^t of Adam's bias corrections (torch forms them in double).  `1.0f - powf(beta, t)` cancels at small t
+// (1 - 0.999^2 keeps 14 of its 24 bits), which put an error of about 1e-6 into every early update; expm1f does not.
+__device__ __forceinline__ float bias_correction(float beta, float t) { return -expm1f(t * logf(beta)); }
+
 // partial sums of squares in a fixed order (deterministic): block b sums elements b*256+tid, +64*256, ...
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* g, long long n, float* partial) {
   __shared__ float red[256];
@@ -168,7 +172,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     coef = coef < 1.0f ? coef : 1.0f;
   }
   const float t = step[0] + 1.0f;
-  const float bc1 = 1.0f - powf(beta1, t), bc2 = 1.0f - powf(beta2, t);
+  const float bc1 = bias_correction(beta1, t), bc2 = bias_correction(beta2, t);
   const float step_size = lr[0] / bc1, rs2 = rsqrtf(bc2);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float gi = g[i] * coef;
@@ -344,7 +348,7 @@ __global__ __launch_bounds__(64) void adaptive_update_kernel(const double* parti
     coef = coef < 1.0f ? coef : 1.0f;
   }
   const float t = step[0] + 1.0f;
-  const float bc1 = 1.0f - powf(beta1, t), bc2 = 1.0f - powf(beta2, t);
+  const float bc1 = bias_correction(beta1, t), bc2 = bias_correction(beta2, t);
   res[kResCoef] = coef;
   res[kResStepSize] = lr[0] / bc1;
   res[kResRs2] = rsqrtf(bc2);
