@@ -255,7 +255,10 @@ int pinn_residual_backward(const PinnNetDesc* net, const float* const* weights, 
  * With these entry points a whole optimiser step is a handful of launches with no autograd in it (and can be
  * captured in a HIP graph): pinn_residual_loss_grad for the residual term, pinn_jet_forward / pinn_jet_backward
  * (orders 0, 0) for the network values on the boundary / initial points, pinn_point_losses for their loss terms,
- * pinn_adam_clip_step for clip_grad_norm_ + Adam — or, with adaptive loss weights, pinn_adaptive_adam_step. */
+ * pinn_adam_clip_step for clip_grad_norm_ + Adam — or, with adaptive loss weights, pinn_adaptive_adam_step.
+ * With L-BFGS (optimizer "lbfgs" / "adam_lbfgs") the same list WITHOUT its optimiser tail is one closure evaluation
+ * (loss and flat gradient), followed by pinn_lbfgs_eval_stats; pinn_lbfgs_direction is the direction update between two
+ * line searches (section "L-BFGS" below). */
 #define PINN_MAX_POINT_TERMS 8
 
 /* Term k (k < n_terms) covers points [lo[k], hi[k]) of u and has its own target array of hi[k] - lo[k] floats:
@@ -323,6 +326,60 @@ int pinn_adaptive_adam_step(float* params, const float* comp_grads, int64_t ld, 
                             float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr, float beta1, float beta2, float eps,
                             float weight_decay, float max_norm, float* step, float* scratch, float* grad_norm_out,
                             float* grad_out, void* stream);
+
+/* ---- L-BFGS (pinnrl/training/trainer.py:299-309, 373-389; torch/optim/lbfgs.py) --------------------------------------
+ * torch.optim.LBFGS on ONE flat fp32 buffer of n elements.  The host keeps the control flow of step() and of the strong-Wolfe
+ * line search on scalars; these two entry points do everything that touches the n-vectors and hand the host one small record
+ * per call.  All memory is the caller's:
+ *   ring       2 * (history_size + 1) rows of `ld` >= n floats: the s rows of the history_size + 1 slots, then their y rows.
+ *              The spare slot takes the tentative pair, so a rejected pair destroys nothing;
+ *   prev_grad, direction   n floats each (direction: zero before the first call);
+ *   state      pinn_lbfgs_state_bytes(history_size) bytes, 8-byte aligned, doubles: {ring head, count, n_iter, H_diag, 4 spare},
+ *              ro per slot, and the Gram matrix of the ring rows.  ALL ZERO = empty history, n_iter = 0;
+ *   scratch    pinn_lbfgs_scratch_bytes(history_size) bytes, 8-byte aligned (partials, coefficients);
+ *   record     PINN_LBFGS_RECORD_DOUBLES doubles, 8-byte aligned (PINN_LBFGS_REC_*).
+ * history_size in [1, PINN_LBFGS_MAX_HISTORY]; the two size queries return 0 outside it.
+ *
+ * pinn_lbfgs_direction: one direction update (lbfgs.py:396-460) from the gradient `grad` of the accepted point, in three
+ * launches.  (1) Update pass, fixed grid: the tentative pair y = grad - prev_grad, s = (float)t_prev * direction into the
+ * spare slot, prev_grad = grad, and per-block partials (double products and sums) of the inner products of {s, y, grad}
+ * with every live ring row and each other, of max|grad| and sum|grad|.  With n_iter == 0 it does none of the pair work.
+ * (2) One workgroup, the only launch that writes the state: sums the partials in a fixed order; accepts the pair iff
+ * y.s > 1e-10 (advance the ring, evict the oldest pair of a full ring, ro = 1 / y.s, H_diag = y.s / y.y, new Gram row and
+ * column; a rejected pair leaves ring and Gram untouched); runs the two-loop recursion in COEFFICIENT space — q and r are
+ * combinations of {grad, s_i, y_i}, so each s_i.q and y_i.r is a dot of a Gram row with the coefficients, in double, in
+ * torch's order (newest to oldest, scale by H_diag, oldest to newest); writes the 2 count + 1 coefficients and
+ * gtd = grad.direction from the Gram matrix.  With n_iter == 0: direction = -grad, an empty history, H_diag = 1.
+ * (3) Combine pass: direction[i] = sum_j coef_j basis_j[i], accumulated in double in registers and rounded once, and one
+ * max|direction| partial per block.
+ * Record: LOSS 0, GTD, GMAX = max|grad|, GSUM = sum|grad|, ACCEPTED (0 | 1), COUNT (live pairs), ITER (n_iter after the
+ * call), HDIAG, and from PINN_LBFGS_REC_DMAX on 64 per-block partials whose maximum is max|direction|.
+ * Numerics: the coefficient-space recursion equals torch's vector recursion mathematically; its scalars are double and its
+ * Gram entries are double sums of exact fp32 products; it would lose accuracy against the direct form only under
+ * cancellation of order 1e7 or more.
+ *
+ * pinn_lbfgs_eval_stats: what the line search reads of one evaluated trial point, two launches (partials, then a
+ * fixed-order sum in double): LOSS = loss[0] (device float, e.g. the total of summary4; nullable = 0), GTD = grad.direction,
+ * GMAX, GSUM; the rest of the record is zeroed.  scratch: 192 doubles (pinn_lbfgs_scratch_bytes covers them).
+ * No atomics anywhere: bit-identical across runs.  16-byte loads where every n-vector (base, and ld of the ring) is
+ * 16-byte aligned, scalar loads otherwise. */
+#define PINN_LBFGS_MAX_HISTORY 64
+#define PINN_LBFGS_RECORD_DOUBLES 72
+#define PINN_LBFGS_REC_LOSS 0
+#define PINN_LBFGS_REC_GTD 1
+#define PINN_LBFGS_REC_GMAX 2
+#define PINN_LBFGS_REC_GSUM 3
+#define PINN_LBFGS_REC_ACCEPTED 4
+#define PINN_LBFGS_REC_COUNT 5
+#define PINN_LBFGS_REC_ITER 6
+#define PINN_LBFGS_REC_HDIAG 7
+#define PINN_LBFGS_REC_DMAX 8
+size_t pinn_lbfgs_state_bytes(int32_t history_size);
+size_t pinn_lbfgs_scratch_bytes(int32_t history_size);
+int pinn_lbfgs_direction(const float* grad, float* prev_grad, float* direction, float* ring, int64_t ld, int64_t n,
+                         int32_t history_size, double t_prev, double* state, double* scratch, double* record, void* stream);
+int pinn_lbfgs_eval_stats(const float* grad, const float* direction, int64_t n, const float* loss, double* scratch,
+                          double* record, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,13 +28,18 @@ PDE = {
 LOSS = {"mse": 0, "mae": 1, "huber": 2}
 ADAPTIVE = {"rbw": 0, "lrw": 1}
 PINN_ADAPTIVE_SCRATCH_FLOATS = 1296
+PINN_LBFGS_MAX_HISTORY = 64
+PINN_LBFGS_RECORD_DOUBLES = 72
+# the record of pinn_lbfgs_direction / pinn_lbfgs_eval_stats (doubles); from "dmax" on: 64 per-block partials of max|d|
+LBFGS_REC = {"loss": 0, "gtd": 1, "gmax": 2, "gsum": 3, "accepted": 4, "count": 5, "n_iter": 6, "h_diag": 7, "dmax": 8}
 
 EXPORTS = (
     "pinn_abi_version", "pinn_last_error", "pinn_build_info", "pinn_num_tensors", "pinn_pde_streams",
     "pinn_workspace_bytes", "pinn_jet_forward", "pinn_jet_backward", "pinn_residual_forward", "pinn_residual_backward",
     "pinn_residual_loss_grad", "pinn_residual_loss_grad_coef", "pinn_point_losses", "pinn_jet_losses", "pinn_adam_clip_step",
     "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name", "pinn_residual_loss_grad_inverse",
-    "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step",
+    "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
+    "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats",
 )
 
 
@@ -156,6 +161,14 @@ def load():
         lib.pinn_adaptive_adam_step.restype = ctypes.c_int
         lib.pinn_adaptive_adam_step.argtypes = [vp, vp, i64, i32, P(vp), P(f32), i32, f64, f64, P(f32), vp, vp, vp, vp, vp, i64, vp,
                                                 f32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
+        lib.pinn_lbfgs_state_bytes.restype = ctypes.c_size_t
+        lib.pinn_lbfgs_state_bytes.argtypes = [i32]
+        lib.pinn_lbfgs_scratch_bytes.restype = ctypes.c_size_t
+        lib.pinn_lbfgs_scratch_bytes.argtypes = [i32]
+        lib.pinn_lbfgs_direction.restype = ctypes.c_int
+        lib.pinn_lbfgs_direction.argtypes = [vp, vp, vp, vp, i64, i64, i32, f64, vp, vp, vp, vp]
+        lib.pinn_lbfgs_eval_stats.restype = ctypes.c_int
+        lib.pinn_lbfgs_eval_stats.argtypes = [vp, vp, i64, vp, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:
             raise JetLibraryError(f"libpinnjet.so ABI {lib.pinn_abi_version()} != expected {PINN_ABI_VERSION}: rebuild")
         _lib = lib

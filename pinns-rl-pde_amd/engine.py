@@ -482,6 +482,78 @@ def adaptive_adam_step(params: Tensor, comp_grads: Tensor, comp_losses, exp_avg:
                                                scratch.data_ptr(), opt(grad_norm_out), opt(grad_out), _stream(dev)))
 
 
+def lbfgs_state_bytes(history_size: int) -> int:
+    return int(_lib.load().pinn_lbfgs_state_bytes(int(history_size)))
+
+
+def lbfgs_scratch_bytes(history_size: int) -> int:
+    return int(_lib.load().pinn_lbfgs_scratch_bytes(int(history_size)))
+
+
+def lbfgs_buffers(n: int, history_size: int, dev: torch.device) -> Dict[str, Tensor]:
+    """The caller-owned memory of `lbfgs_direction` / `lbfgs_eval_stats` for n parameters: zeroed state (= empty history,
+    n_iter 0), scratch, ring (2 (history_size + 1) rows, ld = n rounded up to 16 bytes), prev_grad, direction, record."""
+    if not 1 <= history_size <= _lib.PINN_LBFGS_MAX_HISTORY:
+        raise ValueError(f"history_size {history_size} outside [1, {_lib.PINN_LBFGS_MAX_HISTORY}]")
+    ld = (n + 3) // 4 * 4
+    z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+    return {"state": z(lbfgs_state_bytes(history_size) // 8, dt=torch.float64),
+            "scratch": z(lbfgs_scratch_bytes(history_size) // 8, dt=torch.float64),
+            "ring": z(2 * (history_size + 1), ld), "prev_grad": z(n), "d": z(n),
+            "record": z(_lib.PINN_LBFGS_RECORD_DOUBLES, dt=torch.float64), "history_size": int(history_size), "n": int(n)}
+
+
+def lbfgs_direction(grad: Tensor, prev_grad: Tensor, direction: Tensor, ring: Tensor, history_size: int, t_prev: float,
+                    state: Tensor, scratch: Tensor, record: Tensor) -> None:
+    """One L-BFGS direction update on flat fp32 buffers (`pinn_lbfgs_direction`, torch/optim/lbfgs.py:396-460): the pair
+    (s = t_prev * direction, y = grad - prev_grad) enters the ring iff y.s > 1e-10, `direction` becomes -H grad by the
+    two-loop recursion, prev_grad = grad.  ring: (2 (history_size + 1), ld >= n); state / scratch / record: float64
+    (`lbfgs_buffers`).  Three launches, nothing read on the host: `record` (device) holds the iteration's scalars."""
+    lib = _lib.load()
+    dev = _require_device(grad, prev_grad, direction, ring, state, scratch, record)
+    n = direction.numel()
+    for tns in (grad, prev_grad, direction, ring):
+        if tns.dtype != torch.float32:
+            raise ValueError("lbfgs_direction: float32 vectors only")
+    for tns in (state, scratch, record):
+        if tns.dtype != torch.float64 or not tns.is_contiguous():
+            raise ValueError("lbfgs_direction: state, scratch and record are contiguous float64 buffers")
+    if ring.dim() != 2 or ring.shape[0] != 2 * (history_size + 1) or ring.stride(1) != 1 or ring.shape[1] < n:
+        raise ValueError("ring: (2 (history_size + 1), ld >= n) with unit stride along a row")
+    assert grad.numel() >= n and prev_grad.numel() == n
+    assert grad.is_contiguous() and prev_grad.is_contiguous() and direction.is_contiguous()
+    assert state.numel() * 8 >= lbfgs_state_bytes(history_size) > 0 and scratch.numel() * 8 >= lbfgs_scratch_bytes(history_size)
+    assert record.numel() >= _lib.PINN_LBFGS_RECORD_DOUBLES
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_lbfgs_direction(grad.data_ptr(), prev_grad.data_ptr(), direction.data_ptr(), ring.data_ptr(),
+                                            ring.stride(0), n, int(history_size), float(t_prev), state.data_ptr(),
+                                            scratch.data_ptr(), record.data_ptr(), _stream(dev)))
+
+
+def lbfgs_eval_stats(grad: Tensor, direction: Tensor, loss: Optional[Tensor], scratch: Tensor, record: Tensor) -> None:
+    """record = {loss[0], grad.direction, max|grad|, sum|grad|} of one evaluated trial point (`pinn_lbfgs_eval_stats`).
+    Two launches, nothing read on the host."""
+    lib = _lib.load()
+    dev = _require_device(grad, direction, loss, scratch, record)
+    n = direction.numel()
+    assert grad.dtype == torch.float32 and direction.dtype == torch.float32 and grad.numel() >= n
+    assert grad.is_contiguous() and direction.is_contiguous()
+    assert scratch.dtype == torch.float64 and scratch.numel() >= 192 and record.dtype == torch.float64
+    assert record.numel() >= _lib.PINN_LBFGS_RECORD_DOUBLES and (loss is None or loss.dtype == torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_lbfgs_eval_stats(grad.data_ptr(), direction.data_ptr(), n, loss.data_ptr() if loss is not None else None,
+                                             scratch.data_ptr(), record.data_ptr(), _stream(dev)))
+
+
+def lbfgs_record(rec) -> Dict[str, float]:
+    """The record as a dict of Python numbers, from a HOST copy of it (sequence of PINN_LBFGS_RECORD_DOUBLES doubles)."""
+    R = _lib.LBFGS_REC
+    out = {k: float(rec[i]) for k, i in R.items() if k != "dmax"}
+    out["dmax"] = float(max(rec[R["dmax"] : _lib.PINN_LBFGS_RECORD_DOUBLES]))
+    out["accepted"], out["count"], out["n_iter"] = bool(out["accepted"]), int(out["count"]), int(out["n_iter"])
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # autograd splices
 # ---------------------------------------------------------------------------------------------

@@ -27,7 +27,8 @@ import torch.optim as optim
 
 from .. import distributed as _D
 from .. import engine as _E
-from .._lib import PINN_ADAPTIVE_SCRATCH_FLOATS
+from .._lib import LBFGS_REC, PINN_ADAPTIVE_SCRATCH_FLOATS, PINN_LBFGS_MAX_HISTORY, PINN_LBFGS_RECORD_DOUBLES
+from .lbfgs import LBFGSDriver
 
 
 class _EmaLossWeights:
@@ -56,6 +57,53 @@ class _EmaLossWeights:
                 self.weights = self.alpha * self.prev_weights + (1 - self.alpha) * self.weights
             self.prev_weights = self.weights.clone()
         return self.weights
+
+
+class _FlatLBFGSBackend:
+    """What `LBFGSDriver` asks for, as launches over the flat buffers of a `PDETrainer`.  `evaluate` and `direction` block
+    once each, on the copy of the 72-double record into pinned host memory; nothing else is read on the host."""
+
+    def __init__(self, trainer, L):
+        self.tr, self.L = trainer, L
+
+    def _read(self):
+        L = self.L
+        L["host"].copy_(L["record"], non_blocking=True)
+        torch.cuda.current_stream(self.tr.device).synchronize()
+        return L["host"].tolist()
+
+    def reset(self):
+        self.L["state"].zero_()
+        self.L["d"].zero_()
+
+    def evaluate(self, t):
+        tr, L = self.tr, self.L
+        F = tr._flat
+        if t is not None:
+            torch.add(L["x0"], L["d"], alpha=float(t), out=F["theta"])
+        x, tt = L["batch"]
+        tr._loss_grad_launches(x, tt, F, tr.model.program(), tr.pde._pde_desc(), tr._chain(x.shape[0]))
+        _E.lbfgs_eval_stats(F["grad"], L["d"], F["summary"][3:4], L["scratch"], L["record"])
+        rec = self._read()
+        return {k: rec[LBFGS_REC[k]] for k in ("loss", "gtd", "gmax", "gsum")}
+
+    def direction(self, t_prev):
+        L = self.L
+        _E.lbfgs_direction(self.tr._flat["grad"], L["prev_grad"], L["d"], L["ring"], L["history_size"], float(t_prev),
+                           L["state"], L["scratch"], L["record"])
+        return _E.lbfgs_record(self._read())
+
+    def snapshot(self):
+        self.L["x0"].copy_(self.tr._flat["theta"])
+
+    def accept(self, t):
+        torch.add(self.L["x0"], self.L["d"], alpha=float(t), out=self.tr._flat["theta"])
+
+    def save(self, slot):
+        self.L["slots"][slot].copy_(self.tr._flat["grad"][: self.L["n"]])
+
+    def restore(self, slot):
+        self.tr._flat["grad"][: self.L["n"]].copy_(self.L["slots"][slot])
 
 
 class PDETrainer:
@@ -145,9 +193,16 @@ class PDETrainer:
         self._optimizer_type = kind
 
     def _switch_to_lbfgs(self):
+        """The hand-over of `adam_lbfgs` (trainer.py:339-371): a fresh torch.optim.LBFGS and a ReduceLROnPlateau scheduler.
+        On a flat state (the Adam phase ran the launch list) the step form switches to `_lbfgs_step_flat` and starts from an
+        empty history, like the fresh optimiser; the torch objects stay, for `param_groups["lr"]`."""
         self.optimizer = self._build_lbfgs(self._collect_optimizable_params())
         self._is_lbfgs = True
         self.scheduler = self._build_scheduler(force_reduce_lr=True)
+        if getattr(self, "_flat", None) is not None:
+            self.optimizer._opt_called = True  # the flat L-BFGS steps; the scheduler only reads / writes param_groups
+            if "lbfgs" in self._flat:
+                self._flat["lbfgs"]["driver"].reset()
 
     def _update_scheduler(self, val_loss=None):
         if isinstance(self.scheduler, optim.lr_scheduler.ReduceLROnPlateau):
@@ -243,6 +298,38 @@ class PDETrainer:
             captured["losses"] = self._losses(x, t)
         return captured["losses"]
 
+    def _lbfgs_flat_state(self):
+        """The flat L-BFGS beside the flat parameters: ring, prev_grad, direction and the double block of
+        `pinn_lbfgs_direction`, x0 and three rotating gradient buffers for the line search, a pinned host copy of the
+        record, and the `LBFGSDriver` whose backend these launches are."""
+        F = self._flat
+        L = F.get("lbfgs")
+        if L is None:
+            c = self.config.training.lbfgs
+            n, dev = F["n"], self.device
+            L = _E.lbfgs_buffers(n, int(c.history_size), dev)
+            L["x0"] = torch.zeros(n, dtype=torch.float32, device=dev)
+            L["slots"] = torch.zeros(3, n, dtype=torch.float32, device=dev)
+            L["host"] = torch.zeros(PINN_LBFGS_RECORD_DOUBLES, dtype=torch.float64).pin_memory()
+            L["batch"] = None
+            L["driver"] = LBFGSDriver(_FlatLBFGSBackend(self, L), max_iter=c.max_iter, tolerance_grad=c.tolerance_grad,
+                                      tolerance_change=c.tolerance_change, line_search_fn=c.line_search_fn,
+                                      lr=lambda: self.optimizer.param_groups[0]["lr"])
+            F["lbfgs"] = L
+        return L
+
+    def _lbfgs_step_flat(self, x, t):
+        """`optimizer.step(closure)` of torch.optim.LBFGS on the flat buffers: every closure evaluation is the launch list
+        without its optimiser tail plus `pinn_lbfgs_eval_stats`, every iteration one `pinn_lbfgs_direction`; the host
+        decides on the records (`LBFGSDriver`).  Returns the summary of the LAST evaluation, as the eager closure does."""
+        L = self._lbfgs_flat_state()
+        L["batch"] = (x, t)
+        try:
+            L["driver"].step()
+        finally:
+            L["batch"] = None
+        return self._manual_losses()
+
     def _losses(self, x, t):
         if self.process_group is not None:
             return _D.sharded_compute_loss(self.pde, self.model, x, t, self.process_group)
@@ -319,6 +406,8 @@ class PDETrainer:
     def train_step(self, x, t):
         """zero_grad -> compute_loss -> backward -> clip -> step  (trainer.py:576-694)."""
         if self._is_lbfgs:
+            if getattr(self, "_flat", None) is not None:
+                return self._lbfgs_step_flat(x, t)
             return self._lbfgs_step(x, t)
         if getattr(self, "_flat", None) is not None:  # parameters live in the flat buffers: same sequence, not captured
             self._manual_launches(x, t)
@@ -348,8 +437,13 @@ class PDETrainer:
         from ..pdes.pde_base import PDEBase
 
         tc = self.config.training
-        if self._is_lbfgs or getattr(tc, "optimizer", "adam") != "adam":
-            return "optimizer is not Adam"
+        kind = getattr(tc, "optimizer", "adam")
+        if kind not in ("adam", "lbfgs", "adam_lbfgs") or (self._is_lbfgs and kind == "adam"):
+            return "optimizer is not Adam or L-BFGS"
+        if kind != "adam":
+            why = self._lbfgs_step_unsupported()
+            if why is not None:
+                return why
         if self.rl_agent is not None and not hasattr(self.rl_agent, "action_probabilities"):
             return "RL agent without a device-side action selection"
         if getattr(tc, "collocation_distribution", "uniform") not in ("uniform", "stratified", "residual_based"):
@@ -382,6 +476,22 @@ class PDETrainer:
             return "random initial condition"
         if self.use_adaptive_weights:
             return self._adaptive_step_unsupported(mode, inverse)
+        return None
+
+    def _lbfgs_step_unsupported(self) -> Optional[str]:
+        """What keeps an `lbfgs` / `adam_lbfgs` run on the eager `_lbfgs_step` (and the Adam phase before it on the autograd
+        step): the flat L-BFGS state covers the network's parameters alone, on one device, with fixed loss weights."""
+        tc = self.config.training
+        if len(getattr(self.pde, "_trainable_params", {})) or self.pde._has_trainable_coefficients():
+            return "L-BFGS with trainable PDE coefficients (the flat vector would be [theta || coefficients])"
+        if self.process_group is not None:
+            return "L-BFGS under a process group"
+        if self.use_adaptive_weights:
+            return "L-BFGS with adaptive loss weights"
+        if int(tc.lbfgs.history_size) > PINN_LBFGS_MAX_HISTORY:
+            return f"L-BFGS history_size {int(tc.lbfgs.history_size)} > {PINN_LBFGS_MAX_HISTORY}"
+        if int(tc.lbfgs.history_size) < 1:
+            return "L-BFGS history_size < 1"
         return None
 
     def _adaptive_step_unsupported(self, mode: str, inverse: bool) -> Optional[str]:
@@ -424,7 +534,10 @@ class PDETrainer:
 
     def _build_flat_state(self):
         """Move the parameters into ONE flat fp32 buffer (each `nn.Parameter` becomes a view of it, same layout as the
-        engine's flat gradient) with flat Adam moments beside it; optimizer state of eager steps taken so far comes along."""
+        engine's flat gradient) with flat Adam moments beside it; Adam state of eager steps taken so far comes along.
+        The history of eager L-BFGS steps taken before the flat state exists does NOT come along: the flat L-BFGS starts
+        from an empty history (torch keeps its pairs per parameter list; `train()` builds the flat state before its first
+        step, so this only concerns `train_step` calls made before it)."""
         if getattr(self, "_flat", None) is not None:
             return self._flat
         prog = self.model.program()
@@ -456,7 +569,7 @@ class PDETrainer:
             "scratch": torch.zeros(64, dtype=torch.float32, device=dev), "n": n, "rw": float(rw), "chains": {},
             "grad_side": torch.zeros(n, dtype=torch.float32, device=dev),
             "summary": torch.zeros(4, dtype=torch.float32, device=dev),
-            "betas": g["betas"], "eps": g["eps"], "wd": g["weight_decay"],
+            "betas": g.get("betas", (0.9, 0.999)), "eps": g.get("eps", 1e-8), "wd": g.get("weight_decay", 0.0),
         }
         slots = self._coefficient_slots() if len(getattr(self.pde, "_trainable_params", {})) else None
         if slots:
@@ -553,7 +666,8 @@ class PDETrainer:
         """One optimiser step as a fixed launch sequence, no autograd (pinnrl/training/trainer.py:686-698 with
         pinnrl/pdes/pde_base.py:1086-1235 inlined): zero the flat gradient; residual + mean l(r) + d/dtheta in one
         launch; network values on the 200 boundary + 100 initial points; their loss terms and cotangents; their
-        reverse sweep; clip_grad_norm_ + Adam over the flat buffers.
+        reverse sweep (`_loss_grad_launches`, which is also the closure of the flat L-BFGS); clip_grad_norm_ + Adam over
+        the flat buffers.
 
         `side`: a second stream for the boundary / initial chain (forward, loss terms, reverse sweep into its own
         gradient buffer).  The residual launch leaves most CUs idle during its last tile round (1 555 tiles on 256 CUs:
@@ -570,6 +684,24 @@ class PDETrainer:
         ch = self._chain(N)
         if self.use_adaptive_weights:
             return self._manual_launches_adaptive(x, t, F, prog, pd, ch, side)
+        self._loss_grad_launches(x, t, F, prog, pd, ch, side)
+        _E.adam_clip_step(F["theta"], F["grad"], F["m"], F["v"], F["lr"], F["step"], F["scratch"], beta1=F["betas"][0],
+                          beta2=F["betas"][1], eps=F["eps"], weight_decay=F["wd"],
+                          max_norm=float(self.config.training.gradient_clipping))
+        if "coef" in F:
+            # the reference clips model.parameters() only (trainer.py:690-694) and steps everything with one Adam: the same
+            # update rule on the trainable coefficient slice, unclipped, with its own step counter
+            lo, hi = F["coef_slice"]
+            _E.adam_clip_step(F["coef"][lo:hi], F["coef_grad"][lo:hi], F["coef_m"][lo:hi], F["coef_v"][lo:hi], F["lr"],
+                              F["coef_step"], F["coef_scratch"], beta1=F["betas"][0], beta2=F["betas"][1], eps=F["eps"],
+                              weight_decay=F["wd"], max_norm=0.0)
+
+    def _loss_grad_launches(self, x, t, F, prog, pd, ch, side=None):
+        """The launch list up to, but not including, its optimiser tail: leaves [flat gradient || loss sum] in F["grad"] and
+        {residual, boundary, initial, total} in F["summary"].  The Adam step runs it once; an L-BFGS step runs it once per
+        closure evaluation."""
+        n, N = F["n"], x.shape[0]
+        loss_name, delta = self.pde._loss_function_name(), self.pde._huber_delta()
 
         def residual_launch():
             if "coef" in F:  # trainable coefficients: read from the device buffer, cotangents into their gradient slots
@@ -611,16 +743,6 @@ class PDETrainer:
             tl = ch["term_losses"]
             F["extra"][0:1].copy_(tl[ch["n_bc"] : -1].sum(0, keepdim=True))
             F["extra"][1:2].copy_(tl[-1:])
-        _E.adam_clip_step(F["theta"], F["grad"], F["m"], F["v"], F["lr"], F["step"], F["scratch"], beta1=F["betas"][0],
-                          beta2=F["betas"][1], eps=F["eps"], weight_decay=F["wd"],
-                          max_norm=float(self.config.training.gradient_clipping))
-        if "coef" in F:
-            # the reference clips model.parameters() only (trainer.py:690-694) and steps everything with one Adam: the same
-            # update rule on the trainable coefficient slice, unclipped, with its own step counter
-            lo, hi = F["coef_slice"]
-            _E.adam_clip_step(F["coef"][lo:hi], F["coef_grad"][lo:hi], F["coef_m"][lo:hi], F["coef_v"][lo:hi], F["lr"],
-                              F["coef_step"], F["coef_scratch"], beta1=F["betas"][0], beta2=F["betas"][1], eps=F["eps"],
-                              weight_decay=F["wd"], max_norm=0.0)
 
     def _manual_launches_adaptive(self, x, t, F, prog, pd, ch, side=None):
         """The launch list with adaptive loss weights (RBW / LRW, trainer.py:586-684).  The weights are detached numbers, so
@@ -732,6 +854,8 @@ class PDETrainer:
         static 4-vector of the last replay).  Steps the fixed sequence does not cover (`_manual_step_unsupported()`:
         L-BFGS, adaptive weights in inverse / data modes, >= 2-D problems, data-parallel training) raise."""
         why = self._manual_step_unsupported()
+        if why is None and (self._is_lbfgs or getattr(self.config.training, "optimizer", "adam") != "adam"):
+            why = "L-BFGS: its line search decides on the host"
         if why is None and self.process_group is not None:
             why = "data-parallel training (a collective inside the capture)"
         if why is not None:

@@ -1,7 +1,7 @@
 """Full training step (SURVEY §8(d) "secondary: full-step pts/s", §8(f) rank 1) on ONE GPU, for context.
 
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
-                               [--adaptive {none,rbw,lrw}] [--repeats 1]
+                               [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -14,6 +14,12 @@ residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam,
 `--adaptive rbw|lrw` turns on adaptive loss weights (`training.adaptive_weights`, default settings of the configuration):
 the autograd mode then runs `_adaptive_total` (LRW: one backward pass per loss component), the other two the adaptive launch
 list (`pinn_adaptive_adam_step`).  `--repeats R` times the window R times and prints the median with the range.
+
+`--optimizer lbfgs` times `optimizer="lbfgs"` instead (C2 and C3 unless --configs is given; max_iter 20, history_size 50,
+strong Wolfe, lr 1, one fixed full batch as L-BFGS wants it, uniform points): the eager step (torch.optim.LBFGS around an
+autograd closure) against the launch list (`_lbfgs_step_flat`).  Both run steps until their ring holds 50 pairs before the
+clock starts.  Reported per form: ms per `step()`, closure evaluations per step, and ms per closure evaluation timed on its
+own (loss + gradient + the one host read that follows it).
 """
 import argparse
 import os
@@ -45,6 +51,86 @@ def build(tag, adaptive="none"):
     return name, net, eq, agent, cfg, n_req
 
 
+def bench_lbfgs(args):
+    tags = [c for c in args.configs.split(",") if c] if args.configs != "C1,C2,C3,C4" else ["C2", "C3"]
+    steps, repeats = max(args.steps, 1), max(args.repeats, 1)
+    print("| config | points | form | ms/step() | evaluations/step | ms/evaluation (alone) | last total loss |")
+    print("|---|---|---|---|---|---|---|")
+    for tag in tags:
+        for form in ("eager", "launch list"):
+            torch.manual_seed(0)
+            name, net, eq, n_req = B.CONFIGS[tag]()
+            cfg = Config.__new__(Config)
+            cfg.device = B.dev
+            cfg.training = TrainingConfig(optimizer="lbfgs", learning_rate=1.0, gradient_clipping=0.0)
+            cfg.training.lbfgs.max_iter, cfg.training.lbfgs.history_size = 20, 50
+            tr = PDETrainer(net, eq, None, cfg, device=B.dev, fast_step=False)
+            if form != "eager":
+                why = tr._manual_step_unsupported()
+                if why is not None:
+                    print(f"| {tag} | - | {form} | not covered: {why} | | | |")
+                    continue
+                tr._build_flat_state()
+            x, t = tr._sample(n_req)
+            n = int(x.shape[0])
+
+            def evals(tr=tr, form=form):
+                if form == "eager":
+                    return tr.optimizer.state[tr.optimizer._params[0]].get("func_evals", 0)
+                return tr._flat["lbfgs"]["driver"].func_evals
+
+            def pairs(tr=tr, form=form):
+                if form == "eager":
+                    return len(tr.optimizer.state[tr.optimizer._params[0]].get("old_dirs", []))
+                return int(tr._flat["lbfgs"]["state"][1].item())
+
+            warm = 0
+            while warm < 3 or (pairs() < 50 and warm < 10):
+                out = tr.train_step(x, t)
+                warm += 1
+            filled = pairs()
+            times, counts = [], []
+            for _ in range(repeats):
+                e0 = evals()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    out = tr.train_step(x, t)
+                torch.cuda.synchronize()
+                times.append(1e3 * (time.perf_counter() - t0) / steps)
+                counts.append((evals() - e0) / steps)
+            # one closure evaluation on its own, as the step pays for it: launches + the host read of the loss
+            if form == "eager":
+                def closure(tr=tr):
+                    tr.optimizer.zero_grad()
+                    losses = tr._losses(x, t)
+                    losses["total"].backward()
+                    return float(losses["total"].detach())
+            else:
+                L = tr._flat["lbfgs"]
+                L["batch"] = (x, t)
+                closure = lambda L=L: L["driver"].backend.evaluate(None)  # noqa: E731
+            for _ in range(3):
+                closure()
+            ctimes = []
+            for _ in range(repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(20):
+                    closure()
+                torch.cuda.synchronize()
+                ctimes.append(1e3 * (time.perf_counter() - t0) / 20)
+
+            def med(v):
+                v = sorted(v)
+                return f"{v[len(v) // 2]:.3f}" + (f" ({v[0]:.3f}-{v[-1]:.3f})" if len(v) > 1 else "")
+
+            print(f"| {tag} {name} | {n} | {form} (ring {filled}) | {med(times)} | {med(counts)} | {med(ctimes)} | "
+                  f"{float(out['total'].detach()):.4e} |", flush=True)
+            del tr, net, eq
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C4")
@@ -52,7 +138,10 @@ def main():
     ap.add_argument("--modes", default="autograd,manual,graph")
     ap.add_argument("--adaptive", choices=["none", "rbw", "lrw"], default="none")
     ap.add_argument("--repeats", type=int, default=1)
+    ap.add_argument("--optimizer", choices=["adam", "lbfgs"], default="adam")
     args = ap.parse_args()
+    if args.optimizer == "lbfgs":
+        return bench_lbfgs(args)
     print("| config | points | sampler | mode | ms/step | points/s | last total loss |")
     print("|---|---|---|---|---|---|---|")
     for tag in [c for c in args.configs.split(",") if c]:
