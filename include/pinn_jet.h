@@ -287,6 +287,30 @@ int pinn_jet_losses(const float* jets, int32_t n_streams, int32_t n_total, int32
                     int32_t loss, float huber_delta, float* term_losses, float* cotangent, const float* residual_sum,
                     float residual_scale, float residual_weight, int32_t n_boundary_terms, float* summary4, void* stream);
 
+/* The finite-difference smoothness term of HeatEquation.compute_loss (pinnrl/pdes/heat_equation.py:625-650), 1-D:
+ *   S = mean|(u(x+e,t) - u(x,t))/e| + mean|(u(x,t) - u(x-e,t))/e|  over the N collocation points, shifted points clamped
+ * to [x_lo, x_hi].  Two entry points around a pinn_jet_forward / pinn_jet_backward pair (orders 0, 0) on 3N points.
+ *
+ * pinn_fd_stencil_points: x3 = [x | clamp(x + e, x_lo, x_hi) | clamp(x - e, x_lo, x_hi)], t3 = [t | t | t], 3N floats each,
+ * the segments at offsets 0, N, 2N.  e = (float)eps, the bounds are rounded to float, x + e is one fp32 add: bit-equal to
+ * torch.clamp(x + eps, x_lo, x_hi) on fp32 tensors.  16-byte accesses on every segment whose base is 16-byte aligned,
+ * scalar accesses on the others (N need not be a multiple of 4).  N < 0, eps <= 0, x_lo > x_hi, a null pointer with
+ * N > 0: PINN_ERR_BAD_DESC before any launch.  N == 0: no-op.  One launch.
+ *
+ * pinn_fd_smoothness: u3 = the value stream on those points, [uc | up | um].  loss_out[0] = S, unweighted (fp32
+ * differences, a true division per point, sums and means in double, rounded once);  cotangent3 (3N floats, overwritten) =
+ * weight * dS/du3 = c * [sgn(uc - um) - sgn(up - uc) | sgn(up - uc) | -sgn(uc - um)], c = weight / (eps N), sgn(0) = 0 (a
+ * point on a domain end has up == uc or um == uc exactly);  summary4 (nullable): summary4[3] += weight * S — call it
+ * after the pinn_jet_losses call that wrote the summary.  scratch: PINN_FD_SCRATCH_DOUBLES doubles, 8-byte aligned.
+ * N <= 0, eps <= 0, null u3 / loss_out / cotangent3 / scratch: PINN_ERR_BAD_DESC; misaligned scratch: PINN_ERR_MISALIGNED.
+ * Two launches (a fixed grid of per-block partials and the cotangents, then their ordered sum); no atomics:
+ * bit-identical across runs. */
+#define PINN_FD_SCRATCH_DOUBLES 128
+int pinn_fd_stencil_points(const float* x, const float* t, int64_t N, double eps, double x_lo, double x_hi, float* x3, float* t3,
+                           void* stream);
+int pinn_fd_smoothness(const float* u3, int64_t N, double eps, float weight, float* loss_out, float* cotangent3, float* summary4,
+                       double* scratch, void* stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.
  * lr and step are DEVICE scalars (step = number of steps taken so far, incremented by the call) so that a captured

@@ -28,6 +28,7 @@ PDE = {
 LOSS = {"mse": 0, "mae": 1, "huber": 2}
 ADAPTIVE = {"rbw": 0, "lrw": 1}
 PINN_ADAPTIVE_SCRATCH_FLOATS = 1296
+PINN_FD_SCRATCH_DOUBLES = 128
 PINN_LBFGS_MAX_HISTORY = 64
 PINN_LBFGS_RECORD_DOUBLES = 72
 # the record of pinn_lbfgs_direction / pinn_lbfgs_eval_stats (doubles); from "dmax" on: 64 per-block partials of max|d|
@@ -39,7 +40,7 @@ EXPORTS = (
     "pinn_residual_loss_grad", "pinn_residual_loss_grad_coef", "pinn_point_losses", "pinn_jet_losses", "pinn_adam_clip_step",
     "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name", "pinn_residual_loss_grad_inverse",
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
-    "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats",
+    "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
 )
 
 
@@ -169,6 +170,10 @@ def load():
         lib.pinn_lbfgs_direction.argtypes = [vp, vp, vp, vp, i64, i64, i32, f64, vp, vp, vp, vp]
         lib.pinn_lbfgs_eval_stats.restype = ctypes.c_int
         lib.pinn_lbfgs_eval_stats.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+        lib.pinn_fd_stencil_points.restype = ctypes.c_int
+        lib.pinn_fd_stencil_points.argtypes = [vp, vp, i64, f64, f64, f64, vp, vp, vp]
+        lib.pinn_fd_smoothness.restype = ctypes.c_int
+        lib.pinn_fd_smoothness.argtypes = [vp, i64, f64, f32, vp, vp, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:
             raise JetLibraryError(f"libpinnjet.so ABI {lib.pinn_abi_version()} != expected {PINN_ABI_VERSION}: rebuild")
         _lib = lib

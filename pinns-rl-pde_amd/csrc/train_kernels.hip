@@ -422,6 +422,115 @@ __global__ __launch_bounds__(256) void adaptive_adam_kernel(float* p, const floa
   }
 }
 
+// ---- finite-difference smoothness term (pinnrl/pdes/heat_equation.py:625-650) -------------------------------------------------
+// S = mean|(u(x+e,t) - u(x,t))/e| + mean|(u(x,t) - u(x-e,t))/e| over the collocation batch, shifted points clamped to the
+// domain: the stencil kernel writes the 3N evaluation points [x | x+e | x-e], pinn_jet_forward (orders 0, 0) evaluates them,
+// and one pass over the values gives the partial sums and the cotangents of the reverse sweep (they do not need S).
+// Both kernels walk the points in quads; a quad is moved with one 16-byte access where its segment base is 16-byte aligned
+// and the quad is whole, with scalar accesses otherwise (segment s starts at s * N floats).  Which thread sums which point
+// does not depend on the alignment.
+constexpr int kFdBlocks = 64;
+static_assert(PINN_FD_SCRATCH_DOUBLES >= 2 * kFdBlocks, "scratch size");
+
+__device__ __forceinline__ void fd_load4(const float* p, long long i, long long n, bool vec, float v[4]) {
+  if (vec && i + 4 <= n) {
+    const float4 q = *reinterpret_cast<const float4*>(p + i);
+    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? p[i + j] : 0.0f;
+  }
+}
+
+__device__ __forceinline__ void fd_store4(float* p, long long i, long long n, bool vec, const float v[4]) {
+  if (vec && i + 4 <= n) {
+    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < n) p[i + j] = v[j];
+  }
+}
+
+// al: bit 0 x, bit 1 t, bits 2..4 the three segments of x3, bits 5..7 those of t3 — set where 16-byte aligned.
+// x + e and x - e are single fp32 operations on (float)eps, then torch.clamp's min(max(v, lo), hi): bit-equal to torch.
+__global__ __launch_bounds__(256) void fd_stencil_kernel(const float* x, const float* t, long long n, float eps, float lo, float hi,
+                                                         float* x3, float* t3, int al) {
+  const long long nq = (n + 3) >> 2;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+    const long long i = q << 2;
+    float xc[4], tc[4], xp[4], xm[4];
+    fd_load4(x, i, n, al & 1, xc);
+    fd_load4(t, i, n, al & 2, tc);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      xp[j] = fminf(fmaxf(xc[j] + eps, lo), hi);
+      xm[j] = fminf(fmaxf(xc[j] - eps, lo), hi);
+    }
+    fd_store4(x3, i, n, al & 4, xc);
+    fd_store4(x3 + n, i, n, al & 8, xp);
+    fd_store4(x3 + 2 * n, i, n, al & 16, xm);
+    fd_store4(t3, i, n, al & 32, tc);
+    fd_store4(t3 + n, i, n, al & 64, tc);
+    fd_store4(t3 + 2 * n, i, n, al & 128, tc);
+  }
+}
+
+__device__ __forceinline__ float fd_sign(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }  // sgn(0) = 0: torch's abs backward
+
+// u3 = [uc | up | um].  Block b sums quads b * 256 + tid, + gridDim * 256, ... in double; partial[2 b] = sum|(up - uc)/e|,
+// partial[2 b + 1] = sum|(uc - um)/e|.  The differences are fp32 subtractions (their signs are the reference's signs);
+// the quotient is a true division, taken in double.  cot3 = c * {s2 - s1 | s1 | -s2}, c = weight / (e N).
+// al: bits 0..2 the segments of u3, bits 3..5 those of cot3.
+__global__ __launch_bounds__(256) void fd_smooth_kernel(const float* u3, long long n, double eps, float c, float* cot3, double* partial,
+                                                        int al) {
+  __shared__ double red[256];
+  const long long nq = (n + 3) >> 2;
+  double a1 = 0.0, a2 = 0.0;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+    const long long i = q << 2;
+    float uc[4], up[4], um[4], cc[4], cp[4], cm[4];
+    fd_load4(u3, i, n, al & 1, uc);
+    fd_load4(u3 + n, i, n, al & 2, up);
+    fd_load4(u3 + 2 * n, i, n, al & 4, um);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // lanes past n were loaded as 0: they add 0 and are not stored
+      const float d1 = up[j] - uc[j], d2 = uc[j] - um[j];
+      a1 += fabs((double)d1) / eps;
+      a2 += fabs((double)d2) / eps;
+      const float s1 = fd_sign(d1), s2 = fd_sign(d2);
+      cp[j] = s1 * c;
+      cc[j] = (s2 - s1) * c;
+      cm[j] = -s2 * c;
+    }
+    fd_store4(cot3, i, n, al & 8, cc);
+    fd_store4(cot3 + n, i, n, al & 16, cp);
+    fd_store4(cot3 + 2 * n, i, n, al & 32, cm);
+  }
+  for (int k = 0; k < 2; ++k) {
+    red[threadIdx.x] = k ? a2 : a1;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[2 * blockIdx.x + k] = red[0];
+    __syncthreads();
+  }
+}
+
+// one thread: the block partials in a fixed order, S = mean + mean in double, rounded once
+__global__ void fd_finish_kernel(const double* partial, int blocks, long long n, float weight, float* loss_out, float* summary4) {
+  double s1 = 0.0, s2 = 0.0;
+  for (int b = 0; b < blocks; ++b) {
+    s1 += partial[2 * b];
+    s2 += partial[2 * b + 1];
+  }
+  const double S = s1 / (double)n + s2 / (double)n;
+  loss_out[0] = (float)S;
+  if (summary4) summary4[3] = (float)((double)summary4[3] + (double)weight * S);
+}
+
 }  // namespace
 
 extern "C" int pinn_internal_fail(int code, const char* msg);  // pinn_abi.hip: sets pinn_last_error()
@@ -570,6 +679,44 @@ int pinn_adaptive_adam_step(float* params, const float* comp_grads, int64_t ld, 
   if ((rc = launched("adaptive_update_kernel"))) return rc;
   phase(1);
   return launched("adaptive_adam_kernel");
+}
+
+int pinn_fd_stencil_points(const float* x, const float* t, int64_t N, double eps, double x_lo, double x_hi, float* x3, float* t3,
+                           void* stream) {
+  if (N < 0 || !(eps > 0.0) || !(x_lo <= x_hi))
+    return pinn_internal_fail(PINN_ERR_BAD_DESC, "pinn_fd_stencil_points: N < 0, eps <= 0 or x_lo > x_hi");
+  if (N == 0) return PINN_OK;
+  if (!x || !t || !x3 || !t3) return pinn_internal_fail(PINN_ERR_BAD_DESC, "pinn_fd_stencil_points: null argument");
+  auto al = [](const float* p, int64_t off) { return ((reinterpret_cast<uintptr_t>(p) + 4u * (uintptr_t)off) & 15u) == 0; };
+  int bits = (al(x, 0) ? 1 : 0) | (al(t, 0) ? 2 : 0);
+  for (int s = 0; s < 3; ++s) bits |= (al(x3, s * N) ? 4 << s : 0) | (al(t3, s * N) ? 32 << s : 0);
+  const long long nq = ((long long)N + 3) >> 2;
+  int blocks = (int)((nq + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(fd_stencil_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, t, (long long)N, (float)eps,
+                     (float)x_lo, (float)x_hi, x3, t3, bits);
+  return launched("fd_stencil_kernel");
+}
+
+int pinn_fd_smoothness(const float* u3, int64_t N, double eps, float weight, float* loss_out, float* cotangent3, float* summary4,
+                       double* scratch, void* stream) {
+  if (N <= 0 || !(eps > 0.0)) return pinn_internal_fail(PINN_ERR_BAD_DESC, "pinn_fd_smoothness: N <= 0 or eps <= 0");
+  if (!u3 || !loss_out || !cotangent3 || !scratch) return pinn_internal_fail(PINN_ERR_BAD_DESC, "pinn_fd_smoothness: null argument");
+  if (reinterpret_cast<uintptr_t>(scratch) & 7u)
+    return pinn_internal_fail(PINN_ERR_MISALIGNED, "pinn_fd_smoothness: scratch must be 8-byte aligned");
+  auto al = [](const float* p, int64_t off) { return ((reinterpret_cast<uintptr_t>(p) + 4u * (uintptr_t)off) & 15u) == 0; };
+  int bits = 0;
+  for (int s = 0; s < 3; ++s) bits |= (al(u3, s * N) ? 1 << s : 0) | (al(cotangent3, s * N) ? 8 << s : 0);
+  const long long nq = ((long long)N + 3) >> 2;
+  int blocks = (int)((nq + 255) / 256);
+  if (blocks > kFdBlocks) blocks = kFdBlocks;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const float c = (float)((double)weight / (eps * (double)N));
+  hipLaunchKernelGGL(fd_smooth_kernel, dim3(blocks), dim3(256), 0, st, u3, (long long)N, eps, c, cotangent3, scratch, bits);
+  int rc = launched("fd_smooth_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(fd_finish_kernel, dim3(1), dim3(1), 0, st, scratch, blocks, (long long)N, weight, loss_out, summary4);
+  return launched("fd_finish_kernel");
 }
 
 }  // extern "C"

@@ -423,6 +423,42 @@ def jet_losses(jets: Tensor, terms: Sequence[Tuple[int, int, int, int, Optional[
                                        summary4.data_ptr() if summary4 is not None else None, _stream(dev)))
 
 
+def fd_stencil_points(x: Tensor, t: Tensor, eps: float, lo: float, hi: float, x3: Tensor, t3: Tensor) -> None:
+    """x3 = [x | clamp(x + eps, lo, hi) | clamp(x - eps, lo, hi)], t3 = [t | t | t] (`pinn_fd_stencil_points`, 1-D): the 3N
+    evaluation points of the finite-difference smoothness term, bit-equal to torch's fp32 arithmetic.  x, t: N contiguous
+    floats; x3, t3: 3N each, caller-owned.  One launch."""
+    lib = _lib.load()
+    dev = _require_device(x, t, x3, t3)
+    N = x.numel()
+    for tns in (x, t, x3, t3):
+        if tns.dtype != torch.float32 or not tns.is_contiguous():
+            raise ValueError("fd_stencil_points: contiguous float32 buffers only")
+    assert t.numel() == N and x3.numel() == 3 * N and t3.numel() == 3 * N
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_fd_stencil_points(x.data_ptr(), t.data_ptr(), N, float(eps), float(lo), float(hi), x3.data_ptr(),
+                                              t3.data_ptr(), _stream(dev)))
+
+
+def fd_smoothness(u3: Tensor, eps: float, weight: float, loss_out: Tensor, cot3: Tensor, scratch: Tensor,
+                  summary4: Optional[Tensor] = None) -> None:
+    """The smoothness term on the values u3 = [uc | up | um] of the stencil points (`pinn_fd_smoothness`): loss_out[0] =
+    S = mean|(up - uc)/eps| + mean|(uc - um)/eps| (unweighted), cot3 (3N, overwritten) = weight * dS/du3 with sgn(0) = 0,
+    summary4[3] += weight * S where given.  scratch: PINN_FD_SCRATCH_DOUBLES float64.  Two launches, no atomics."""
+    lib = _lib.load()
+    dev = _require_device(u3, loss_out, cot3, scratch, summary4)
+    if u3.numel() % 3:
+        raise ValueError("fd_smoothness: u3 holds the three segments [uc | up | um] of equal length")
+    N = u3.numel() // 3
+    for tns in (u3, loss_out, cot3):
+        if tns.dtype != torch.float32 or not tns.is_contiguous():
+            raise ValueError("fd_smoothness: contiguous float32 buffers only")
+    assert cot3.numel() == 3 * N and loss_out.numel() >= 1 and (summary4 is None or summary4.numel() >= 4)
+    assert scratch.dtype == torch.float64 and scratch.is_contiguous() and scratch.numel() >= _lib.PINN_FD_SCRATCH_DOUBLES
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_fd_smoothness(u3.data_ptr(), N, float(eps), float(weight), loss_out.data_ptr(), cot3.data_ptr(),
+                                          summary4.data_ptr() if summary4 is not None else None, scratch.data_ptr(), _stream(dev)))
+
+
 def adam_clip_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, lr: Tensor, step: Tensor,
                    scratch: Tensor, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                    weight_decay: float = 0.0, max_norm: float = 0.0, grad_norm_out: Optional[Tensor] = None) -> None:

@@ -278,8 +278,18 @@ class HeatEquation(PDEBase):
                  (2 * nbp, 2 * nbp + xi.shape[0], 0, 0, target.reshape(-1).float().contiguous(), float(iw))]
         return {"x": x_all, "t": t_all, "nt": 1, "nx": 1, "terms": terms, "n_bc": 2}
 
+    _SMOOTHNESS_EPS = 1e-4  # heat_equation.py:634; read by the eager term below and by the launch list
+
+    def _manual_smoothness(self):
+        """`_compute_smoothness_loss` as data for the launch list (see PDEBase._manual_smoothness): 1-D, positive weight."""
+        lw = self._loss_weights()
+        weight = float(lw.get("smoothness", 0.0)) if lw else 0.0
+        if self.dimension != 1 or not weight > 0.0:
+            return None
+        return {"eps": float(self._SMOOTHNESS_EPS), "weight": weight, "lo": float(self.domain[0][0]), "hi": float(self.domain[0][1])}
+
     def _compute_smoothness_loss(self, model, x, t):  # heat_equation.py:625-650
-        eps = 1e-4
+        eps = self._SMOOTHNESS_EPS
         x, t = x.detach(), t.detach()
         uc = model(torch.cat([x, t], dim=1))
         out = torch.zeros((), device=self.device)

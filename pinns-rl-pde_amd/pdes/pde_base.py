@@ -645,6 +645,12 @@ class PDEBase:
         return {"x": torch.cat([xb, xi], 0).contiguous(), "t": torch.cat([tb, ti], 0).contiguous(), "nt": 0, "nx": 0,
                 "terms": terms, "n_bc": len(terms) - 1}
 
+    def _manual_smoothness(self) -> Optional[Dict[str, float]]:
+        """The smoothness term of an own `compute_loss` as data for the autograd-free step: None (no such term, or none
+        with a launch-list form), or {"eps", "weight", "lo", "hi"} of a 1-D finite-difference term on the collocation batch
+        (`engine.fd_stencil_points` / `engine.fd_smoothness`)."""
+        return None
+
     def _compose_losses(self, residual_loss, boundary_loss, initial_loss, smoothness_loss, data_loss, aux_scale=1.0):
         """The weighting / mode gating tail shared by every `compute_loss` (pde_base.py:1168-1235, heat_equation.py:543-623)."""
         lw_obj = self._loss_weights()

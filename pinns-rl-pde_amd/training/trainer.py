@@ -27,7 +27,7 @@ import torch.optim as optim
 
 from .. import distributed as _D
 from .. import engine as _E
-from .._lib import LBFGS_REC, PINN_ADAPTIVE_SCRATCH_FLOATS, PINN_LBFGS_MAX_HISTORY, PINN_LBFGS_RECORD_DOUBLES
+from .._lib import LBFGS_REC, PINN_ADAPTIVE_SCRATCH_FLOATS, PINN_FD_SCRATCH_DOUBLES, PINN_LBFGS_MAX_HISTORY, PINN_LBFGS_RECORD_DOUBLES
 from .lbfgs import LBFGSDriver
 
 
@@ -452,7 +452,10 @@ class PDETrainer:
         if own_loss and type(self.pde)._manual_chain is PDEBase._manual_chain:
             return f"{type(self.pde).__name__} overrides compute_loss without a launch-list form (_manual_chain)"
         if own_loss and (self.pde._loss_weights() or {}).get("smoothness", 0.0) > 0:
-            return "smoothness term"
+            if self.pde._manual_smoothness() is None:
+                return "smoothness term"
+            if self.process_group is not None:
+                return "smoothness term under a process group"
         if self.pde.dimension != 1:
             return "multi-dimensional problem"
         mode = self.pde._training_mode()
@@ -602,6 +605,8 @@ class PDETrainer:
                                                 self.pde._huber_delta())})
         F = self._flat
         F["extra"] = torch.zeros(2, dtype=torch.float32, device=dev)  # {initial, data} when the chain carries a data term
+        if self.pde._manual_smoothness() is not None:
+            F["smooth_loss"] = torch.zeros(1, dtype=torch.float32, device=dev)  # the unweighted smoothness term of the last step
         if self.use_adaptive_weights:
             # adaptive loss weights: one gradient row per component [residual, boundary, initial] and the EMA state of
             # pinn_adaptive_adam_step {running[4], prev_weights[4], weights[4], calls, has_prev}; the state of eager steps
@@ -659,6 +664,15 @@ class PDETrainer:
                     ch["term_losses_" + half] = torch.zeros(len(terms), dtype=torch.float32, device=dev)
                     ch["cot_" + half] = torch.zeros(K, npts, dtype=torch.float32, device=dev)
                     ch["summary_" + half] = torch.zeros(4, dtype=torch.float32, device=dev)
+            sm = self.pde._manual_smoothness()
+            if sm is not None:
+                # the finite-difference smoothness term on the collocation batch: its 3 n_batch stencil points, the
+                # cotangents of their values and the partial sums of pinn_fd_smoothness
+                nb = int(n_batch)
+                ch["smooth"] = dict(sm, x3=torch.zeros(3 * nb, 1, dtype=torch.float32, device=dev),
+                                    t3=torch.zeros(3 * nb, 1, dtype=torch.float32, device=dev),
+                                    cot3=torch.zeros(1, 3 * nb, dtype=torch.float32, device=dev),
+                                    scratch=torch.zeros(PINN_FD_SCRATCH_DOUBLES, dtype=torch.float64, device=dev))
             F["chains"][key] = ch
         return ch
 
@@ -737,6 +751,17 @@ class PDETrainer:
             # kernel runs once more here; it rewrites the same cotangents
             _E.jet_losses(u, ch["terms"], loss_name, delta, ch["term_losses"], ch["cot"], residual_sum=F["grad"][n : n + 1],
                           residual_scale=1.0 / float(N), residual_weight=F["rw"], n_boundary_terms=ch["n_bc"], summary4=F["summary"])
+        sm = ch.get("smooth")
+        if sm is not None:
+            # the smoothness term (HeatEquation._compute_smoothness_loss), after the summary is written and every other
+            # gradient is in place: stencil points of the batch, their values, S + cotangents (total += weight * S), the
+            # reverse sweep into the same flat gradient.  On the main stream, after the join: nothing else writes
+            # F["grad"] or F["summary"] by then.  The term does not depend on the PDE coefficients.
+            _E.fd_stencil_points(x.detach().float().contiguous().reshape(-1), t.detach().float().contiguous().reshape(-1),
+                                 sm["eps"], sm["lo"], sm["hi"], sm["x3"], sm["t3"])
+            u3 = _E.jets_forward(prog, sm["x3"], sm["t3"], 0, 0)
+            _E.fd_smoothness(u3, sm["eps"], sm["weight"], F["smooth_loss"], sm["cot3"], sm["scratch"], summary4=F["summary"])
+            _E.jets_backward(prog, sm["x3"], sm["t3"], 0, 0, sm["cot3"], F["grad"][:n])
         F["has_data"] = ch["has_data"]
         if ch["has_data"]:
             # summary4's `initial` is "all terms after the boundary ones": split the data term (the last one) out of it
@@ -812,7 +837,8 @@ class PDETrainer:
                           max_norm=float(self.config.training.gradient_clipping))
 
     def _manual_losses(self, static: bool = False):
-        """{residual, boundary, initial, total} of the last manual step — with adaptive loss weights also "weights", the
+        """{residual, boundary, initial, total} of the last manual step — with a smoothness term on the launch list also
+        "smoothness" (unweighted; it is part of total); with adaptive loss weights also "weights", the
         step's four weights (padded with 0), and total = sum_c w_c L_c.  `static=True` hands out views of the persistent
         summary buffer (what a captured graph refreshes in place); otherwise independent copies, so that a caller may
         keep one per step (`train()` averages them per epoch)."""
@@ -825,6 +851,8 @@ class PDETrainer:
             out["initial"], out["data"] = e[0], e[1]
         elif self.pde._training_mode() in ("inverse", "data_augmented"):
             out["data"] = torch.zeros((), dtype=torch.float32, device=s.device)
+        if "smooth_loss" in self._flat:
+            out["smoothness"] = self._flat["smooth_loss"][0] if static else self._flat["smooth_loss"][0].clone()
         if "weights" in self._flat:
             out["weights"] = self._flat["weights"] if static else self._flat["weights"].clone()
         return out
@@ -851,8 +879,11 @@ class PDETrainer:
         `loss.backward()` crashed on a stale AccumulateGrad node).  The learning rate lives in a device scalar that
         `train` refreshes after each scheduler step.  Adaptive loss weights (RBW / LRW) of a forward problem are part of
         the captured step (`_manual_launches_adaptive`: the EMA state lives on the device; `losses["weights"]` is the
-        static 4-vector of the last replay).  Steps the fixed sequence does not cover (`_manual_step_unsupported()`:
-        L-BFGS, adaptive weights in inverse / data modes, >= 2-D problems, data-parallel training) raise."""
+        static 4-vector of the last replay).  HeatEquation's finite-difference smoothness term (1-D, fixed loss weights) is
+        part of it too: four more launches on the main stream after the join (`losses["smoothness"]` is the static,
+        unweighted term of the last replay).  Steps the fixed sequence does not cover (`_manual_step_unsupported()`:
+        L-BFGS, adaptive weights in inverse / data modes or with a smoothness component, >= 2-D problems, data-parallel
+        training) raise."""
         why = self._manual_step_unsupported()
         if why is None and (self._is_lbfgs or getattr(self.config.training, "optimizer", "adam") != "adam"):
             why = "L-BFGS: its line search decides on the host"

@@ -1,7 +1,7 @@
 """Full training step (SURVEY §8(d) "secondary: full-step pts/s", §8(f) rank 1) on ONE GPU, for context.
 
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
-                               [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}]
+                               [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -14,6 +14,10 @@ residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam,
 `--adaptive rbw|lrw` turns on adaptive loss weights (`training.adaptive_weights`, default settings of the configuration):
 the autograd mode then runs `_adaptive_total` (LRW: one backward pass per loss component), the other two the adaptive launch
 list (`pinn_adaptive_adam_step`).  `--repeats R` times the window R times and prints the median with the range.
+
+`--smoothness W` (C1 only) runs HeatEquation with the reference's default loss weights {residual 15, boundary 20, initial 10,
+smoothness W}: its finite-difference smoothness term is three more network evaluations of the batch and their reverse
+sweeps — autograd nodes in the autograd mode, four launches of the launch list in the other two.
 
 `--optimizer lbfgs` times `optimizer="lbfgs"` instead (C2 and C3 unless --configs is given; max_iter 20, history_size 50,
 strong Wolfe, lr 1, one fixed full batch as L-BFGS wants it, uniform points): the eager step (torch.optim.LBFGS around an
@@ -37,7 +41,7 @@ from pinnrl_amd.rl import RLAgent  # noqa: E402
 from pinnrl_amd.training import PDETrainer  # noqa: E402
 
 
-def build(tag, adaptive="none"):
+def build(tag, adaptive="none", smoothness=0.0):
     name, net, eq, n_req = B.CONFIGS[tag]()
     agent = None
     if tag == "C3":  # BASELINE C3: DQN adaptive sampling
@@ -46,6 +50,10 @@ def build(tag, adaptive="none"):
     cfg = Config.__new__(Config)
     cfg.device = B.dev
     cfg.training = TrainingConfig()
+    if smoothness > 0:  # the reference's default configuration: the PDE reads its loss weights from the training section
+        cfg.training = TrainingConfig(loss_weights={"residual": 15.0, "boundary": 20.0, "initial": 10.0, "smoothness": float(smoothness)})
+        eq.config.training = cfg.training
+        name += f", smoothness {smoothness:g}"
     if adaptive != "none":
         cfg.training.adaptive_weights = AdaptiveWeightsConfig(enabled=True, strategy=adaptive)
     return name, net, eq, agent, cfg, n_req
@@ -139,6 +147,7 @@ def main():
     ap.add_argument("--adaptive", choices=["none", "rbw", "lrw"], default="none")
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--optimizer", choices=["adam", "lbfgs"], default="adam")
+    ap.add_argument("--smoothness", type=float, default=0.0, help="C1 only: weight of HeatEquation's smoothness term")
     args = ap.parse_args()
     if args.optimizer == "lbfgs":
         return bench_lbfgs(args)
@@ -146,8 +155,11 @@ def main():
     print("|---|---|---|---|---|---|---|")
     for tag in [c for c in args.configs.split(",") if c]:
         for mode in args.modes.split(","):
+            if args.smoothness > 0 and tag != "C1":
+                print(f"| {tag} | - | - | {mode} | not covered: --smoothness applies to C1 (HeatEquation) only | | |")
+                continue
             torch.manual_seed(0)
-            name, net, eq, agent, cfg, n_req = build(tag, args.adaptive)
+            name, net, eq, agent, cfg, n_req = build(tag, args.adaptive, args.smoothness)
             tr = PDETrainer(net, eq, None, cfg, device=B.dev, rl_agent=agent, fast_step=False)
             if mode != "autograd":
                 why = tr._manual_step_unsupported()
