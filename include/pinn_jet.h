@@ -169,6 +169,18 @@ int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32
 int pinn_kernel_name(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
                      char* buf, size_t len);
 
+/* How jet_kernel_u16 deals N points to `grid` workgroups (the grid of pinn_kernel_for).  rounds = R = N / (16 grid):
+ * workgroup b runs the 16-point units b, b + grid, ... of R full rounds.  The points from first_tail_point = 16 grid R on
+ * are the last round, groups = G = ceil((N - first_tail_point) / (4 grid)) four-point groups per workgroup:
+ *   G = 0      nothing is left;
+ *   G = 1..3   one packed round (4 points x 4 streams per 16-column MFMA operand group): workgroup b takes the points
+ *              first_tail_point + 4 G b .. + 4 G - 1 that lie below N, so the round costs G quarters of a unit's MFMAs and
+ *              all workgroups run it;
+ *   G = 4      ordinary units first_tail_point / 16 + b.
+ * A unit that was built without the packed round (pinn_build_info(): "nopack ...") runs every G > 0 as G = 4.
+ * Outputs are nullable.  PINN_OK, or PINN_ERR_BAD_DESC for N < 0 or grid < 1. */
+int pinn_unit_tail_plan(int64_t N, int32_t grid, int64_t* rounds, int32_t* groups, int64_t* first_tail_point);
+
 /* Every compute entry point: `weights` (and `weight_grads`) are tables of `num_tensors` device pointers in the
  * reference's state_dict order; the count is validated against the descriptor BEFORE any entry is read.
  * `workspace` must hold pinn_workspace_bytes(...) bytes, 16-byte aligned (may be NULL when that is 0).

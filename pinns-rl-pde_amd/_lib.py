@@ -41,6 +41,7 @@ EXPORTS = (
     "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name", "pinn_residual_loss_grad_inverse",
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
+    "pinn_unit_tail_plan",
 )
 
 
@@ -174,6 +175,8 @@ def load():
         lib.pinn_fd_stencil_points.argtypes = [vp, vp, i64, f64, f64, f64, vp, vp, vp]
         lib.pinn_fd_smoothness.restype = ctypes.c_int
         lib.pinn_fd_smoothness.argtypes = [vp, i64, f64, f32, vp, vp, vp, vp, vp]
+        lib.pinn_unit_tail_plan.restype = ctypes.c_int
+        lib.pinn_unit_tail_plan.argtypes = [i64, i32, P(i64), P(i32), P(i64)]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:
             raise JetLibraryError(f"libpinnjet.so ABI {lib.pinn_abi_version()} != expected {PINN_ABI_VERSION}: rebuild")
         _lib = lib
@@ -206,6 +209,13 @@ def kernel_name(prog, N: int, nt: int, nx: int, backward: int) -> str:
     buf = ctypes.create_string_buffer(64)
     check(load().pinn_kernel_name(ctypes.byref(prog.desc), int(N), int(nt), int(nx), int(backward), buf, len(buf)))
     return buf.value.decode("ascii")
+
+
+def u16_tail_plan(N: int, grid: int) -> tuple:
+    """(rounds, groups, first_tail_point) of jet_kernel_u16 on N points and `grid` workgroups (pinn_unit_tail_plan)."""
+    r, g, f = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+    check(load().pinn_unit_tail_plan(int(N), int(grid), ctypes.byref(r), ctypes.byref(g), ctypes.byref(f)))
+    return r.value, g.value, f.value
 
 
 def check(rc: int) -> None:

@@ -91,6 +91,11 @@ struct KernelArgs {
   int det_mask;                             // two-level flush (det_stride < 0): rows - 1, a power of two minus one
   int flush_store;                          // det_stride > 0 only: the end-of-kernel flush writes this workgroup's row with plain
                                             // STORES (every address exactly once; no memset of the slab beforehand)
+  // jet_kernel_u16 only, the plan of jet_u16_tail_plan() (jet_kernel_u16.h): the unit loop runs the units of the points
+  // below u16_loop_points (N, or the whole rounds only); then every workgroup b runs one packed round of u16_tail_groups
+  // (0 = none, 1..3) four-point groups on the points from u16_loop_points + 4 u16_tail_groups b on
+  long long u16_loop_points;
+  int u16_tail_groups;
 };
 
 // Gradient / loss accumulation at the end of a workgroup (or per tile for layers beyond the persistent ones): float

@@ -232,6 +232,121 @@ __device__ __forceinline__ void u16_outer(f32x4 (&pt)[NPT], int na, const float*
   u16_outer_n<K, NMAX, OFF, NPT>(pt, zl, al);
 }
 
+// ---- the packed round (the kernel's last round): a 16-column operand group holds 4 points x 4 streams
+// instead of 16 points x 1 stream.  Column c of group j is (stream c >> 2, point 4j + (c & 3)); the images keep their
+// [stream][point][feature] layout, rows 0 .. 4G-1 in use.  G (1..3) is wave-uniform; every j < G test below is a scalar
+// branch around a block of MFMAs, so accumulator indices stay compile-time. ----
+#ifndef PINN_U16_PACK
+#define PINN_U16_PACK 1  // 0: the unit is compiled without the packed round (csrc/Makefile: it would need scratch)
+#endif
+constexpr int kUPackMax = 3;  // groups of a packed round; four groups are an ordinary unit
+
+// acc[j] += W-slice . column (stream, point 4j + q) over depth 16 NB; xl = X + stream kUImgS + q kUP + 4g.  Blocks, steps
+// and weight prefetch distance of u16_gemm_n: every column sums in the order it has in a full unit.
+template <int NB, bool COLS>
+__device__ __forceinline__ void u16p_gemm_n(f32x4 (&acc)[kUPackMax], int G, const float* W, int ld, unsigned off, f32x4 w0, f32x4 w1, const float* xl) {
+  f32x4 wq[3];
+  wq[0] = w0;
+  wq[1] = w1;
+  f32x4 bc[kUPackMax], bn[kUPackMax];
+#pragma unroll
+  for (int j = 0; j < kUPackMax; ++j) {
+    bc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    bn[j] = bc[j];
+    if (j < G) bc[j] = *reinterpret_cast<const f32x4*>(xl + 4 * j * kUP);
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    if (b + 2 < NB) wq[(b + 2) % 3] = u16_wload<COLS>(W, ld, off, b + 2);
+    if (b + 1 < NB) {
+#pragma unroll
+      for (int j = 0; j < kUPackMax; ++j)
+        if (j < G) bn[j] = *reinterpret_cast<const f32x4*>(xl + 4 * j * kUP + 16 * (b + 1));
+    }
+#pragma unroll
+    for (int j = 0; j < kUPackMax; ++j) {
+      if (j < G) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[j] = mfma16(wq[b % 3][m], bc[j][m], acc[j]);
+      }
+    }
+    if (b + 1 < NB) {
+#pragma unroll
+      for (int j = 0; j < kUPackMax; ++j) bc[j] = bn[j];
+    }
+  }
+}
+
+template <bool COLS>
+__device__ __forceinline__ void u16p_gemm(f32x4 (&acc)[kUPackMax], int G, const float* W, int ld, unsigned off, f32x4 w0, f32x4 w1, int nb, const float* xl) {
+  switch (nb) {
+    case 8: u16p_gemm_n<8, COLS>(acc, G, W, ld, off, w0, w1, xl); return;
+    case 4: u16p_gemm_n<4, COLS>(acc, G, W, ld, off, w0, w1, xl); return;
+    default: break;
+  }
+#pragma unroll 1
+  for (int b = 0; b < nb; ++b) {
+    const f32x4 w = b == 0 ? w0 : b == 1 ? w1 : u16_wload<COLS>(W, ld, off, b);
+#pragma unroll
+    for (int j = 0; j < kUPackMax; ++j) {
+      if (j < G) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[j] = mfma16(w[m], xl[4 * j * kUP + 16 * b + m], acc[j]);
+      }
+    }
+  }
+}
+
+// u16_outer_n on the packed round: the MFMA k index is (stream, point of the group).  Per group K steps, step = stream;
+// lane group g supplies point 4j + g: zl = Z + g kUP + 16w + c, al = A + g kUP + c
+template <int K, int NA, int OFF, int NPT>
+__device__ __forceinline__ void u16p_outer_n(f32x4 (&pt)[NPT], int G, const float* zl, const float* al) {
+#pragma unroll
+  for (int j = 0; j < kUPackMax; ++j) {
+    if (j < G) {
+      float zc, zn = 0.0f, ac[NA], an[NA];
+      zc = zl[4 * j * kUP];
+#pragma unroll
+      for (int t = 0; t < NA; ++t) {
+        ac[t] = al[4 * j * kUP + 16 * t];
+        an[t] = 0.0f;
+      }
+#pragma unroll
+      for (int s = 0; s < K; ++s) {
+        if (s + 1 < K) {
+          zn = zl[(s + 1) * kUImgS + 4 * j * kUP];
+#pragma unroll
+          for (int t = 0; t < NA; ++t) an[t] = al[(s + 1) * kUImgS + 4 * j * kUP + 16 * t];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < NA; ++t) pt[OFF + t] = mfma16(zc, ac[t], pt[OFF + t]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + 1 < K) {
+          zc = zn;
+#pragma unroll
+          for (int t = 0; t < NA; ++t) ac[t] = an[t];
+        }
+      }
+    }
+  }
+}
+
+template <int K, int OFF, int NMAX, int NPT>
+__device__ __forceinline__ void u16p_outer(f32x4 (&pt)[NPT], int G, int na, const float* zl, const float* al) {
+  if constexpr (NMAX >= 8) {
+    if (na * 2 == NMAX) { u16p_outer_n<K, NMAX / 2, OFF, NPT>(pt, G, zl, al); return; }
+  }
+  u16p_outer_n<K, NMAX, OFF, NPT>(pt, G, zl, al);
+}
+
+// the writes of this wave's lanes to LDS are ordered before the reads that follow (rows of the wave's own)
+__device__ __forceinline__ void u16_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // forward activation jets of the accumulator (rows 16w + 4g + r, point c); rec gets the tape record
 template <int ACT, int NT, int NX>
 __device__ __forceinline__ void u16_ew_forward(f32x4 (&v)[1 + NT + NX], float w, f32x4 (&rec)[1 + NT + NX]) {
@@ -319,6 +434,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   float* pdwl = pl + (kPersist + kMaxDin + 1) * kUH;  // kUThreads * 4: per-lane partial dw_out (reverse launches; no
                                                       // VGPRs to spare for a running sum that B0 alone touches)
   float* psl = pdwl + 4 * kUThreads;  // 2 * kU: running loss and db_out sums of the writer lanes (tid < kU), same reason
+  float* xint = psl + 2 * kU;         // kMaxDin * kU: coordinates of the packed round's points (fetched at kernel start)
 
   PINN_STAMP_DECL
   const int tid = threadIdx.x;
@@ -327,7 +443,14 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   const int g = lane >> 4, c = lane & 15;
   const int din = net.din;
   const int nl = net.n_layers;
-  const long long nunits = (a.N + kU - 1) / kU;
+  // The unit loop's points: a.N, or the whole rounds only when a packed round follows (every unit of the loop is then
+  // full).  The loop knows no other point count: one more scalar held across it costs the reverse kernel scratch.
+#if PINN_U16_PACK
+  const long long NL = a.u16_loop_points;
+#else
+  const long long NL = a.N;
+#endif
+  const long long nunits = (NL + kU - 1) / kU;
   const int frow = 16 * wv + 4 * g;  // first of this lane's four accumulator rows
   const int ioff = c * kUP + frow;   // this lane's 16-byte word of an image (point c, rows frow .. frow+3)
 
@@ -364,7 +487,18 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   auto fetch_coords = [&](long long u) {
     if (tid < kU) {
       const long long p = u * kU + tid;
-      const bool ok = u < nunits && p < a.N;
+      const bool ok = u < nunits && p < NL;
+#pragma unroll
+      for (int cc = 0; cc < kMaxDin; ++cc) {
+        if (cc < din - 1) xr[cc] = ok ? a.x[p * (din - 1) + cc] : 0.0f;
+        if (cc == din - 1) xr[cc] = ok ? a.t[p] : 0.0f;
+      }
+    }
+  };
+  auto fetch_coords_at = [&](long long p0, int npts) {  // points p0 .. p0 + npts - 1 (npts <= kU)
+    if (tid < kU) {
+      const long long p = p0 + tid;
+      const bool ok = tid < npts && p < a.N;
 #pragma unroll
       for (int cc = 0; cc < kMaxDin; ++cc) {
         if (cc < din - 1) xr[cc] = ok ? a.x[p * (din - 1) + cc] : 0.0f;
@@ -378,6 +512,12 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       for (int cc = 0; cc < kMaxDin; ++cc) dst[cc * kU + tid] = xr[cc];
     }
   };
+#if PINN_U16_PACK
+  if (a.u16_tail_groups > 0) {  // the packed round's coordinates: visible long before the round's first barrier
+    fetch_coords_at(a.u16_loop_points + 4LL * a.u16_tail_groups * blockIdx.x, 4 * a.u16_tail_groups);
+    put_coords(xint);
+  }
+#endif
   fetch_coords(blockIdx.x);
   put_coords(xin2);
   int xpar = 0;
@@ -468,7 +608,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     float ub[K];
     {
       const long long p = p0 + c;
-      const bool ok = p < a.N;
+      const bool ok = p < NL;
       const bool writer = tid < kU;
       float j[K];
 #pragma unroll
@@ -665,6 +805,368 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     }
   }
 
+#if PINN_U16_PACK
+  // ---- the packed round: G = a.u16_tail_groups groups of 4 points x K streams (top of the file), on the points whose
+  // coordinates were fetched into xint at kernel start.  The phases, images and barriers of a unit; the GEMMs work on
+  // (stream, point) columns and the element-wise phases on points, so between the two a wave passes its accumulators
+  // through its own columns of an image: lane (g, c) stores rows 16w + 4g .. + 3 of column c and loads them back for point
+  // 4j + (c & 3), all streams.  The four lanes c >> 2 = 0 .. 3 of a point then run the unit's element-wise code on
+  // the same values and store the same words.  Nothing here is live across the unit loop besides pt[] and the
+  // running sums in LDS: addresses come from an opaque copy of the thread index.
+  if (a.u16_tail_groups > 0) {
+    const int G = a.u16_tail_groups;
+    const int tp = u16_opaque(tid);
+    const int gp = (tp & 63) >> 4, cp = tp & 15;
+    const int sp = cp >> 2, qp = cp & 3;       // stream and point-in-group of this lane's MFMA column
+    const int frowp = 16 * wv + 4 * gp;
+    const int boff = (sp < K ? sp : 0) * kUImgS + qp * kUP + 4 * gp;  // B operand of group 0, block 0 (K < 4: idle columns repeat stream 0)
+    const int woff = sp * kUImgS + qp * kUP + frowp;                  // this lane's accumulator word of group 0
+    const int eoff = qp * kUP + frowp;                                // element-wise word of group 0 (point qp, rows frowp .. + 3)
+    const bool wcol = sp < K;
+    const bool writer = tp < 4;  // owns point 4j + tp of every group
+    const long long tail_p0 = a.u16_loop_points + 4LL * G * blockIdx.x;
+    auto acc_put = [&](float* im, const f32x4 (&pa)[kUPackMax]) {
+#pragma unroll
+      for (int j = 0; j < kUPackMax; ++j)
+        if (j < G && wcol) *reinterpret_cast<f32x4*>(im + woff + 4 * j * kUP) = pa[j];
+      u16_wave_sync();
+    };
+
+    // the last unit's readers of X / A2 / UP are done; the round's coordinates are visible
+    U16_BARRIER(ST_BWD_FLUSH);
+    const float* xin = xint;
+    f32x4 w0, w1;
+    {
+      const LayerDev L0 = uniform_layer(net.layer[0]);
+      const unsigned off = u16_rows_off(16 * wv < L0.out_dim ? 16 * wv : 0, L0.ld, cp, gp);
+      w0 = u16_wload<false>(L0.W, L0.ld, off, 0);
+      w1 = u16_wload<false>(L0.W, L0.ld, off, L0.in_dim > 16 ? 1 : 0);
+    }
+    PINN_STAMP(ST_STAGE);
+    float* src = (nl & 1) ? X : A2;
+    float* dst = (nl & 1) ? A2 : X;
+    u16_encode<ACT, NT, NX>(net, ep, xin, src, tp);
+    U16_BARRIER(ST_ENCODE);
+
+    // ---- hidden layers; the last one leaves its output-layer partials in UP ----
+    for (int l = 0; l < nl; ++l) {
+      const LayerDev Ly = uniform_layer(net.layer[l]);
+      const bool on = 16 * wv < Ly.out_dim;
+      const bool last = l + 1 == nl;
+      f32x4 pa[kUPackMax];
+#pragma unroll
+      for (int j = 0; j < kUPackMax; ++j) pa[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (on) u16p_gemm<false>(pa, G, Ly.W, Ly.ld, u16_rows_off(16 * wv, Ly.ld, cp, gp), w0, w1, Ly.in_dim >> 4, src + boff);
+      PINN_STAMP(ST_FWD_GEMM);
+      if (!last) {
+        const LayerDev Ln = uniform_layer(net.layer[l + 1]);
+        const unsigned off = u16_rows_off(16 * wv < Ln.out_dim ? 16 * wv : 0, Ln.ld, cp, gp);
+        w0 = u16_wload<false>(Ln.W, Ln.ld, off, 0);
+        w1 = u16_wload<false>(Ln.W, Ln.ld, off, Ln.in_dim > 16 ? 1 : 0);
+      }
+      // dst (the last layer: A2) was last read a barrier ago; its columns 16w .. 16w+15 are this wave's until the next one
+      if (on) acc_put(dst, pa);
+      const f32x4 bias = *reinterpret_cast<const f32x4*>(wb + (1 + l) * kUH + frowp);
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(wb + frowp);
+#pragma unroll
+      for (int j = 0; j < kUPackMax; ++j) {
+        if (j < G) {
+          // The two branches repeat the unit's: the jets of a layer stand in the code once with the record and image
+          // stores behind them and once with the record store and the output layer behind them, so the compiler pairs
+          // and contracts their arithmetic as it does there, and a point's jets round as in a unit.
+          f32x4 v[K];
+#pragma unroll
+          for (int s = 0; s < K; ++s) v[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          if (!last) {
+            if (on) {
+              u16_get<K>(dst + eoff + 4 * j * kUP, v);
+              v[0] += bias;
+              f32x4 rec[K];
+              u16_ew_forward<ACT, NT, NX>(v, Ly.act_param, rec);
+              if constexpr (BWD) u16_put<K>(REC + l * img + eoff + 4 * j * kUP, rec);
+              u16_put<K>(dst + eoff + 4 * j * kUP, v);
+            }
+          } else if (on) {
+            u16_get<K>(dst + eoff + 4 * j * kUP, v);
+            v[0] += bias;
+            f32x4 rec[K];
+            u16_ew_forward<ACT, NT, NX>(v, Ly.act_param, rec);
+            if constexpr (BWD) u16_put<K>(A2 + eoff + 4 * j * kUP, rec);  // parked record
+          }
+          if (last) {  // output layer (H_last -> 1): the unit's reduction order
+            float po[K];
+#pragma unroll
+            for (int s = 0; s < K; ++s) {
+              po[s] = fmaf(w4[0], v[s][0], fmaf(w4[1], v[s][1], fmaf(w4[2], v[s][2], w4[3] * v[s][3])));
+              po[s] += __shfl_xor(po[s], 16);
+              po[s] += __shfl_xor(po[s], 32);
+            }
+            if (gp == 0 && sp == 0) {
+#pragma unroll
+              for (int s = 0; s < K; ++s) UP[(wv * K + s) * kU + 4 * j + qp] = po[s];
+            }
+          }
+        }
+      }
+      if (!last) {
+        U16_BARRIER(ST_FWD_EW);
+        float* const t = src;
+        src = dst;
+        dst = t;
+      }
+    }
+    U16_BARRIER(ST_OUT);
+
+    // ---- epilogue and B0, group by group: by every lane for point 4 jg + qp.  One loop, not unrolled: the epilogue
+    // stands in the code once, followed by B0 or by nothing, as it does in a unit.  The adjoint of a group waits for
+    // the next barrier in this wave's own columns of an image nobody else reads (park), not in registers: first where
+    // the parked record was ----
+    [[maybe_unused]] const float* park = A2;
+#pragma unroll 1
+    for (int jg = 0; jg < G; ++jg) {
+      float ub[K];
+      const int pp = 4 * jg + qp;
+      {
+        const long long p = tail_p0 + pp;
+        const bool ok = p < a.N;
+        float j[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+          float v = s == 0 ? b_out0 : 0.0f;
+#pragma unroll
+          for (int w = 0; w < kUWaves; ++w) v += UP[(w * K + s) * kU + pp];
+          j[s] = v;
+        }
+        if (a.mode == MODE_JETS) {
+#pragma unroll
+          for (int s = 0; s < K; ++s) {
+            if (writer && ok && a.jets_out[s]) a.jets_out[s][p] = j[s];
+            ub[s] = (BWD && ok && a.jets_bar[s]) ? a.jets_bar[s][p] : 0.0f;
+          }
+        } else {
+          float d[K];
+          PdeDev pde = a.pde;
+          pde.c0 = X[0 * kUP + kUH + 2];
+          pde.c1 = X[1 * kUP + kUH + 2];
+          pde.c2 = X[2 * kUP + kUH + 2];
+          pde.c3 = X[3 * kUP + kUH + 2];
+          const float r = pde_residual<NT, NX>(pde, j, xin[pp], d);
+          float dl;
+          float lt = loss_term(pde, r, &dl);
+          if (!ok) {
+            lt = 0.0f;
+            dl = 0.0f;
+          }
+          if (writer && ok && a.residual_out) a.residual_out[p] = r;
+          if (writer) psl[pp] += lt;
+          const float rb = !BWD ? 0.0f : a.res_bar ? (ok ? a.res_bar[p] : 0.0f) : a.grad_scale * dl;
+#pragma unroll
+          for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
+          if constexpr (COEF) {
+            float dc0, dc1;
+            pde_coef_grads<NT, NX>(pde, j, xin[pp], dc0, dc1);
+            if (writer) {
+              X[pp * kUP + kUH] += rb * dc0;
+              X[pp * kUP + kUH + 1] += rb * dc1;
+            }
+          }
+        }
+      }
+      PINN_STAMP(ST_EPI);
+      if constexpr (!BWD) continue;
+      // ---- B0 ----
+      if (writer) psl[kU + pp] += ub[0];
+      f32x4 ab[K];
+      {
+        const LayerDev Lz = uniform_layer(net.layer[nl - 1]);
+        const f32x4 w4 = *reinterpret_cast<const f32x4*>(wb + frowp);
+#pragma unroll
+        for (int s = 0; s < K; ++s) ab[s] = w4 * ub[s];
+        if (16 * wv < Lz.out_dim) {
+          f32x4 rec[K];
+          float* const rp = A2 + eoff + 4 * jg * kUP;
+          u16_get<K>(rp, rec);
+          if (sp == 0) {  // one of the point's four lanes adds its dw_out terms
+            float* const pdwp = pdwl + 4 * tp;
+            f32x4 pdw = *reinterpret_cast<const f32x4*>(pdwp);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float z[K], y[K];
+#pragma unroll
+              for (int s = 0; s < K; ++s) z[s] = rec[s][r];
+              act_fwd_tape<ACT, NT, NX>(Lz.act_param, z, y);
+              float gg = 0.0f;
+#pragma unroll
+              for (int s = 0; s < K; ++s) gg = fmaf(ub[s], y[s], gg);
+              pdw[r] += gg;
+            }
+            *reinterpret_cast<f32x4*>(pdwp) = pdw;
+          }
+          u16_ew_backward<ACT, NT, NX>(ab, Lz.act_param, rec);
+          u16_put<K>(rp, ab);
+        }
+      }
+      PINN_STAMP(ST_B0);
+    }
+
+    if constexpr (BWD) {
+      for (int l = nl - 1; l >= 0; --l) {
+        const LayerDev Ly = uniform_layer(net.layer[l]);
+        const bool on = 16 * wv < Ly.out_dim;
+        const bool need_abar = l > 0 || net.enc == ENC_LINEAR;
+        const bool kon = 16 * wv < Ly.in_dim;
+        // zbar_l goes from where it was parked into this wave's columns of X.  The last layer's (the first here) was
+        // parked in A2 and X's columns have been free since the output layer's barrier, so it moves BEFORE the barrier
+        // below: with a single MFMA layer that barrier is all that keeps u16_encode (every column of A2, below) of a wave
+        // that is ahead from overwriting the parked adjoint of a wave that is behind.  The other layers' X is read by
+        // the GEMMs of layer l+1 up to the barrier, so theirs moves after it.
+        auto unpark = [&]() {
+#pragma unroll
+          for (int j = 0; j < kUPackMax; ++j) {
+            if (j < G && on) {
+              f32x4 zb[K];
+              u16_get<K>(park + eoff + 4 * j * kUP, zb);
+              u16_put<K>(X + eoff + 4 * j * kUP, zb);
+            }
+          }
+        };
+        const bool top = l + 1 == nl;
+        if (top) unpark();
+        if (!top || nl == 1) U16_BARRIER(ST_BWD_EW);
+        if (!top) unpark();
+        float pw = 0.0f;
+        u16_wave_sync();  // this wave's parked words are read before its replay below overwrites them (top layer: A2)
+        if (l > 0) {
+          const LayerDev P = uniform_layer(net.layer[l - 1]);
+          pw = P.act_param;
+          if (kon) {  // replay a_{l-1} into this wave's columns of A2
+#pragma unroll
+            for (int j = 0; j < kUPackMax; ++j) {
+              if (j < G) {
+                f32x4 rec[K], y[K];
+                u16_get<K>(REC + (l - 1) * img + eoff + 4 * j * kUP, rec);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  float z[K], yy[K];
+#pragma unroll
+                  for (int s = 0; s < K; ++s) z[s] = rec[s][r];
+                  act_fwd_tape<ACT, NT, NX>(pw, z, yy);
+#pragma unroll
+                  for (int s = 0; s < K; ++s) y[s][r] = yy[s];
+                }
+                u16_put<K>(A2 + eoff + 4 * j * kUP, y);
+              }
+            }
+          }
+        } else {
+          u16_encode<ACT, NT, NX>(net, ep, xin, A2, tp);
+        }
+        const unsigned coff = u16_cols_off(kon ? 16 * wv : 0, Ly.ld, cp, gp);
+        if (need_abar) {
+          w0 = u16_wload<true>(Ly.W, Ly.ld, coff, 0);
+          w1 = u16_wload<true>(Ly.W, Ly.ld, coff, 1);
+        }
+        U16_BARRIER(ST_BWD_PUT);
+        if (Ly.db && tp < Ly.out_dim) {
+          float gsum = 0.0f;
+          for (int n = 0; n < 4 * G; ++n) gsum += X[n * kUP + tp];
+          pl[l * kUH + tp] += gsum;
+        }
+        PINN_STAMP(ST_BWD_DB);
+        // abar_{l-1} = W^T zbar, then the activation adjoint of layer l-1.  The accumulators go through the wave's own
+        // columns of the record image of layer l-1 (l = 0: of layer 0), which nothing reads any more: the replay above
+        // was its last reader but for the adjoint below, which takes the record into registers first.
+        if (need_abar) {
+          f32x4 pa[kUPackMax];
+#pragma unroll
+          for (int j = 0; j < kUPackMax; ++j) pa[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          if (kon) u16p_gemm<true>(pa, G, Ly.W, Ly.ld, coff, w0, w1, Ly.out_dim >> 4, X + boff);
+          PINN_STAMP(ST_BWD_DX);
+          float* const xch = REC + (l > 0 ? l - 1 : 0) * img;
+#pragma unroll
+          for (int j = 0; j < kUPackMax; ++j) {
+            if (j < G) {
+              // l = 0 (first Linear as the encoding): abar stays where the accumulators put it; the encoding backward
+              // reads it there after a workgroup barrier
+              f32x4 rec[K];
+              if (l > 0) {
+                if (kon) u16_get<K>(xch + eoff + 4 * j * kUP, rec);
+                u16_wave_sync();
+              }
+              if (kon && wcol) *reinterpret_cast<f32x4*>(xch + woff + 4 * j * kUP) = pa[j];
+              if (l > 0) {
+                u16_wave_sync();
+                if (kon) {
+                  f32x4 ab[K];
+                  u16_get<K>(xch + eoff + 4 * j * kUP, ab);
+                  u16_ew_backward<ACT, NT, NX>(ab, pw, rec);
+                  u16_put<K>(xch + eoff + 4 * j * kUP, ab);
+                }
+              }
+            }
+          }
+          park = xch;
+          PINN_STAMP(ST_BWD_EW);
+        }
+        if (on && Ly.dW) {
+          const float* zl = X + gp * kUP + 16 * wv + cp;
+          const float* al = A2 + gp * kUP + cp;
+          const int na = Ly.in_dim >> 4;
+          if (l == 0) u16p_outer<K, 0, NA0, NPT>(pt, G, na, zl, al);
+          else if (l == 1) u16p_outer<K, NA0, NKT, NPT>(pt, G, na, zl, al);
+          else u16p_outer<K, NA0 + NKT, NKT, NPT>(pt, G, na, zl, al);
+        }
+        PINN_STAMP(ST_BWD_STREAM);
+      }
+
+      // ---- encoding backward (first Linear of feedforward / SIREN) ----
+      if (net.enc == ENC_LINEAR && net.d_encW) {
+        const int H = net.enc_out;
+        U16_BARRIER(ST_ENC_BWD);
+        if (16 * wv < H) {
+#pragma unroll
+          for (int j = 0; j < kUPackMax; ++j) {
+            if (j < G) {
+              f32x4 ab[K];
+              u16_get<K>(park + eoff + 4 * j * kUP, ab);  // abar of the encoding's outputs, left there by layer 0
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                float z[K], abv[K], zb[K];
+                u16_enc_preact<NT, NX>(ep, din, xin, frowp + r, 4 * j + qp, z);
+#pragma unroll
+                for (int s = 0; s < K; ++s) abv[s] = ab[s][r];
+                act_bwd<ACT, NT, NX>(net.enc_param, z, abv, zb);
+#pragma unroll
+                for (int s = 0; s < K; ++s) ab[s][r] = zb[s];
+              }
+              u16_put<K>(X + eoff + 4 * j * kUP, ab);
+            }
+          }
+        }
+        U16_BARRIER(ST_ENC_BWD);
+        if (tp < H) {
+          float gb = 0.0f, gt = 0.0f, gx = 0.0f;
+          float gw[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
+          for (int n = 0; n < 4 * G; ++n) {
+            const float vv = X[n * kUP + tp];
+            gb += vv;
+#pragma unroll
+            for (int cc = 0; cc < kMaxDin; ++cc)
+              if (cc < din) gw[cc] = fmaf(vv, xin[cc * kU + n], gw[cc]);
+            if constexpr (NT >= 1) gt += X[1 * kUImgS + n * kUP + tp];
+            if constexpr (NX >= 1) gx += X[(1 + NT) * kUImgS + n * kUP + tp];
+          }
+#pragma unroll
+          for (int cc = 0; cc < kMaxDin; ++cc) pl[(kPersist + cc) * kUH + tp] += gw[cc] + (cc == din - 1 ? gt : 0.0f) + (cc == 0 ? gx : 0.0f);
+          pl[(kPersist + kMaxDin) * kUH + tp] += gb;
+        }
+        PINN_STAMP(ST_ENC_BWD);
+      }
+    }
+    __syncthreads();  // the round's writers of the running sums (psl, the COEF slots) are not the flush's readers
+  }
+#endif
+
   // ---- one flush per workgroup: reverse launches store into row blockIdx.x of the slab (a.flush_store: every address
   // written once); a forward-only launch adds its loss sum as the 32-point kernel does ----
   // The flush addresses are derived from an opaque copy of the thread index: computed from tid itself they are
@@ -742,9 +1244,36 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
 #endif
 }
 
+// The launch plan (host).  With grid workgroups, R = N / (16 grid) full rounds of 16-point units and M = N - 16 grid R
+// points left, G = ceil(M / (4 grid)) <= 4 four-point groups per workgroup hold them.  G = 1..3 (and a unit compiled with
+// the packed round): every workgroup runs its R units and then one packed round of G groups, workgroup b on the (at most
+// 4 G) points from first_tail + 4 G b on.  G = 0: nothing is left.  G = 4: the last round is ordinary units.
+struct U16Plan {
+  long long rounds;      // R
+  long long first_tail;  // 16 grid R
+  int groups;            // G
+};
+inline U16Plan jet_u16_tail_plan(long long N, int grid, bool packed) {
+  U16Plan p;
+  const long long per_round = (long long)kU * grid;
+  p.rounds = N / per_round;
+  p.first_tail = p.rounds * per_round;
+  const long long M = N - p.first_tail;
+  p.groups = (int)((M + 4LL * grid - 1) / (4LL * grid));
+  if (!packed && p.groups > 0) p.groups = 4;
+  return p;
+}
+// the plan as the kernel reads it
+inline void jet_u16_set_plan(KernelArgs& a, int grid, bool packed) {
+  const U16Plan p = jet_u16_tail_plan(a.N, grid, packed);
+  const bool pack = p.groups >= 1 && p.groups <= kUPackMax;
+  a.u16_loop_points = pack ? p.first_tail : a.N;
+  a.u16_tail_groups = pack ? p.groups : 0;
+}
+
 inline size_t jet_u16_lds_bytes(int K) {
   return sizeof(float) * ((size_t)4 * K * kUImgS + kUWaves * K * kU + 2 * kMaxDin * kU + (1 + kPersist) * kUH +
-                          (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH + 4 * kUThreads + 2 * kU);
+                          (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH + 4 * kUThreads + 2 * kU + kMaxDin * kU);
 }
 
 

@@ -391,6 +391,14 @@ static bool use_u16(const PinnNetDesc* d, const NetDev& n, int nt, int nx, bool 
   return strstr(pinn_build_info(), unit) == nullptr;
 }
 
+// The unit of this launch carries the packed round (jet_kernel_u16.h).  A unit that would need scratch with it is built
+// without (csrc/Makefile) and listed in pinn_build_info() as "nopack jet_u16..."; its last round stays ordinary units.
+static bool u16_unit_packed(const NetDev& n, int nt, int nx, bool coef) {
+  char unit[64];
+  snprintf(unit, sizeof(unit), coef ? "nopack jet_u16c_%d_%d_%d " : "nopack jet_u16_%d_%d_%d ", nt, nx, jet_wide_act_family(n));
+  return strstr(pinn_build_info(), unit) == nullptr;
+}
+
 // reverse launch of a COEF unit: the 16-point kernel (u16) or the 32-point one
 static hipError_t dispatch_coef(bool u16, int nt, int nx, const KernelArgs& a, int grid, hipStream_t st) {
 #ifndef PINN_DEV
@@ -563,6 +571,7 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
         if (em != hipSuccess) return fail(PINN_ERR_HIP, "HIP error %d: %s", (int)em, hipGetErrorString(em));
       }
     }
+    if (u16) jet_u16_set_plan(a, grid, u16_unit_packed(a.net, nt, nx, inverse));
     hipError_t e = inverse ? dispatch_coef(u16, nt, nx, a, grid, static_cast<hipStream_t>(stream))
                    : u16   ? dispatch_u16(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream))
                            : dispatch_wide(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream));
@@ -725,6 +734,15 @@ int pinn_kernel_name(const PinnNetDesc* net, int64_t N, int32_t time_order, int3
     name = use_u16(net, n, time_order, space_order, backward == 1) ? "jet_kernel_u16" : "jet_kernel_wide";
   }
   snprintf(buf, len, "%s", name);
+  return PINN_OK;
+}
+
+int pinn_unit_tail_plan(int64_t N, int32_t grid, int64_t* rounds, int32_t* groups, int64_t* first_tail_point) {
+  if (N < 0 || grid < 1) return fail(PINN_ERR_BAD_DESC, "pinn_unit_tail_plan: N = %lld, grid = %d", (long long)N, (int)grid);
+  const U16Plan p = jet_u16_tail_plan(N, grid, true);
+  if (rounds) *rounds = p.rounds;
+  if (groups) *groups = p.groups;
+  if (first_tail_point) *first_tail_point = p.first_tail;
   return PINN_OK;
 }
 
