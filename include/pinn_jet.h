@@ -48,7 +48,7 @@ extern "C" {
 #define PINN_MAX_STREAMS 7 /* value + up to 2 time + up to 4 space derivatives */
 
 /* PinnNetDesc.flags */
-#define PINN_FLAG_LAYER_NORM 1    /* feedforward: a LayerNorm follows every hidden Linear (feedforward.py:43-45) */
+#define PINN_FLAG_LAYER_NORM 1    /* feedforward, autoencoder: a LayerNorm follows every hidden Linear (feedforward.py:43-45) */
 #define PINN_FLAG_DETERMINISTIC 2 /* weight gradients (and, on calls WITH a reverse sweep, the loss sum) reduced in a fixed
                                      order: two launches on the same inputs give bit-identical results (reference anchor:
                                      tests/unit_tests/test_benchmarks.py:61-64).  Both engines: per-workgroup slab rows +
@@ -76,7 +76,15 @@ typedef enum PinnArch {
   PINN_ARCH_FOURIER = 1,     /* fourier.py:65-124 */
   PINN_ARCH_SIREN = 2,       /* siren.py:49-90 */
   PINN_ARCH_RESNET = 3,      /* resnet.py:68-142 */
-  PINN_ARCH_ATTENTION = 4    /* attention.py:110-183 (sequence length 1 => an MLP with LayerNorm) */
+  PINN_ARCH_ATTENTION = 4,   /* attention.py:110-183 (sequence length 1 => an MLP with LayerNorm) */
+  PINN_ARCH_AUTOENCODER = 5  /* autoencoder.py:9-100.  With n = len(hidden_dims) >= 1: num_blocks = n, num_linear = 2 n + 2,
+                                widths = [h_1 .. h_n, latent_dim, h_n .. h_1, 1], activation = the hidden activation,
+                                PINN_FLAG_LAYER_NORM as for feedforward.  Tensors in state_dict order: encoder.{0, 3, ..}
+                                (with LayerNorm: each Linear followed by its LayerNorm at +1; without: Linears at 0, 2, ..),
+                                the latent Linear, the decoder the same way, the output Linear last: 8 n + 4 tensors with
+                                LayerNorm, 4 n + 4 without.  Nothing sits between the latent Linear and the first decoder
+                                Linear.  num_linear != 2 num_blocks + 2: PINN_ERR_BAD_DESC; n = 0 (a purely linear model):
+                                PINN_ERR_UNSUPPORTED; PINN_MAX_LINEAR caps n at 11.  Always the layer-major engine. */
 } PinnArch;
 
 typedef enum PinnAct { /* base_network.py:91-104, plus SIREN's sin(omega_0 z) */
@@ -113,7 +121,7 @@ typedef struct PinnNetDesc {
   int32_t mapping_size;            /* fourier: columns of B (features = 2 * mapping_size) */
   float act_param;                 /* omega_0 for PINN_ACT_SIN */
   float ln_eps;                    /* LayerNorm epsilon (resnet / attention) */
-  int32_t num_blocks;              /* resnet blocks / attention layers */
+  int32_t num_blocks;              /* resnet blocks / attention layers / autoencoder hidden layers per side */
   int32_t flags;                   /* PINN_FLAG_* */
 } PinnNetDesc;
 

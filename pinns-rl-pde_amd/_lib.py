@@ -19,7 +19,7 @@ PINN_FLAG_DETERMINISTIC = 2
 PINN_FLAG_LAYER_MAJOR = 4
 PINN_FLAG_WIDE_TILE32 = 8
 
-ARCH = {"feedforward": 0, "fourier": 1, "siren": 2, "resnet": 3, "attention": 4}
+ARCH = {"feedforward": 0, "fourier": 1, "siren": 2, "resnet": 3, "attention": 4, "autoencoder": 5}
 ACT = {"tanh": 0, "sin": 1, "gelu": 2, "sigmoid": 3, "relu": 4, "leaky_relu": 5, "identity": 6}
 PDE = {
     "burgers": 0, "heat": 1, "allen_cahn": 2, "kdv": 3, "cahn_hilliard": 4, "wave": 5, "convection": 6,

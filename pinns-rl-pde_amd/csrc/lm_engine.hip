@@ -238,6 +238,7 @@ int expected_tensors(const PinnNetDesc* d) {
     case PINN_ARCH_SIREN: return 2 * d->num_linear;
     case PINN_ARCH_RESNET: return 4 + 8 * d->num_blocks;
     case PINN_ARCH_ATTENTION: return 4 + 16 * d->num_blocks;
+    case PINN_ARCH_AUTOENCODER: return ((d->flags & PINN_FLAG_LAYER_NORM) ? 8 : 4) * (d->num_blocks > 0 ? d->num_blocks : 0) + 4;
     default: return -1;
   }
 }
@@ -426,6 +427,65 @@ int build_program(const PinnNetDesc* d, Program& P, char* err, size_t en) {
     P.head.H = H;
     P.w_out = 2 + 16 * nl;
     P.b_out = P.w_out + 1;
+  } else if (d->arch == PINN_ARCH_AUTOENCODER) {
+    // encoder: n x (Linear, [LayerNorm], act), Linear -> latent;  decoder: n x (Linear, [LayerNorm], act), Linear -> 1.
+    // Nothing sits between the latent Linear and the first decoder Linear: that node's prologue is the identity, its V
+    // record IS the latent node's Y record (make_layout) and no element-wise launch runs for it in either sweep.
+    const int n = d->num_blocks;
+    if (n < 0 || d->num_linear != 2 * n + 2) return failf(err, en, PINN_ERR_BAD_DESC, "autoencoder: num_blocks=%d / num_linear=%d (want 2 * num_blocks + 2)", n, d->num_linear);
+    if (n < 1) return failf(err, en, PINN_ERR_UNSUPPORTED, "autoencoder: hidden_dims is empty, which makes the network purely linear (no hidden prologue to run)");
+    const bool ln = (d->flags & PINN_FLAG_LAYER_NORM) != 0;
+    const int step = ln ? 4 : 2;
+    for (int i = 0; i <= 2 * n; ++i)
+      if (!check_w(d->widths[i])) return failf(err, en, PINN_ERR_UNSUPPORTED, "%s width %d outside [1,1024]", i == n ? "latent" : "hidden", d->widths[i]);
+    use_tensor(P, 0, d->widths[0], d->input_dim, true);
+    use_tensor(P, 1, 1, d->widths[0]);
+    Prologue pro;
+    pro.src_kind = SRC_COORDS_LINEAR;
+    pro.enc_w = 0;
+    pro.enc_b = 1;
+    pro.act = act;
+    pro.act_param = par;
+    if (ln) {
+      pro.ln_g = 2;
+      pro.ln_b = 3;
+      use_tensor(P, 2, 1, d->widths[0]);
+      use_tensor(P, 3, 1, d->widths[0]);
+    }
+    auto hidden_after = [&](int m, int lin, int wd) {  // [LayerNorm] + activation of node m, whose Linear is tensor `lin`
+      Prologue q;
+      q.src_node = m;
+      q.act = act;
+      q.act_param = par;
+      if (ln) {
+        q.ln_g = lin + 2;
+        q.ln_b = lin + 3;
+        use_tensor(P, q.ln_g, 1, wd);
+        use_tensor(P, q.ln_b, 1, wd);
+      }
+      return q;
+    };
+    int prev = d->widths[0];
+    for (int i = 1; i < n; ++i) {  // encoder Linears 2 .. n
+      const int m = add_node(pro, step * i, step * i + 1, prev, d->widths[i], -1);
+      pro = hidden_after(m, step * i, d->widths[i]);
+      prev = d->widths[i];
+    }
+    const int latent = add_node(pro, step * n, step * n + 1, prev, d->widths[n], -1);
+    pro = Prologue();  // identity: the first decoder Linear reads the latent record as it is
+    pro.src_node = latent;
+    prev = d->widths[n];
+    const int base = step * n + 2;
+    for (int j = 0; j < n; ++j) {  // decoder Linears 1 .. n
+      const int wd = d->widths[n + 1 + j];
+      const int m = add_node(pro, base + step * j, base + step * j + 1, prev, wd, -1);
+      pro = hidden_after(m, base + step * j, wd);
+      prev = wd;
+    }
+    P.head = pro;
+    P.head.H = prev;
+    P.w_out = base + step * n;
+    P.b_out = P.w_out + 1;
   } else {
     return failf(err, en, PINN_ERR_UNSUPPORTED, "architecture id %d has no kernel", d->arch);
   }
@@ -499,11 +559,18 @@ void plan_fusion(Program& P, int nt, int nx) {
     const Node& nd = P.node[m];
     const Prologue& cp = consumer_of(P, m);
     const int lnm = fused_ln_mask();
-    if (cp.src_kind == SRC_REC && cp.src_node == m && !cp.identity() && cp.H == nd.Hout && !(nd.add_node >= 0 && cp.skip_node >= 0) &&
+    // Identity prologues (the autoencoder's latent record feeding the first decoder Linear) stay on the plain GEMMs on
+    // BOTH sides, by choice: the fused kernels' epilogue always writes a second record (V forward, Zbar of the source in
+    // reverse), and here that record is the very one the GEMM writes (V[m + 1] aliases Y[m], Vbar[m + 1] aliases Zbar[m]).
+    // So the producer of an identity consumer runs lm_gemm forward, and the identity node itself runs lm_gemm in reverse,
+    // which STORES W^T Zbar into the source's Zbar.  The nodes around them fuse as usual.
+    const bool feeds_identity = cp.identity();
+    const bool is_identity = nd.pro.identity();
+    if (cp.src_kind == SRC_REC && cp.src_node == m && !feeds_identity && cp.H == nd.Hout && !(nd.add_node >= 0 && cp.skip_node >= 0) &&
         (cp.ln_g < 0 || (lnm & (cp.skip_node >= 0 ? 2 : 1))))
       fuse_shape(nd.Hout, nd.Hin, cp.ln_g >= 0, P.fuse_fwd[m]);
     const Prologue& pro = nd.pro;
-    if (pro.src_kind == SRC_REC && !pro.identity() && (pro.ln_g < 0 || (lnm & (round32(nd.Hout) <= 128 ? 4 : 8))))
+    if (pro.src_kind == SRC_REC && !is_identity && (pro.ln_g < 0 || (lnm & (round32(nd.Hout) <= 128 ? 4 : 8))))
       fuse_shape(nd.Hin, nd.Hout, pro.ln_g >= 0, P.fuse_bwd[m]);
   }
 }

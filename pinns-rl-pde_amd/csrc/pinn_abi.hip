@@ -6,7 +6,8 @@
 //     fourier, siren), hidden widths multiples of 32 up to 128, all K streams of a tile resident in LDS — the
 //     headline Burgers / fourier 4x128 configuration;
 //   * the layer-major engine (lm_*.h): everything else — LayerNorm architectures (ResNet, attention, feedforward with
-//     layer_norm), widths up to 1024 that need not be multiples of 32, any derivative order the ABI admits.
+//     layer_norm), the autoencoder (always: use_wide admits the plain MLP family only), widths up to 1024 that need not
+//     be multiples of 32, any derivative order the ABI admits.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>

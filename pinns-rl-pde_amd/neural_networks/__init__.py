@@ -22,7 +22,7 @@ NetworkConfig = Dict[str, Any]
 __all__ = [
     "BaseNetwork", "InputType", "OutputType", "NetworkConfig", "FeedForwardNetwork", "ResNet", "ResNetBlock",
     "SIREN", "SIRENLayer", "FourierNetwork", "FourierFeatures", "AttentionNetwork", "SelfAttention",
-    "FeedForwardBlock", "PINNModel",
+    "FeedForwardBlock", "AutoEncoder", "PINNModel",
 ]
 
 _ACT_MODULES = {"relu": nn.ReLU, "leaky_relu": nn.LeakyReLU, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid, "gelu": nn.GELU}
@@ -345,6 +345,66 @@ class AttentionNetwork(BaseNetwork):  # attention.py:110-183
                     widths=[self.hidden_dim, self.output_dim], num_blocks=self.num_layers)
 
 
+class AutoEncoder(BaseNetwork):  # autoencoder.py:9-100
+    """encoder: (Linear, [LayerNorm], act) per hidden width, Linear -> latent_dim; decoder: the same over the reversed
+    widths from latent_dim, Linear -> output_dim.  `forward` = decode(encode(x)) runs on the layer-major engine;
+    `encode` / `decode` themselves are the reference's loops over the module lists in plain torch (the latent code has
+    latent_dim outputs, which the engine, whose networks end in one output, does not serve)."""
+
+    def __init__(self, config: NetworkConfig) -> None:
+        super().__init__(config)
+        self.input_dim = config["input_dim"]
+        self.latent_dim = config.get("latent_dim", 16)  # a ModelConfig that never set it yields None: nn.Linear raises, as upstream
+        self.hidden_dims = config.get("hidden_dims", [32, 64])
+        self.activation_name = config.get("activation", "relu")
+        self.dropout_rate = config.get("dropout", 0.0)
+        self.use_layer_norm = config.get("layer_norm", True)
+        self.output_dim = config.get("output_dim", 1)
+        self.encoder = nn.ModuleList()
+        prev = self.input_dim
+        for h in self.hidden_dims:
+            prev = self._append_hidden(self.encoder, prev, h)
+        self.encoder.append(nn.Linear(prev, self.latent_dim))
+        self.decoder = nn.ModuleList()
+        prev = self.latent_dim
+        for h in reversed(self.hidden_dims):
+            prev = self._append_hidden(self.decoder, prev, h)
+        self.decoder.append(nn.Linear(prev, self.output_dim))
+        self.to(self.device)
+
+    def _append_hidden(self, modules: nn.ModuleList, prev: int, h: int) -> int:
+        modules.append(nn.Linear(prev, h))
+        if self.use_layer_norm:
+            modules.append(nn.LayerNorm(h))
+        modules.append(self._get_activation_module(self.activation_name))
+        if self.dropout_rate > 0.0:
+            modules.append(nn.Dropout(self.dropout_rate))
+        return h
+
+    def encode(self, x: InputType) -> torch.Tensor:
+        x = self._prepare_input(x)
+        for layer in self.encoder:
+            x = layer(x)
+        return x
+
+    def decode(self, z: torch.Tensor) -> torch.Tensor:
+        for layer in self.decoder:
+            z = layer(z)
+        return z
+
+    def _program_spec(self):
+        _dropout_guard(self.dropout_rate, "AutoEncoder")
+        hidden = list(self.hidden_dims)
+        if not hidden:
+            raise NotImplementedError(
+                "AutoEncoder: hidden_dims is empty, which makes the network purely linear; the layer-major engine has no "
+                "program for it (PINN_ERR_UNSUPPORTED)"
+            )
+        return dict(arch="autoencoder", activation=self.activation_name, input_dim=self.input_dim,
+                    widths=hidden + [self.latent_dim] + hidden[::-1] + [self.output_dim], num_blocks=len(hidden),
+                    layer_norm=bool(self.use_layer_norm))
+
+
 class PINNModel(BaseNetwork):
     """neural_networks/__init__.py:61-154 — architecture factory; `.model` holds the network."""
 
@@ -374,7 +434,9 @@ class PINNModel(BaseNetwork):
             self.model = SIREN(mc)
         elif a == "attention":
             self.model = AttentionNetwork(mc)
-        elif a in ("autoencoder", "fno"):
+        elif a == "autoencoder":
+            self.model = AutoEncoder(mc)
+        elif a == "fno":
             raise NotImplementedError(
                 f"pinnrl_amd: architecture '{a}' is outside the accelerated hot path (SURVEY.md §2 rows 8-9); "
                 "use pinnrl itself for it"

@@ -1,9 +1,12 @@
 """Residual+grad throughput of the five BASELINE.json configurations on ONE GPU (context for DESIGN.md §8).
 
-    python tools/bench_configs.py [--steps 10] [--only C3,C4]
+    python tools/bench_configs.py [--steps 10] [--only C3,C4] [--rounds 3]
 
 C2 is the headline (bench.py); the others are parity-test configurations timed here for information:
-one fused `pinn_residual_loss_grad` launch per step, points and weights resident.
+one fused `pinn_residual_loss_grad` launch per step, points and weights resident.  C6 is the autoencoder of the
+reference's shipped config.yaml and C6y its yardstick, the feedforward + LayerNorm network with the same GEMMs (plus a
+LayerNorm and an activation on the 64-wide layer).  --rounds R times the selected configurations R times in alternation
+(C6, C6y, C6, C6y, ...) and adds one line per configuration with the median and the spread over the rounds.
 """
 import argparse
 import math
@@ -52,44 +55,70 @@ CONFIGS = {
                    pde(P.KdVEquation, [(-15.0, 15.0)], (0.0, 5.0), {"speed": 1.0}, {"type": "soliton"}), 200000),
     "C5": lambda: ("Cahn-Hilliard 2D, attention 4 layers x128 (4 heads)", model("attention", 128, 4, "gelu", input_dim=3, num_heads=4),
                    pde(P.CahnHilliardEquation, [(0.0, 1.0), (0.0, 1.0)], (0.0, 1.0), {"epsilon": 0.01}, {"type": "tanh"}, 2), 1000000),
+    "C6": lambda: ("Burgers 1D nu=0.01/pi, autoencoder [124, 248, 124] latent 64, relu + LayerNorm",
+                   model("autoencoder", 124, 3, "relu", hidden_dims=[124, 248, 124], latent_dim=64, layer_norm=True),
+                   pde(P.BurgersEquation, [(-1.0, 1.0)], (0.0, 1.0), {"nu": 0.01 / math.pi}, {"type": "sine"}), 50000),
+    "C6y": lambda: ("Burgers 1D nu=0.01/pi, feedforward [124, 248, 124, 64, 124, 248, 124], relu + LayerNorm",
+                    model("feedforward", 124, 7, "relu", hidden_dims=[124, 248, 124, 64, 124, 248, 124], layer_norm=True),
+                    pde(P.BurgersEquation, [(-1.0, 1.0)], (0.0, 1.0), {"nu": 0.01 / math.pi}, {"type": "sine"}), 50000),
 }
+
+
+def prepare(tag):
+    name, net, eq, n_req = CONFIGS[tag]()
+    torch.manual_seed(1)
+    if tag == "C3":  # adaptive sampling yields exactly N points; throughput is distribution-independent
+        x = torch.rand(n_req, 1, device=dev) * 2 - 1
+        t = torch.rand(n_req, 1, device=dev)
+    else:
+        x, t = eq.generate_collocation_points(n_req, strategy="uniform")
+    prog, pd = net.program(), eq._pde_desc()
+    return name, net, prog, pd, x, t, E.new_flat_grad(prog, dev)
+
+
+def time_one(tag, ready, steps):
+    name, net, prog, pd, x, t, flat = ready
+    N = x.shape[0]
+    nt, nx = E.pde_streams(pd)
+    K = 1 + nt + nx
+    for _ in range(3):
+        flat.zero_()
+        E.residual_loss_grad(prog, pd, x, t, 1.0 / N, flat)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        flat.zero_()
+        E.residual_loss_grad(prog, pd, x, t, 1.0 / N, flat)
+    torch.cuda.synchronize()
+    ms = 1e3 * (time.perf_counter() - t0) / steps
+    tf = 3 * K * prog.flops_per_point() * N / (ms * 1e-3) / 1e12
+    print(f"| {tag} {name} | {N} | {net.count_parameters()} | {K} | {ms:.3f} | {N / ms * 1e3:.3e} | {tf:.1f} | {tf / 157.3:.3f} |", flush=True)
+    return ms
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--only", default="")
+    ap.add_argument("--rounds", type=int, default=1)
     args = ap.parse_args()
     only = [s for s in args.only.split(",") if s]
+    tags = [tag for tag in CONFIGS if not only or tag in only]
     print("| config | points | params | K | ms/step | points/s | TFLOP/s (3 K F_fwd) | frac of 157.3 |")
     print("|---|---|---|---|---|---|---|---|")
-    for tag, mk in CONFIGS.items():
-        if only and tag not in only:
-            continue
-        name, net, eq, n_req = mk()
-        torch.manual_seed(1)
-        if tag == "C3":  # adaptive sampling yields exactly N points; throughput is distribution-independent
-            x = torch.rand(n_req, 1, device=dev) * 2 - 1
-            t = torch.rand(n_req, 1, device=dev)
-        else:
-            x, t = eq.generate_collocation_points(n_req, strategy="uniform")
-        N = x.shape[0]
-        prog, pd = net.program(), eq._pde_desc()
-        nt, nx = E.pde_streams(pd)
-        K = 1 + nt + nx
-        flat = E.new_flat_grad(prog, dev)
-        for _ in range(3):
-            flat.zero_()
-            E.residual_loss_grad(prog, pd, x, t, 1.0 / N, flat)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            flat.zero_()
-            E.residual_loss_grad(prog, pd, x, t, 1.0 / N, flat)
-        torch.cuda.synchronize()
-        ms = 1e3 * (time.perf_counter() - t0) / args.steps
-        tf = 3 * K * prog.flops_per_point() * N / (ms * 1e-3) / 1e12
-        print(f"| {tag} {name} | {N} | {net.count_parameters()} | {K} | {ms:.3f} | {N / ms * 1e3:.3e} | {tf:.1f} | {tf / 157.3:.3f} |", flush=True)
+    if args.rounds <= 1:  # one configuration resident at a time
+        for tag in tags:
+            time_one(tag, prepare(tag), args.steps)
+        return
+    ready = {tag: prepare(tag) for tag in tags}  # alternation needs the selected configurations resident together
+    times = {tag: [] for tag in tags}
+    for _ in range(args.rounds):
+        for tag in tags:
+            times[tag].append(time_one(tag, ready[tag], args.steps))
+    for tag, ms in times.items():
+        s = sorted(ms)
+        print(f"{tag}: median {s[len(s) // 2]:.3f} ms over {len(s)} rounds, min {s[0]:.3f}, max {s[-1]:.3f} "
+              f"(spread {100 * (s[-1] - s[0]) / s[len(s) // 2]:.1f} % of the median)", flush=True)
 
 
 if __name__ == "__main__":
