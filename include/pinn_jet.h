@@ -331,6 +331,68 @@ int pinn_fd_stencil_points(const float* x, const float* t, int64_t N, double eps
 int pinn_fd_smoothness(const float* u3, int64_t N, double eps, float weight, float* loss_out, float* cotangent3, float* summary4,
                        double* scratch, void* stream);
 
+/* ---- residuals given as data (pinnrl: a user's PDEBase subclass, pinnrl/pdes/pde_base.py:574-588) ---------------------
+ * A residual outside the nine compiled PDEs, as a sum of products of streams, coordinates and sin / cos of the value:
+ *   r = sum_{m < n_terms} c_m prod_{f < n_factors[m]} phi_{m,f}
+ * Each factor is one PinnTermFactor code, whatever the stream set; a repeated code is a power (u^3 = U, U, U); a term
+ * without factors is a constant source.  The coefficients c_m are NOT in the descriptor: they are n_terms device floats
+ * read at launch time (the `coef_values` convention of pinn_residual_loss_grad_inverse), so a captured graph follows a
+ * coefficient that changes.
+ *
+ * pinn_term_residual is the element-wise middle of the chain pinn_jet_forward -> pinn_term_residual -> pinn_jet_backward:
+ *   jets               K x N, K = 1 + time_order + space_order, stream s at jets + s N (what pinn_jet_forward writes into
+ *                      K consecutive rows); x, t: N floats each (1-D problems), read only when a term names X / T;
+ *   residual_out       N floats, nullable;
+ *   loss_sum_out       nullable: loss_sum_out[0] += sum_n l(r_n), l = PinnLoss `loss` (as pinn_residual_loss_grad);
+ *   jet_cotangents     K x N, nullable, overwritten with rbar_n dr_n/djet_s[n] — the jet_cotangents of pinn_jet_backward;
+ *                      rbar_n = grad_scale l'(r_n) (sgn(0) = 0 for the absolute value, Huber's quadratic branch on
+ *                      |r| < delta), or residual_cotangent[n] when that array (N floats, nullable) is given: the backward of
+ *                      a residual tensor in an arbitrary downstream graph;
+ *   coef_grads         nullable: coef_grads[m] += sum_n rbar_n prod_f phi_{m,f}, m < n_terms;
+ *   scratch            PINN_TERM_SCRATCH_DOUBLES doubles, 8-byte aligned; may be NULL when neither loss_sum_out nor
+ *                      coef_grads is given.
+ * 256-thread blocks on a fixed grid of at most 64, one point per thread with its K streams in registers, the term list in
+ * the kernel arguments.  The loss and coefficient sums are per-block partials in double that a second launch adds in block
+ * order: no atomics, bit-identical across runs.  Without loss_sum_out and coef_grads the call is ONE launch.
+ * Checked on the host before any HIP call: n_terms outside [0, PINN_TERM_MAX_TERMS], n_factors outside
+ * [0, PINN_TERM_MAX_FACTORS], an unknown factor code, a factor naming a stream that (time_order, space_order) does not
+ * hold, a stream set without a compiled unit, N < 0, null jets / coef_values (or x / t under an X / T factor, or scratch
+ * where it is needed) with N > 0: PINN_ERR_BAD_DESC; misaligned scratch: PINN_ERR_MISALIGNED.  N == 0: no-op. */
+#define PINN_TERM_MAX_TERMS 16
+#define PINN_TERM_MAX_FACTORS 4
+#define PINN_TERM_SCRATCH_DOUBLES (64 * (1 + PINN_TERM_MAX_TERMS))
+
+typedef enum PinnTermFactor {
+  PINN_TERM_U = 0,
+  PINN_TERM_UT = 1,
+  PINN_TERM_UTT = 2,
+  PINN_TERM_UX = 3,
+  PINN_TERM_UXX = 4,
+  PINN_TERM_UXXX = 5,
+  PINN_TERM_UXXXX = 6,
+  PINN_TERM_X = 7,
+  PINN_TERM_T = 8,
+  PINN_TERM_SIN_U = 9,
+  PINN_TERM_COS_U = 10
+} PinnTermFactor;
+
+typedef struct PinnTermPdeTerm {
+  int32_t n_factors;                     /* 0 .. PINN_TERM_MAX_FACTORS */
+  int32_t factor[PINN_TERM_MAX_FACTORS]; /* PinnTermFactor */
+} PinnTermPdeTerm;
+
+typedef struct PinnTermPde {
+  int32_t time_order, space_order; /* the stream set of `jets`: one the library has a unit for */
+  int32_t n_terms;                 /* 0 .. PINN_TERM_MAX_TERMS */
+  int32_t loss;                    /* PinnLoss */
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_TERM_MAX_TERMS];
+} PinnTermPde;
+
+int pinn_term_residual(const PinnTermPde* pde, const float* coef_values, const float* jets, const float* x, const float* t,
+                       int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out, float* loss_sum_out,
+                       float* jet_cotangents, float* coef_grads, double* scratch, void* stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.
  * lr and step are DEVICE scalars (step = number of steps taken so far, incremented by the call) so that a captured

@@ -188,7 +188,46 @@ def pde_desc(kind: str, dimension: int = 1, coef: Sequence[float] = (), loss: st
     return d
 
 
+class TermDesc:
+    """A residual given as data (`pinn_term_residual`): r = sum_m c_m prod_f phi_{m,f}.
+
+    terms: one sequence of factor names (`_lib.TERM_FACTOR`: "u", "u_t", ..., "u_xxxx", "x", "t", "sin(u)", "cos(u)") per
+    term, at most 16 terms of at most 4 factors; coef_values: the c_m, float32 on the device, read at LAUNCH time (a
+    captured graph follows an in-place write); (nt, nx): a compiled stream set that holds every stream the factors name.
+    Wherever the engine takes a `PinnPdeDesc` it takes a `TermDesc` too and runs the chain jets_forward -> term_residual
+    (-> jets_backward) in place of the one fused launch."""
+
+    def __init__(self, terms: Sequence[Sequence[str]], coef_values: Tensor, nt: int, nx: int, loss: str = "mse",
+                 huber_delta: float = 1.0):
+        if len(terms) > _lib.PINN_TERM_MAX_TERMS:
+            raise ValueError(f"a term residual has at most {_lib.PINN_TERM_MAX_TERMS} terms (got {len(terms)})")
+        d = _lib.PinnTermPde()
+        d.time_order, d.space_order, d.n_terms = int(nt), int(nx), len(terms)
+        d.loss = _lib.LOSS.get(loss, 0)  # unknown names fall back to mse (pde_base.py:313-315)
+        d.huber_delta = float(huber_delta)
+        for m, factors in enumerate(terms):
+            if len(factors) > _lib.PINN_TERM_MAX_FACTORS:
+                raise ValueError(f"term {m}: at most {_lib.PINN_TERM_MAX_FACTORS} factors (got {len(factors)})")
+            d.terms[m].n_factors = len(factors)
+            for f, name in enumerate(factors):
+                if name not in _lib.TERM_FACTOR:
+                    raise ValueError(f"term {m}: unknown factor '{name}' (one of {', '.join(_lib.TERM_FACTOR)})")
+                d.terms[m].factor[f] = _lib.TERM_FACTOR[name]
+        if coef_values.dtype != torch.float32 or not coef_values.is_contiguous() or coef_values.numel() < len(terms):
+            raise ValueError("coef_values: one contiguous float32 value per term")
+        self.desc = d
+        self.terms = [tuple(f) for f in terms]
+        self.coef_values = coef_values
+        self.nt, self.nx = int(nt), int(nx)
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "TermDesc":
+        """The same program and the same coefficient tensor under another loss kind."""
+        return TermDesc(self.terms, self.coef_values, self.nt, self.nx, loss, huber_delta)
+
+
 def pde_streams(pd) -> Tuple[int, int]:
+    if isinstance(pd, TermDesc):
+        return pd.nt, pd.nx
     nt, nx = ctypes.c_int32(), ctypes.c_int32()
     _lib.check(_lib.load().pinn_pde_streams(ctypes.byref(pd), ctypes.byref(nt), ctypes.byref(nx)))
     return nt.value, nx.value
@@ -276,11 +315,51 @@ def jets_backward_inputs(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: in
     return xg, tg
 
 
+def term_residual(td: TermDesc, jets: Tensor, x: Tensor, t: Tensor, grad_scale: float = 0.0,
+                  residual_cotangent: Optional[Tensor] = None, want_residual: bool = True, loss_sum: Optional[Tensor] = None,
+                  want_cotangents: bool = False, coef_grads: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """`pinn_term_residual` on (K, N) jets of the descriptor's stream set: (residual (N, 1) | None, cotangents (K, N) | None).
+    loss_sum[0] += sum_n l(r_n) and coef_grads[m] += sum_n rbar_n prod_f phi_{m,f} where given; the cotangents are
+    rbar_n dr_n/djet_s with rbar_n = grad_scale l'(r_n), or residual_cotangent[n] when that is given.  One launch, two with a
+    loss or coefficient sum; the buffers come from torch's allocator."""
+    lib = _lib.load()
+    dev = _require_device(jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads)
+    K = 1 + td.nt + td.nx
+    if jets.dim() != 2 or jets.shape[0] != K or jets.dtype != torch.float32 or not jets.is_contiguous():
+        raise ValueError(f"term_residual: jets must be a contiguous float32 ({K}, N) tensor of the set ({td.nt}, {td.nx})")
+    N = jets.shape[1]
+    x, t = _f32c(x.detach()), _f32c(t.detach())
+    if x.numel() != N or t.numel() != N:
+        raise ValueError(f"term_residual: x and t hold one value per point of a 1-D problem (N = {N}; got {tuple(x.shape)}, {tuple(t.shape)})")
+    if residual_cotangent is not None:
+        residual_cotangent = _f32c(residual_cotangent).reshape(-1)
+        assert residual_cotangent.numel() == N
+    for tns in (loss_sum, coef_grads):
+        assert tns is None or (tns.dtype == torch.float32 and tns.is_contiguous())
+    assert coef_grads is None or coef_grads.numel() >= td.desc.n_terms
+    r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
+    cot = torch.empty((K, N), dtype=torch.float32, device=dev) if want_cotangents else None
+    if N == 0:
+        return r, cot
+    reduce = loss_sum is not None or coef_grads is not None
+    scratch = torch.empty(_lib.PINN_TERM_SCRATCH_DOUBLES, dtype=torch.float64, device=dev) if reduce else None
+    opt = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_term_residual(ctypes.byref(td.desc), td.coef_values.data_ptr(), jets.data_ptr(), x.data_ptr(),
+                                          t.data_ptr(), N, float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum),
+                                          opt(cot), opt(coef_grads), opt(scratch), _stream(dev)))
+    return r, cot
+
+
 def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: bool = True) -> Tuple[Optional[Tensor], Tensor]:
     """(residual (N,1) | None, loss_sum (1,)) with loss_sum = sum_n l(r_n) over THESE points."""
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    if isinstance(pd, TermDesc) and N:  # the chain: jets, then the element-wise residual
+        s = torch.zeros(1, dtype=torch.float32, device=dev)
+        r, _ = term_residual(pd, jets_forward(prog, x, t, pd.nt, pd.nx), x, t, want_residual=want_residual, loss_sum=s)
+        return r, s
     r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
     s = torch.zeros(1, dtype=torch.float32, device=dev)
     if N:
@@ -304,6 +383,14 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
     lib = _lib.load()
     dev = _require_device(x, t, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    if isinstance(pd, TermDesc) and N:
+        # the chain: jets, the element-wise residual with its loss sum and cotangents (coef_grads: one sum per term), the
+        # reverse sweep of the jets
+        s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
+        r, cot = term_residual(pd, jets_forward(prog, x, t, pd.nt, pd.nx), x, t, grad_scale=grad_scale,
+                               want_residual=want_residual, loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
+        jets_backward(prog, x, t, pd.nt, pd.nx, cot, flat_grad)
+        return r, s
     r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
     s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
     if N:
@@ -368,6 +455,11 @@ def residual_backward(prog: NetProgram, pd, x: Tensor, t: Tensor, res_bar: Tenso
         return
     res_bar = _f32c(res_bar).reshape(-1)
     assert res_bar.numel() == N
+    if isinstance(pd, TermDesc):  # the chain with the caller's cotangent in place of grad_scale l'(r)
+        _, cot = term_residual(pd, jets_forward(prog, x, t, pd.nt, pd.nx), x, t, residual_cotangent=res_bar,
+                               want_residual=False, want_cotangents=True)
+        jets_backward(prog, x, t, pd.nt, pd.nx, cot, flat_grad)
+        return
     nt, nx = pde_streams(pd)
     ws, wptr, wn = _scratch(prog, dev, N, nt, nx, True)
     with torch.cuda.device(dev):

@@ -5,6 +5,7 @@ from .equations import (  # noqa: F401
     KdVEquation, PendulumEquation, WaveEquation,
 )
 from .pde_base import PDEBase, PDEConfig  # noqa: F401
+from .term_pde import TermPDE  # noqa: F401
 
 _BY_TYPE = {
     "heat": HeatEquation, "wave": WaveEquation, "burgers": BurgersEquation, "kdv": KdVEquation,

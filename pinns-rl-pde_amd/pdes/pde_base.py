@@ -305,6 +305,11 @@ class PDEBase:
         coefs = [float(c.detach()) if isinstance(c, torch.Tensor) else float(c) for c in self._coefficients()]
         return _E.pde_desc(self.KIND, self.dimension, coefs, self._loss_function_name(), self._huber_delta())
 
+    def _pde_desc_l1(self):
+        """The residual under the l1 reduction, whose loss sum is sum |r|: the normaliser of the RAR sampler."""
+        coefs = [float(c.detach()) if isinstance(c, torch.Tensor) else float(c) for c in self._coefficients()]
+        return _E.pde_desc(self.KIND, self.dimension, coefs, "mae", 1.0)
+
     def _has_trainable_coefficients(self) -> bool:
         return any(isinstance(c, torch.Tensor) and c.requires_grad for c in self._coefficients())
 
@@ -462,8 +467,7 @@ class PDEBase:
                     total = mag.sum()
                 else:
                     _jets_of(model)
-                    coefs = [float(c.detach()) if isinstance(c, torch.Tensor) else float(c) for c in self._coefficients()]
-                    pd_l1 = _E.pde_desc(self.KIND, self.dimension, coefs, "mae", 1.0)
+                    pd_l1 = self._pde_desc_l1()
                     r, total = _E.residual_forward(model.program(), pd_l1, x_pool.detach().to(self.device), t_pool.detach().to(self.device))
                     mag = torch.abs(r).reshape(-1)
         except NotImplementedError:

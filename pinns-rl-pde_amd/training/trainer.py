@@ -435,6 +435,7 @@ class PDETrainer:
     def _manual_step_unsupported(self) -> Optional[str]:
         """None when the step can run as the fixed launch sequence below; else the reason (callers fall back)."""
         from ..pdes.pde_base import PDEBase
+        from ..pdes.term_pde import TermPDE
 
         tc = self.config.training
         kind = getattr(tc, "optimizer", "adam")
@@ -448,6 +449,16 @@ class PDETrainer:
             return "RL agent without a device-side action selection"
         if getattr(tc, "collocation_distribution", "uniform") not in ("uniform", "stratified", "residual_based"):
             return "unknown sampler"
+        if isinstance(self.pde, TermPDE):
+            # a residual given as data runs the launch list through the chain jets -> pinn_term_residual -> reverse sweep
+            # (engine.residual_loss_grad dispatches on the descriptor), with its coefficients by value on the device
+            if self.pde._has_trainable_coefficients():  # a trainable parameter no term names gets the general reason below
+                return ("TermPDE with trainable term coefficients (the flat coefficient state of the inverse launch list has "
+                        "two slots, a term residual up to sixteen coefficients)")
+            if self.pde._training_mode() != "forward" or getattr(self.pde, "observation_data", None):
+                return "TermPDE in a data mode (the launch list of a term residual covers forward problems)"
+            if self.process_group is not None:
+                return "TermPDE under a process group"
         own_loss = type(self.pde).compute_loss is not PDEBase.compute_loss
         if own_loss and type(self.pde)._manual_chain is PDEBase._manual_chain:
             return f"{type(self.pde).__name__} overrides compute_loss without a launch-list form (_manual_chain)"

@@ -2,6 +2,7 @@
 
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
+                               [--term-pde]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -18,6 +19,11 @@ list (`pinn_adaptive_adam_step`).  `--repeats R` times the window R times and pr
 `--smoothness W` (C1 only) runs HeatEquation with the reference's default loss weights {residual 15, boundary 20, initial 10,
 smoothness W}: its finite-difference smoothness term is three more network evaluations of the batch and their reverse
 sweeps — autograd nodes in the autograd mode, four launches of the launch list in the other two.
+
+`--term-pde` (C2 only) runs Burgers as a `TermPDE` (u_t + u u_x - nu u_xx given as three terms): the residual part of the
+step is then the chain pinn_jet_forward -> pinn_term_residual -> pinn_jet_backward in place of the one fused launch.  After
+the step table it times those three launches on their own (device time between two events, the step's batch) next to the
+compiled kind's `pinn_residual_loss_grad`.
 
 `--optimizer lbfgs` times `optimizer="lbfgs"` instead (C2 and C3 unless --configs is given; max_iter 20, history_size 50,
 strong Wolfe, lr 1, one fixed full batch as L-BFGS wants it, uniform points): the eager step (torch.optim.LBFGS around an
@@ -36,13 +42,21 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: E402
 
 import bench_configs as B  # noqa: E402
+from pinnrl_amd import engine as E  # noqa: E402
 from pinnrl_amd.config import AdaptiveWeightsConfig, Config, TrainingConfig  # noqa: E402
+from pinnrl_amd.pdes import TermPDE  # noqa: E402
 from pinnrl_amd.rl import RLAgent  # noqa: E402
 from pinnrl_amd.training import PDETrainer  # noqa: E402
 
 
-def build(tag, adaptive="none", smoothness=0.0):
+BURGERS_TERMS = [(1.0, ("u_t",)), (1.0, ("u", "u_x")), ((-1.0, "nu"), ("u_xx",))]
+
+
+def build(tag, adaptive="none", smoothness=0.0, term_pde=False):
     name, net, eq, n_req = B.CONFIGS[tag]()
+    if term_pde:  # the same configuration object, the residual given as data
+        eq = TermPDE(eq.config, BURGERS_TERMS)
+        name += ", as TermPDE"
     agent = None
     if tag == "C3":  # BASELINE C3: DQN adaptive sampling
         agent = RLAgent(state_dim=2, action_dim=1, hidden_dim=64, device=B.dev)
@@ -139,6 +153,41 @@ def bench_lbfgs(args):
             torch.cuda.empty_cache()
 
 
+def time_term_launches(tag, iters=20):
+    """Device time of the three launches of the term chain, each on its own, and of the compiled kind's one launch."""
+    torch.manual_seed(0)
+    name, net, eq, n_req = B.CONFIGS[tag]()
+    term = TermPDE(eq.config, BURGERS_TERMS)
+    x, t = eq.generate_collocation_points(n_req, strategy="uniform")
+    prog, pd, td = net.program(), eq._pde_desc(), term._pde_desc()
+    n = int(x.shape[0])
+    nt, nx = E.pde_streams(td)
+    flat, s = E.new_flat_grad(prog, B.dev), torch.zeros(1, device=B.dev)
+    jets = E.jets_forward(prog, x, t, nt, nx)
+    _, cot = E.term_residual(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
+    calls = [("pinn_jet_forward", lambda: E.jets_forward(prog, x, t, nt, nx)),
+             ("pinn_term_residual (loss sum + cotangents, two launches)",
+              lambda: E.term_residual(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)),
+             ("pinn_term_residual (residual only, one launch)", lambda: E.term_residual(td, jets, x, t)),
+             ("pinn_jet_backward", lambda: E.jets_backward(prog, x, t, nt, nx, cot, flat)),
+             ("the chain through engine.residual_loss_grad", lambda: E.residual_loss_grad(prog, td, x, t, 1.0 / n, flat, loss_sum=s)),
+             ("compiled kind: pinn_residual_loss_grad", lambda: E.residual_loss_grad(prog, pd, x, t, 1.0 / n, flat, loss_sum=s))]
+    print()
+    print(f"| {tag} launch ({n} points, kernels {E._lib.kernel_name(prog, n, nt, nx, 0)} / {E._lib.kernel_name(prog, n, nt, nx, 1)}) | ms |")
+    print("|---|---|")
+    for label, fn in calls:
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        print(f"| {label} | {a.elapsed_time(b) / iters:.4f} |", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C4")
@@ -148,7 +197,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--optimizer", choices=["adam", "lbfgs"], default="adam")
     ap.add_argument("--smoothness", type=float, default=0.0, help="C1 only: weight of HeatEquation's smoothness term")
+    ap.add_argument("--term-pde", action="store_true", help="C2 only: Burgers as a TermPDE, and the chain's launches on their own")
     args = ap.parse_args()
+    if args.term_pde and args.configs == "C1,C2,C3,C4":
+        args.configs = "C2"
     if args.optimizer == "lbfgs":
         return bench_lbfgs(args)
     print("| config | points | sampler | mode | ms/step | points/s | last total loss |")
@@ -158,8 +210,11 @@ def main():
             if args.smoothness > 0 and tag != "C1":
                 print(f"| {tag} | - | - | {mode} | not covered: --smoothness applies to C1 (HeatEquation) only | | |")
                 continue
+            if args.term_pde and tag != "C2":
+                print(f"| {tag} | - | - | {mode} | not covered: --term-pde applies to C2 (Burgers) only | | |")
+                continue
             torch.manual_seed(0)
-            name, net, eq, agent, cfg, n_req = build(tag, args.adaptive, args.smoothness)
+            name, net, eq, agent, cfg, n_req = build(tag, args.adaptive, args.smoothness, args.term_pde)
             tr = PDETrainer(net, eq, None, cfg, device=B.dev, rl_agent=agent, fast_step=False)
             if mode != "autograd":
                 why = tr._manual_step_unsupported()
@@ -194,6 +249,8 @@ def main():
             print(f"| {tag} {name} | {n} | {sampler} | {mode} | {ms:.3f}{spread} | {n / ms * 1e3:.3e} | {float(last['total'].detach()):.4e} |", flush=True)
             del tr, net, eq
             torch.cuda.empty_cache()
+        if args.term_pde and tag == "C2":
+            time_term_launches(tag)
 
 
 if __name__ == "__main__":
