@@ -60,6 +60,9 @@ extern "C" {
                                      applies (same results to rounding; tests run both) */
 #define PINN_FLAG_WIDE_TILE32 8   /* engine hint: reverse launches of the fused tile-major kernel keep the 32-point kernel
                                      where the 16-point one would run (A/B runs and tests; same results to rounding) */
+#define PINN_FLAG_PLAIN_STREAMS 16 /* engine hint: every call of the descriptor keeps one stream per derivative where the
+                                      16-point kernel would run 1-D Burgers on the merged set u, u_t - nu u_xx, u_x (A/B
+                                      runs and tests; same results to rounding) */
 
 typedef enum PinnStatus {
   PINN_OK = 0,

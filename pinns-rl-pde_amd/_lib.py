@@ -18,6 +18,7 @@ PINN_FLAG_LAYER_NORM = 1
 PINN_FLAG_DETERMINISTIC = 2
 PINN_FLAG_LAYER_MAJOR = 4
 PINN_FLAG_WIDE_TILE32 = 8
+PINN_FLAG_PLAIN_STREAMS = 16
 
 ARCH = {"feedforward": 0, "fourier": 1, "siren": 2, "resnet": 3, "attention": 4, "autoencoder": 5}
 ACT = {"tanh": 0, "sin": 1, "gelu": 2, "sigmoid": 3, "relu": 4, "leaky_relu": 5, "identity": 6}

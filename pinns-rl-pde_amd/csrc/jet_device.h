@@ -236,6 +236,70 @@ __device__ __forceinline__ void act_bwd_tape(float w, const float* z, const floa
   zb[0] = z0b;
 }
 
+// ---------------------------------------------------------------------------
+// Merged stream set.  A residual that reads u_t and u_xx only through w = u_t + c u_xx = D u,
+// D = d/dt + c d2/dx2, needs three streams [value, w, d/dx] instead of four: D passes a Linear layer unchanged
+// and an activation y = f(z) as  y_x = f' z_x,  y_w = f' z_w + c f'' z_x^2.  Burgers: c = -nu, r = w + u u_x.
+// The stream order is that of the (1,1) set with w in the time slot, so a first Linear takes its t column as z_w
+// and its x column as z_x.  tests/merged_model.py is the executable specification.
+// ---------------------------------------------------------------------------
+// jets of f(z) from f[1], f[2] (f[0] is the caller's)
+__device__ __forceinline__ void merged_fwd(const float (&f)[6], float cc, const float* z, float* a) {
+  a[1] = fmaf(cc * f[2], z[2] * z[2], f[1] * z[1]);
+  a[2] = f[1] * z[2];
+}
+
+template <int ACT>
+__device__ __forceinline__ void act_fwd_merged(float w, float cc, const float* z, float* a) {
+  float f[6];
+  act_derivs<ACT, 2>(z[0], w, f);
+  a[0] = f[0];
+  merged_fwd(f, cc, z, a);
+}
+
+template <int ACT>
+__device__ __forceinline__ void act_fwd_tape_merged(float w, float cc, const float* z, float* a) {
+  float f[6];
+  act_derivs_tape<ACT, 2>(z[0], w, f);
+  a[0] = f[0];
+  merged_fwd(f, cc, z, a);
+}
+
+// adjoint from f[1..3]; returns the element's share of dL/dc, ab_w f'' z_x^2 (the coefficient partial)
+__device__ __forceinline__ float merged_bwd(const float (&f)[6], float cc, const float* z, const float* ab, float* zb) {
+  const float zx2 = z[2] * z[2];
+  zb[1] = f[1] * ab[1];
+  zb[2] = fmaf(2.0f * cc * f[2] * z[2], ab[1], f[1] * ab[2]);
+  zb[0] = f[1] * ab[0] + f[2] * z[2] * ab[2] + (f[2] * z[1] + cc * f[3] * zx2) * ab[1];
+  return ab[1] * f[2] * zx2;
+}
+
+template <int ACT>
+__device__ __forceinline__ float act_bwd_merged(float w, float cc, const float* z, const float* ab, float* zb) {
+  float f[6];
+  act_derivs<ACT, 3>(z[0], w, f);
+  return merged_bwd(f, cc, z, ab, zb);
+}
+
+template <int ACT>
+__device__ __forceinline__ float act_bwd_tape_merged(float w, float cc, const float* z, const float* ab, float* zb) {
+  float f[6];
+  act_derivs_tape<ACT, 3>(z[0], w, f);
+  return merged_bwd(f, cc, z, ab, zb);
+}
+
+// Burgers epilogue on the merged jets j = [u, w, u_x]: r = w + u u_x and dr/dj.  The coefficient does not appear: its
+// cotangent is the sum of the coefficient partials of every activation element and of the Fourier features.
+__device__ __forceinline__ float pde_residual_merged(const float* j, float* d) {
+  d[0] = j[2];
+  d[1] = 1.0f;
+  d[2] = j[0];
+  return j[1] + j[0] * j[2];
+}
+
+// coefficient partial of a Fourier feature (sin or cos alike): d y_w / dc = -b_x^2 (value feature)
+__device__ __forceinline__ float fourier_coef_partial_merged(float bx, float value) { return -(bx * bx) * value; }
+
 // Runtime activation id -> compile-time tag (the id is uniform across the workgroup).
 // The body sees `ACT` as a constant expression; variadic so template commas survive.
 #define PINN_ACT_SWITCH(act_id, ...)                                           \

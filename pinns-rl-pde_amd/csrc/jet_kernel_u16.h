@@ -82,8 +82,9 @@ __device__ __forceinline__ void u16_enc_preact(const float* ep, int din, const f
 }
 
 // encoding into an image dst[s][n][f]; thread -> (point tid & 15, feature tid >> 4 + 32 i)
-template <int ACT, int NT, int NX>
-__device__ __forceinline__ void u16_encode(const NetDev& net, const float* ep, const float* xin, float* dst, int tid) {
+// MRG: the merged stream set [value, w, d/dx] (jet_device.h), cc its coefficient c; NT = NX = 1 then
+template <int ACT, int NT, int NX, bool MRG = false>
+__device__ __forceinline__ void u16_encode(const NetDev& net, const float* ep, const float* xin, float* dst, int tid, float cc = 0.0f) {
   constexpr int K = 1 + NT + NX;
   const int n = tid & 15;
   const int din = net.din;
@@ -100,10 +101,15 @@ __device__ __forceinline__ void u16_encode(const NetDev& net, const float* ep, c
       const float fc[6] = {cs, -sn, -cs, sn, cs, -sn};
       ys[0] = sn;
       yc[0] = cs;
-      dir_fwd<NT>(fs, z + 1, ys + 1);
-      dir_fwd<NX>(fs, z + 1 + NT, ys + 1 + NT);
-      dir_fwd<NT>(fc, z + 1, yc + 1);
-      dir_fwd<NX>(fc, z + 1 + NT, yc + 1 + NT);
+      if constexpr (MRG) {
+        merged_fwd(fs, cc, z, ys);
+        merged_fwd(fc, cc, z, yc);
+      } else {
+        dir_fwd<NT>(fs, z + 1, ys + 1);
+        dir_fwd<NX>(fs, z + 1 + NT, ys + 1 + NT);
+        dir_fwd<NT>(fc, z + 1, yc + 1);
+        dir_fwd<NX>(fc, z + 1 + NT, yc + 1 + NT);
+      }
 #pragma unroll
       for (int s = 0; s < K; ++s) {
         row[s * kUImgS + m] = ys[s];
@@ -116,7 +122,8 @@ __device__ __forceinline__ void u16_encode(const NetDev& net, const float* ep, c
     for (int f = tid >> 4; f < H; f += kUThreads / kU) {
       float z[K], y[K];
       u16_enc_preact<NT, NX>(ep, din, xin, f, n, z);
-      act_fwd<ACT, NT, NX>(net.enc_param, z, y);
+      if constexpr (MRG) act_fwd_merged<ACT>(net.enc_param, cc, z, y);
+      else act_fwd<ACT, NT, NX>(net.enc_param, z, y);
 #pragma unroll
       for (int s = 0; s < K; ++s) row[s * kUImgS + f] = y[s];
     }
@@ -348,15 +355,16 @@ __device__ __forceinline__ void u16_wave_sync() {
 }
 
 // forward activation jets of the accumulator (rows 16w + 4g + r, point c); rec gets the tape record
-template <int ACT, int NT, int NX>
-__device__ __forceinline__ void u16_ew_forward(f32x4 (&v)[1 + NT + NX], float w, f32x4 (&rec)[1 + NT + NX]) {
+template <int ACT, int NT, int NX, bool MRG = false>
+__device__ __forceinline__ void u16_ew_forward(f32x4 (&v)[1 + NT + NX], float w, f32x4 (&rec)[1 + NT + NX], float cc = 0.0f) {
   constexpr int K = 1 + NT + NX;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float z[K], y[K];
 #pragma unroll
     for (int s = 0; s < K; ++s) z[s] = v[s][r];
-    act_fwd<ACT, NT, NX>(w, z, y);
+    if constexpr (MRG) act_fwd_merged<ACT>(w, cc, z, y);
+    else act_fwd<ACT, NT, NX>(w, z, y);
     rec[0][r] = ActTape<ACT>::value_is_output ? y[0] : z[0];
 #pragma unroll
     for (int s = 1; s < K; ++s) rec[s][r] = z[s];
@@ -376,10 +384,11 @@ __device__ __forceinline__ void u16_get(const float* il, f32x4 (&v)[K]) {
   for (int s = 0; s < K; ++s) v[s] = *reinterpret_cast<const f32x4*>(il + s * kUImgS);
 }
 
-// activation adjoint of the accumulator rows with record rec
-template <int ACT, int NT, int NX>
-__device__ __forceinline__ void u16_ew_backward(f32x4 (&ab)[1 + NT + NX], float w, const f32x4 (&rec)[1 + NT + NX]) {
+// activation adjoint of the accumulator rows with record rec; MRG: returns the rows' coefficient partials (else 0)
+template <int ACT, int NT, int NX, bool MRG = false>
+__device__ __forceinline__ float u16_ew_backward(f32x4 (&ab)[1 + NT + NX], float w, const f32x4 (&rec)[1 + NT + NX], float cc = 0.0f) {
   constexpr int K = 1 + NT + NX;
+  float part = 0.0f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float z[K], abv[K], zb[K];
@@ -388,10 +397,19 @@ __device__ __forceinline__ void u16_ew_backward(f32x4 (&ab)[1 + NT + NX], float 
       z[s] = rec[s][r];
       abv[s] = ab[s][r];
     }
-    act_bwd_tape<ACT, NT, NX>(w, z, abv, zb);
+    if constexpr (MRG) part += act_bwd_tape_merged<ACT>(w, cc, z, abv, zb);
+    else act_bwd_tape<ACT, NT, NX>(w, z, abv, zb);
 #pragma unroll
     for (int s = 0; s < K; ++s) ab[s][r] = zb[s];
   }
+  return part;
+}
+
+// replay of activation jets from a tape record, either stream set
+template <int ACT, int NT, int NX, bool MRG>
+__device__ __forceinline__ void u16_act_replay(float w, float cc, const float* z, float* y) {
+  if constexpr (MRG) act_fwd_tape_merged<ACT>(w, cc, z, y);
+  else act_fwd_tape<ACT, NT, NX>(w, z, y);
 }
 
 // sum over the 64 lanes of a wave of lanes with (lane & 15) == 0 .. 15 folded: every lane gets the sum over its
@@ -413,8 +431,14 @@ __device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
 // X[n][128], X[n][129]: the sums of writer lane n (COEF only); X[k][130], k < 4: coefficient c_k (every variant: the
 // by-value coefficients are staged there too, so that products of them are formed in the epilogue and not held in
 // VGPRs across the unit loop).
-template <int ACT, int NT, int NX, bool BWD, int NA0, bool COEF = false>
+//
+// MRG = true (jet_u16m_* / jet_u16mc_* units, NT = NX = 1): the merged stream set [value, w, d/dx] of jet_device.h on
+// the Burgers residual, K = 3.  Its coefficient c = -c_0 is read from the row pad where it is used.  The merged COEF
+// form sums dL/dc per lane in pcl (every activation element's partial, and at layer 0 the Fourier features' through one
+// more single-stream abar GEMM) and stores -sum as the cotangent of c_0 in the slab row's slot.
+template <int ACT, int NT, int NX, bool BWD, int NA0, bool COEF = false, bool MRG = false>
 __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs a) {
+  static_assert(!MRG || (NT == 1 && NX == 1), "the merged set is laid out as the (1,1) set");
   constexpr int K = 1 + NT + NX;
   constexpr int NKT = kUH / 16;
   constexpr int NPT = NA0 + (kPersist - 1) * NKT;
@@ -435,6 +459,16 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
                                                       // VGPRs to spare for a running sum that B0 alone touches)
   float* psl = pdwl + 4 * kUThreads;  // 2 * kU: running loss and db_out sums of the writer lanes (tid < kU), same reason
   float* xint = psl + 2 * kU;         // kMaxDin * kU: coordinates of the packed round's points (fetched at kernel start)
+  [[maybe_unused]] float* pcl = xint + kMaxDin * kU;  // kUThreads: per-lane dL/dc sums (merged COEF units only: not allocated otherwise)
+  auto mcoef = [&]() -> float {  // c of the merged set (visible after the unit loop's first barrier)
+    if constexpr (MRG) return -X[kUH + 2];
+    else return 0.0f;
+  };
+  auto cadd = [&](float part, bool own) {  // lane-private slot
+    if constexpr (MRG && COEF) {
+      if (own) pcl[u16_opaque(threadIdx.x)] += part;
+    }
+  };
 
   PINN_STAMP_DECL
   const int tid = threadIdx.x;
@@ -482,6 +516,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   for (int t = 0; t < NPT; ++t) pt[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   if constexpr (BWD) *reinterpret_cast<f32x4*>(pdwl + 4 * tid) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};  // lane-private
   if (tid < 2 * kU) psl[tid] = 0.0f;  // lane-private from here on: slot tid and slot kU + tid of lane tid < kU
+  if constexpr (MRG && COEF) pcl[tid] = 0.0f;
 
   float xr[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
   auto fetch_coords = [&](long long u) {
@@ -544,7 +579,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     // its record is then parked in A2 and the reverse sweep finds zbar -> X, a_{l-1} -> A2 for every n_layers.
     float* src = (nl & 1) ? X : A2;
     float* dst = (nl & 1) ? A2 : X;
-    u16_encode<ACT, NT, NX>(net, ep, xin, src, u16_opaque(tid));  // opaque: addresses formed here, not held over the loop
+    u16_encode<ACT, NT, NX, MRG>(net, ep, xin, src, u16_opaque(tid), mcoef());  // opaque: addresses formed here, not held over the loop
     U16_BARRIER(ST_ENCODE);
 
     // ---- hidden layers ----
@@ -570,7 +605,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         }
         if (on) {  // the record goes to this wave's own columns: nobody else reads them in the forward sweep
           f32x4 rec[K];
-          u16_ew_forward<ACT, NT, NX>(acc, Ly.act_param, rec);
+          u16_ew_forward<ACT, NT, NX, MRG>(acc, Ly.act_param, rec, mcoef());
           if constexpr (BWD) u16_put<K>(REC + l * img + ioff, rec);
         }
         // dst was last read a barrier ago (by the GEMMs of layer l-1, or by the previous unit's reverse sweep)
@@ -581,7 +616,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         dst = t;
       } else if (on) {  // last hidden layer: activations stay in acc, the record is parked in this wave's columns of A2
         f32x4 rec[K];
-        u16_ew_forward<ACT, NT, NX>(acc, Ly.act_param, rec);
+        u16_ew_forward<ACT, NT, NX, MRG>(acc, Ly.act_param, rec, mcoef());
         if constexpr (BWD) u16_put<K>(A2 + ioff, rec);
       }
     }
@@ -631,7 +666,9 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         pde.c1 = X[1 * kUP + kUH + 2];
         pde.c2 = X[2 * kUP + kUH + 2];
         pde.c3 = X[3 * kUP + kUH + 2];
-        const float r = pde_residual<NT, NX>(pde, j, xin[c], d);
+        float r;
+        if constexpr (MRG) r = pde_residual_merged(j, d);
+        else r = pde_residual<NT, NX>(pde, j, xin[c], d);
         float dl;
         float lt = loss_term(pde, r, &dl);
         if (!ok) {
@@ -643,7 +680,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         const float rb = !BWD ? 0.0f : a.res_bar ? (ok ? a.res_bar[p] : 0.0f) : a.grad_scale * dl;
 #pragma unroll
         for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
-        if constexpr (COEF) {
+        if constexpr (COEF && !MRG) {
           float dc0, dc1;
           pde_coef_grads<NT, NX>(pde, j, xin[c], dc0, dc1);
           if (writer) {  // lane-private LDS slots (tid < kU: c == tid)
@@ -674,14 +711,14 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           float z[K], y[K];
 #pragma unroll
           for (int s = 0; s < K; ++s) z[s] = rec[s][r];
-          act_fwd_tape<ACT, NT, NX>(Lz.act_param, z, y);
+          u16_act_replay<ACT, NT, NX, MRG>(Lz.act_param, mcoef(), z, y);
           float gg = 0.0f;
 #pragma unroll
           for (int s = 0; s < K; ++s) gg = fmaf(ub[s], y[s], gg);
           pdw[r] += gg;
         }
         *reinterpret_cast<f32x4*>(pdwp) = pdw;
-        u16_ew_backward<ACT, NT, NX>(ab, Lz.act_param, rec);
+        cadd(u16_ew_backward<ACT, NT, NX, MRG>(ab, Lz.act_param, rec, mcoef()), true);
       }
     }
     PINN_STAMP(ST_B0);
@@ -707,14 +744,14 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
             float z[K], yy[K];
 #pragma unroll
             for (int s = 0; s < K; ++s) z[s] = rec[s][r];
-            act_fwd_tape<ACT, NT, NX>(pw, z, yy);
+            u16_act_replay<ACT, NT, NX, MRG>(pw, mcoef(), z, yy);
 #pragma unroll
             for (int s = 0; s < K; ++s) y[s][r] = yy[s];
           }
           u16_put<K>(A2 + ioff, y);
         }
       } else {
-        u16_encode<ACT, NT, NX>(net, ep, xin, A2, u16_opaque(tid));
+        u16_encode<ACT, NT, NX, MRG>(net, ep, xin, A2, u16_opaque(tid), mcoef());
       }
       const unsigned coff = u16_cols_off(kon ? 16 * wv : 0, Ly.ld, c, g);
       if (need_abar) {  // requests hide under the barrier
@@ -759,15 +796,44 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         if (l > 0 && kon) {
           f32x4 rec[K];
           u16_get<K>(REC + (l - 1) * img + ioff, rec);
-          u16_ew_backward<ACT, NT, NX>(ab, pw, rec);
+          cadd(u16_ew_backward<ACT, NT, NX, MRG>(ab, pw, rec, mcoef()), true);
         }
         PINN_STAMP(ST_BWD_EW);
+      }
+      if constexpr (MRG && COEF) {
+        // Fourier features depend on c through their w stream: dL/dc += sum_j abar_w,j e_j with e_j = -b_x^2 (value
+        // feature j).  abar_w = W0^T zbar_w is one single-stream GEMM; the value features are stream 0 of A2.
+        if (l == 0 && net.enc == ENC_FOURIER && kon) {
+          f32x4 aw[1] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+          {  // a rolled loop: the unrolled, prefetching form of u16_gemm_n costs this unit scratch
+            const float* xl = X + kUImgS + c * kUP + 4 * g;
+            const int nb = Ly.out_dim >> 4;
+#pragma unroll 1
+            for (int b = 0; b < nb; ++b) {
+              const f32x4 w = u16_wload<true>(Ly.W, Ly.ld, coff, b);
+              const f32x4 xv = *reinterpret_cast<const f32x4*>(xl + 16 * b);
+#pragma unroll
+              for (int m = 0; m < 4; ++m) aw[0] = mfma16(w[m], xv[m], aw[0]);
+            }
+          }
+          const int M = net.enc_out >> 1;
+          const f32x4 val = *reinterpret_cast<const f32x4*>(A2 + ioff);
+          float part = 0.0f;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int jf = frow + r;
+            part = fmaf(aw[0][r], fourier_coef_partial_merged(ep[jf < M ? jf : jf - M], val[r]), part);
+          }
+          cadd(part, true);
+        }
       }
     }
 
     // ---- encoding backward (first Linear of feedforward / SIREN) ----
-    if (net.enc == ENC_LINEAR && net.d_encW) {
+    if (net.enc == ENC_LINEAR && (net.d_encW || (MRG && COEF))) {
       const int H = net.enc_out;
+      // merged COEF units run the adjoint for its coefficient partials even without a first-Linear gradient to form
+      const bool enc_sums = !(MRG && COEF) || net.d_encW != nullptr;
       U16_BARRIER(ST_ENC_BWD);
       if (16 * wv < H) {
 #pragma unroll
@@ -776,15 +842,16 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           u16_enc_preact<NT, NX>(ep, din, xin, frow + r, c, z);
 #pragma unroll
           for (int s = 0; s < K; ++s) abv[s] = ab[s][r];
-          act_bwd<ACT, NT, NX>(net.enc_param, z, abv, zb);
+          if constexpr (MRG) cadd(act_bwd_merged<ACT>(net.enc_param, mcoef(), z, abv, zb), true);
+          else act_bwd<ACT, NT, NX>(net.enc_param, z, abv, zb);
 #pragma unroll
           for (int s = 0; s < K; ++s) ab[s][r] = zb[s];
         }
-        u16_put<K>(X + ioff, ab);
+        if (enc_sums) u16_put<K>(X + ioff, ab);
       }
       U16_BARRIER(ST_ENC_BWD);
       const int te = u16_opaque(tid);  // keeps the pl addresses below out of the unit loop's live registers
-      if (te < H) {
+      if (enc_sums && te < H) {
         float gb = 0.0f, gt = 0.0f, gx = 0.0f;
         float gw[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 4
@@ -845,7 +912,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     PINN_STAMP(ST_STAGE);
     float* src = (nl & 1) ? X : A2;
     float* dst = (nl & 1) ? A2 : X;
-    u16_encode<ACT, NT, NX>(net, ep, xin, src, tp);
+    u16_encode<ACT, NT, NX, MRG>(net, ep, xin, src, tp, mcoef());
     U16_BARRIER(ST_ENCODE);
 
     // ---- hidden layers; the last one leaves its output-layer partials in UP ----
@@ -882,7 +949,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
               u16_get<K>(dst + eoff + 4 * j * kUP, v);
               v[0] += bias;
               f32x4 rec[K];
-              u16_ew_forward<ACT, NT, NX>(v, Ly.act_param, rec);
+              u16_ew_forward<ACT, NT, NX, MRG>(v, Ly.act_param, rec, mcoef());
               if constexpr (BWD) u16_put<K>(REC + l * img + eoff + 4 * j * kUP, rec);
               u16_put<K>(dst + eoff + 4 * j * kUP, v);
             }
@@ -890,7 +957,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
             u16_get<K>(dst + eoff + 4 * j * kUP, v);
             v[0] += bias;
             f32x4 rec[K];
-            u16_ew_forward<ACT, NT, NX>(v, Ly.act_param, rec);
+            u16_ew_forward<ACT, NT, NX, MRG>(v, Ly.act_param, rec, mcoef());
             if constexpr (BWD) u16_put<K>(A2 + eoff + 4 * j * kUP, rec);  // parked record
           }
           if (last) {  // output layer (H_last -> 1): the unit's reduction order
@@ -950,7 +1017,9 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           pde.c1 = X[1 * kUP + kUH + 2];
           pde.c2 = X[2 * kUP + kUH + 2];
           pde.c3 = X[3 * kUP + kUH + 2];
-          const float r = pde_residual<NT, NX>(pde, j, xin[pp], d);
+          float r;
+          if constexpr (MRG) r = pde_residual_merged(j, d);
+          else r = pde_residual<NT, NX>(pde, j, xin[pp], d);
           float dl;
           float lt = loss_term(pde, r, &dl);
           if (!ok) {
@@ -962,7 +1031,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           const float rb = !BWD ? 0.0f : a.res_bar ? (ok ? a.res_bar[p] : 0.0f) : a.grad_scale * dl;
 #pragma unroll
           for (int s = 0; s < K; ++s) ub[s] = rb * d[s];
-          if constexpr (COEF) {
+          if constexpr (COEF && !MRG) {
             float dc0, dc1;
             pde_coef_grads<NT, NX>(pde, j, xin[pp], dc0, dc1);
             if (writer) {
@@ -994,7 +1063,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
               float z[K], y[K];
 #pragma unroll
               for (int s = 0; s < K; ++s) z[s] = rec[s][r];
-              act_fwd_tape<ACT, NT, NX>(Lz.act_param, z, y);
+              u16_act_replay<ACT, NT, NX, MRG>(Lz.act_param, mcoef(), z, y);
               float gg = 0.0f;
 #pragma unroll
               for (int s = 0; s < K; ++s) gg = fmaf(ub[s], y[s], gg);
@@ -1002,7 +1071,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
             }
             *reinterpret_cast<f32x4*>(pdwp) = pdw;
           }
-          u16_ew_backward<ACT, NT, NX>(ab, Lz.act_param, rec);
+          cadd(u16_ew_backward<ACT, NT, NX, MRG>(ab, Lz.act_param, rec, mcoef()), sp == 0);
           u16_put<K>(rp, ab);
         }
       }
@@ -1050,7 +1119,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
                   float z[K], yy[K];
 #pragma unroll
                   for (int s = 0; s < K; ++s) z[s] = rec[s][r];
-                  act_fwd_tape<ACT, NT, NX>(pw, z, yy);
+                  u16_act_replay<ACT, NT, NX, MRG>(pw, mcoef(), z, yy);
 #pragma unroll
                   for (int s = 0; s < K; ++s) y[s][r] = yy[s];
                 }
@@ -1059,7 +1128,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
             }
           }
         } else {
-          u16_encode<ACT, NT, NX>(net, ep, xin, A2, tp);
+          u16_encode<ACT, NT, NX, MRG>(net, ep, xin, A2, tp, mcoef());
         }
         const unsigned coff = u16_cols_off(kon ? 16 * wv : 0, Ly.ld, cp, gp);
         if (need_abar) {
@@ -1099,7 +1168,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
                 if (kon) {
                   f32x4 ab[K];
                   u16_get<K>(xch + eoff + 4 * j * kUP, ab);
-                  u16_ew_backward<ACT, NT, NX>(ab, pw, rec);
+                  cadd(u16_ew_backward<ACT, NT, NX, MRG>(ab, pw, rec, mcoef()), sp == 0);
                   u16_put<K>(xch + eoff + 4 * j * kUP, ab);
                 }
               }
@@ -1117,11 +1186,35 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           else u16p_outer<K, NA0 + NKT, NKT, NPT>(pt, G, na, zl, al);
         }
         PINN_STAMP(ST_BWD_STREAM);
+        if constexpr (MRG && COEF) {  // the Fourier features' coefficient partial, as in a unit: the lanes of the w columns
+          if (l == 0 && net.enc == ENC_FOURIER && kon) {
+            f32x4 pa[kUPackMax];
+#pragma unroll
+            for (int j = 0; j < kUPackMax; ++j) pa[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            u16p_gemm<true>(pa, G, Ly.W, Ly.ld, coff, u16_wload<true>(Ly.W, Ly.ld, coff, 0), u16_wload<true>(Ly.W, Ly.ld, coff, 1),
+                            Ly.out_dim >> 4, X + boff);
+            const int M = net.enc_out >> 1;
+            float part = 0.0f;
+#pragma unroll
+            for (int j = 0; j < kUPackMax; ++j) {
+              if (j < G) {
+                const f32x4 val = *reinterpret_cast<const f32x4*>(A2 + eoff + 4 * j * kUP);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  const int jf = frowp + r;
+                  part = fmaf(pa[j][r], fourier_coef_partial_merged(ep[jf < M ? jf : jf - M], val[r]), part);
+                }
+              }
+            }
+            cadd(part, sp == 1);
+          }
+        }
       }
 
       // ---- encoding backward (first Linear of feedforward / SIREN) ----
-      if (net.enc == ENC_LINEAR && net.d_encW) {
+      if (net.enc == ENC_LINEAR && (net.d_encW || (MRG && COEF))) {
         const int H = net.enc_out;
+        const bool enc_sums = !(MRG && COEF) || net.d_encW != nullptr;
         U16_BARRIER(ST_ENC_BWD);
         if (16 * wv < H) {
 #pragma unroll
@@ -1135,16 +1228,17 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
                 u16_enc_preact<NT, NX>(ep, din, xin, frowp + r, 4 * j + qp, z);
 #pragma unroll
                 for (int s = 0; s < K; ++s) abv[s] = ab[s][r];
-                act_bwd<ACT, NT, NX>(net.enc_param, z, abv, zb);
+                if constexpr (MRG) cadd(act_bwd_merged<ACT>(net.enc_param, mcoef(), z, abv, zb), sp == 0);
+                else act_bwd<ACT, NT, NX>(net.enc_param, z, abv, zb);
 #pragma unroll
                 for (int s = 0; s < K; ++s) ab[s][r] = zb[s];
               }
-              u16_put<K>(X + eoff + 4 * j * kUP, ab);
+              if (enc_sums) u16_put<K>(X + eoff + 4 * j * kUP, ab);
             }
           }
         }
         U16_BARRIER(ST_ENC_BWD);
-        if (tp < H) {
+        if (enc_sums && tp < H) {
           float gb = 0.0f, gt = 0.0f, gx = 0.0f;
           float gw[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
           for (int n = 0; n < 4 * G; ++n) {
@@ -1190,7 +1284,20 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   if constexpr (!BWD) write_stamps();
 #endif
   if constexpr (!BWD) return;
-  if constexpr (COEF) {
+  if constexpr (COEF && MRG) {  // dL/dc_0 = -dL/dc: lanes -> waves -> the slab row's slot; c_1 has no cotangent
+    float sc = pcl[tf];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sc += __shfl_xor(sc, o);
+    if ((tf & 63) == 0) UP[wv] = sc;
+    __syncthreads();
+    if (a.mode == MODE_PDE && a.pde.dcoef && tf == 0) {
+      float st = 0.0f;
+#pragma unroll
+      for (int w = 0; w < kUWaves; ++w) st += UP[w];
+      a.pde.dcoef[doff] = -st;
+      a.pde.dcoef[doff + 1] = 0.0f;
+    }
+  } else if constexpr (COEF) {
     if (a.mode == MODE_PDE && a.pde.dcoef && wv == 0) {
       float s0 = tf < kU ? X[tf * kUP + kUH] : 0.0f, s1 = tf < kU ? X[tf * kUP + kUH + 1] : 0.0f;
 #pragma unroll
@@ -1275,6 +1382,8 @@ inline size_t jet_u16_lds_bytes(int K) {
   return sizeof(float) * ((size_t)4 * K * kUImgS + kUWaves * K * kU + 2 * kMaxDin * kU + (1 + kPersist) * kUH +
                           (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH + 4 * kUThreads + 2 * kU + kMaxDin * kU);
 }
+// the merged units: K = 3; the COEF form has its per-lane dL/dc sums (pcl) behind everything else
+inline size_t jet_u16m_lds_bytes(bool coef) { return jet_u16_lds_bytes(3) + (coef ? sizeof(float) * kUThreads : 0); }
 
 
 // The 16-point kernel can run the reverse launch of this network, and then runs its forward-only launches too (the
@@ -1307,6 +1416,24 @@ hipError_t launch_jet_u16_coef(const KernelArgs& a, int grid, hipStream_t stream
   hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16_lds_bytes(K), stream, a);
+  return hipGetLastError();
+}
+
+// the merged units (MRG = true): forward-only / reverse, and the COEF reverse launch
+template <int ACT>
+hipError_t launch_jet_u16m_act(const KernelArgs& a, bool bwd, int grid, hipStream_t stream) {
+  auto kern = bwd ? jet_kernel_u16<ACT, 1, 1, true, 4, false, true> : jet_kernel_u16<ACT, 1, 1, false, 4, false, true>;
+  hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(false), stream, a);
+  return hipGetLastError();
+}
+template <int ACT>
+hipError_t launch_jet_u16m_coef(const KernelArgs& a, int grid, hipStream_t stream) {
+  auto kern = jet_kernel_u16<ACT, 1, 1, true, 4, true, true>;
+  hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(true), stream, a);
   return hipGetLastError();
 }
 

@@ -57,6 +57,15 @@ PINN_DECLC(uc, 2, 0)
 #undef PINN_DECLC1
 #endif
 
+/* merged stream set (Burgers on three streams): jet_u16m_<family>, jet_u16mc_<family> */
+#if !defined(PINN_DEV)
+#define PINN_DECLM(a) hipError_t launch_jetum_a##a(const KernelArgs&, bool, int, hipStream_t); hipError_t launch_jetumc_a##a(const KernelArgs&, int, hipStream_t);
+PINN_DECLM(0) PINN_DECLM(1) PINN_DECLM(2) PINN_DECLM(3) PINN_DECLM(4)
+#undef PINN_DECLM
+#elif defined(PINN_DEV_MERGED)
+hipError_t launch_jetum_a0(const KernelArgs&, bool, int, hipStream_t);
+#endif
+
 #ifdef PINN_STAMPS
 static unsigned long long* g_stamps = nullptr;  // diagnostic builds only: device buffer for in-kernel phase timing
 #endif
@@ -400,6 +409,48 @@ static bool u16_unit_packed(const NetDev& n, int nt, int nx, bool coef) {
   return strstr(pinn_build_info(), unit) == nullptr;
 }
 
+// The merged units (jet_kernel_u16.h, MRG) run the residual-mode calls of 1-D Burgers on the stream set (1,2) with three
+// streams instead of four.  The answer is a function of the descriptor, the PDE and the build alone, the same for
+// forward-only, fused, res_bar and inverse calls, so their per-point residuals stay bit-identical: both four-stream u16
+// units (plain and COEF) must take the descriptor, and both merged units of the family must be routable (the dev build
+// has no COEF units at all and asks for the one it has).  PINN_FLAG_PLAIN_STREAMS keeps the four-stream units.
+static bool use_merged(const PinnNetDesc* d, const NetDev& n, const PinnPdeDesc* pde, int nt, int nx, int mode) {
+  if (mode != MODE_PDE || !pde || pde->kind != PINN_PDE_BURGERS || pde->dimension != 1 || nt != 1 || nx != 2) return false;
+  if (d->flags & PINN_FLAG_PLAIN_STREAMS) return false;
+  const int fam = jet_wide_act_family(n);
+#if defined(PINN_DEV) && !defined(PINN_DEV_MERGED)
+  return false;
+#elif defined(PINN_DEV)
+  return fam == PINN_ACT_TANH && use_u16(d, n, nt, nx, true, false);
+#else
+  if (!use_u16(d, n, nt, nx, true, false) || !use_u16(d, n, nt, nx, true, true)) return false;
+  char unit[64];
+  snprintf(unit, sizeof(unit), "jet_u16m_%d:", fam);
+  if (strstr(pinn_build_info(), unit)) return false;
+  snprintf(unit, sizeof(unit), "jet_u16mc_%d:", fam);
+  return strstr(pinn_build_info(), unit) == nullptr;
+#endif
+}
+
+static bool u16m_unit_packed(const NetDev& n, bool coef) {
+  char unit[64];
+  snprintf(unit, sizeof(unit), coef ? "nopack jet_u16mc_%d " : "nopack jet_u16m_%d ", jet_wide_act_family(n));
+  return strstr(pinn_build_info(), unit) == nullptr;
+}
+
+static hipError_t dispatch_u16m(bool coef, const KernelArgs& a, bool bwd, int grid, hipStream_t st) {
+  [[maybe_unused]] const int fam = jet_wide_act_family(a);
+#if !defined(PINN_DEV)
+#define PINN_MCASE(A_) \
+  if (fam == A_) return coef ? launch_jetumc_a##A_(a, grid, st) : launch_jetum_a##A_(a, bwd, grid, st);
+  PINN_MCASE(0) PINN_MCASE(1) PINN_MCASE(2) PINN_MCASE(3) PINN_MCASE(4)
+#undef PINN_MCASE
+#elif defined(PINN_DEV_MERGED)
+  if (!coef && fam == 0) return launch_jetum_a0(a, bwd, grid, st);
+#endif
+  return hipErrorInvalidValue;
+}
+
 // reverse launch of a COEF unit: the 16-point kernel (u16) or the 32-point one
 static hipError_t dispatch_coef(bool u16, int nt, int nx, const KernelArgs& a, int grid, hipStream_t st) {
 #ifndef PINN_DEV
@@ -572,8 +623,10 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
         if (em != hipSuccess) return fail(PINN_ERR_HIP, "HIP error %d: %s", (int)em, hipGetErrorString(em));
       }
     }
-    if (u16) jet_u16_set_plan(a, grid, u16_unit_packed(a.net, nt, nx, inverse));
-    hipError_t e = inverse ? dispatch_coef(u16, nt, nx, a, grid, static_cast<hipStream_t>(stream))
+    const bool merged = u16 && use_merged(net, a.net, pde, nt, nx, mode);
+    if (u16) jet_u16_set_plan(a, grid, merged ? u16m_unit_packed(a.net, inverse) : u16_unit_packed(a.net, nt, nx, inverse));
+    hipError_t e = merged  ? dispatch_u16m(inverse, a, bwd, grid, static_cast<hipStream_t>(stream))
+                   : inverse ? dispatch_coef(u16, nt, nx, a, grid, static_cast<hipStream_t>(stream))
                    : u16   ? dispatch_u16(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream))
                            : dispatch_wide(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(PINN_ERR_HIP, "HIP error %d: %s", (int)e, hipGetErrorString(e));
