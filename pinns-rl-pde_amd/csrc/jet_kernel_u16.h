@@ -25,6 +25,10 @@
 //     during the current unit, so a unit starts with one barrier.  In the reverse sweep the two waves of a SIMD
 //     (w and w + 4) run a layer's two GEMMs in opposite order, so that the activation adjoint of each (VALU) runs
 //     beside a GEMM of the other.  Ten barriers per unit for three MFMA layers behind Fourier features.
+//   * Reverse launches of the merged units (K = 3) have LDS for a fifth image S and keep what the forward sweep wrote:
+//     static image roles, the last layer's record in S, every zbar stored over the record it was computed from, so a
+//     reverse layer is one barrier and two GEMMs, without the put and the replay (KEEP in the kernel; eight barriers per
+//     unit for the network above; DESIGN.md §4.1 has the table of who reads and writes which image when).
 //   * Registers.  The reverse kernel sits at the 256-VGPR limit of two waves per SIMD, and what the optimizer hoists
 //     out of the unit loop is spilled.  So running sums that one phase alone touches (dw_out per lane, loss, db_out)
 //     and the PDE coefficients live in LDS, and addresses used once per unit or once per kernel are formed from an
@@ -449,7 +453,11 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   float* X = smem;                    // forward activations (ping-pong with A2); zbar in the reverse sweep
   float* A2 = X + img;                // forward activations; the last layer's parked record; reverse sweep: a_{l-1}
   float* REC = A2 + img;              // records of layers 0, 1 (replayed in the reverse sweep)
-  float* UP = REC + 2 * img;          // kUWaves * K * kU: per-wave partial sums of the output layer
+  // Reverse launches of the merged units keep a fifth image S: the last layer's record is parked there, X and A2 keep
+  // the forward activations, and every zbar_l is stored over the record it was computed from (S, REC[l]).
+  constexpr bool KEEP = MRG && BWD;
+  [[maybe_unused]] float* S = REC + 2 * img;
+  float* UP = REC + (KEEP ? 3 : 2) * img;  // kUWaves * K * kU: per-wave partial sums of the output layer
   float* xin2 = UP + kUWaves * K * kU;  // 2 * kMaxDin * kU: coordinates of this unit and of the workgroup's next one
   float* wb = xin2 + 2 * kMaxDin * kU;     // (1 + n_layers) * 128: w_out, then the hidden-layer biases
   float* ep = wb + (1 + kPersist) * kUH;  // (kMaxDin + 1) * 128: encoding parameters
@@ -577,8 +585,10 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     // The forward sweep ping-pongs between X and A2: layer l reads one image and puts its activations into the other,
     // so a layer boundary is one barrier.  The encoding goes where the parity of n_layers makes the LAST layer read X:
     // its record is then parked in A2 and the reverse sweep finds zbar -> X, a_{l-1} -> A2 for every n_layers.
-    float* src = (nl & 1) ? X : A2;
-    float* dst = (nl & 1) ? A2 : X;
+    // The merged units have static roles instead: the encoding in X, a_l in A2 for even l and in X for odd l, the last
+    // layer's record in S; their reverse sweep reads the activations where the forward sweep left them.
+    float* src = (MRG || (nl & 1)) ? X : A2;
+    float* dst = (MRG || (nl & 1)) ? A2 : X;
     u16_encode<ACT, NT, NX, MRG>(net, ep, xin, src, u16_opaque(tid), mcoef());  // opaque: addresses formed here, not held over the loop
     U16_BARRIER(ST_ENCODE);
 
@@ -615,9 +625,9 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         src = dst;
         dst = t;
       } else if (on) {  // last hidden layer: activations stay in acc, the record is parked in this wave's columns of A2
-        f32x4 rec[K];
+        f32x4 rec[K];   // (merged units: of S)
         u16_ew_forward<ACT, NT, NX, MRG>(acc, Ly.act_param, rec, mcoef());
-        if constexpr (BWD) u16_put<K>(A2 + ioff, rec);
+        if constexpr (BWD) u16_put<K>((KEEP ? S : A2) + ioff, rec);
       }
     }
     PINN_STAMP(ST_FWD_EW);
@@ -703,7 +713,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       for (int s = 0; s < K; ++s) ab[s] = w4 * ub[s];
       if (16 * wv < Lz.out_dim) {
         f32x4 rec[K];
-        u16_get<K>(A2 + ioff, rec);
+        u16_get<K>((KEEP ? S : A2) + ioff, rec);
         float* const pdwp = pdwl + 4 * u16_opaque(tid);
         f32x4 pdw = *reinterpret_cast<const f32x4*>(pdwp);
 #pragma unroll
@@ -711,7 +721,12 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           float z[K], y[K];
 #pragma unroll
           for (int s = 0; s < K; ++s) z[s] = rec[s][r];
-          u16_act_replay<ACT, NT, NX, MRG>(Lz.act_param, mcoef(), z, y);
+          if constexpr (KEEP) {  // the last layer's activations are still in acc
+#pragma unroll
+            for (int s = 0; s < K; ++s) y[s] = acc[s][r];
+          } else {
+            u16_act_replay<ACT, NT, NX, MRG>(Lz.act_param, mcoef(), z, y);
+          }
           float gg = 0.0f;
 #pragma unroll
           for (int s = 0; s < K; ++s) gg = fmaf(ub[s], y[s], gg);
@@ -719,6 +734,8 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         }
         *reinterpret_cast<f32x4*>(pdwp) = pdw;
         cadd(u16_ew_backward<ACT, NT, NX, MRG>(ab, Lz.act_param, rec, mcoef()), true);
+        // zbar of the last layer goes over the record it came from: that word is this lane's alone
+        if constexpr (KEEP) u16_put<K>(S + ioff, ab);
       }
     }
     PINN_STAMP(ST_B0);
@@ -730,10 +747,19 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       const bool kon = 16 * wv < Ly.in_dim;  // this wave owns input-feature rows of the layer
       // the GEMMs of layer l+1 have finished reading X (zbar) and A2; with a single MFMA layer the barrier keeps
       // u16_encode (all columns of A2, below) from overwriting another wave's parked record before its B0 has read it
-      if (l + 1 < nl || nl == 1) U16_BARRIER(ST_BWD_EW);
-      if (on) u16_put<K>(X + ioff, ab);
+      if constexpr (!KEEP) {
+        if (l + 1 < nl || nl == 1) U16_BARRIER(ST_BWD_EW);
+        if (on) u16_put<K>(X + ioff, ab);
+      }
+      // The layer's operands: zbar_l in ZB, a_{l-1} in AP.  Merged units: zbar_l lies over the record of layer l (B0 and
+      // the adjoint behind layer l+1's abar GEMM stored it there) and a_{l-1} where the forward sweep put it, so the
+      // layer needs no put, no replay and one barrier (DESIGN.md §4.1 lists every interval's readers and writers).
+      const float* const ZB = !KEEP ? X : l + 1 == nl ? S : REC + l * img;
+      const float* const AP = !KEEP || (l & 1) ? A2 : X;
       float pw = 0.0f;  // act_param of layer l-1
-      if (l > 0) {
+      if constexpr (KEEP) {
+        if (l > 0) pw = uniform_layer(net.layer[l - 1]).act_param;
+      } else if (l > 0) {
         const LayerDev P = uniform_layer(net.layer[l - 1]);
         pw = P.act_param;
         if (kon) {  // replay a_{l-1} from its record into this wave's columns of A2
@@ -762,7 +788,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       if (Ly.db && tid < Ly.out_dim) {
         float gsum = 0.0f;
 #pragma unroll
-        for (int n = 0; n < kU; ++n) gsum += X[n * kUP + tid];
+        for (int n = 0; n < kU; ++n) gsum += ZB[n * kUP + tid];
         pl[l * kUH + tid] += gsum;
       }
       PINN_STAMP(ST_BWD_DB);
@@ -776,8 +802,8 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       for (int half = 0; half < 2; ++half) {
         // dW (persistent tiles): first for waves 4-7, last for waves 0-3
         if ((half == 0) == dw_first && on && Ly.dW) {
-          const float* zl = X + 4 * g * kUP + 16 * wv + c;
-          const float* al = A2 + 4 * g * kUP + c;
+          const float* zl = ZB + 4 * g * kUP + 16 * wv + c;
+          const float* al = AP + 4 * g * kUP + c;
           const int na = Ly.in_dim >> 4;
           if (l == 0) u16_outer<K, 0, NA0, NPT>(pt, na, zl, al);
           else if (l == 1) u16_outer<K, NA0, NKT, NPT>(pt, na, zl, al);
@@ -789,7 +815,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         if (need_abar) {
 #pragma unroll
           for (int s = 0; s < K; ++s) ab[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-          if (kon) u16_gemm<K, true>(ab, Ly.W, Ly.ld, coff, w0, w1, Ly.out_dim >> 4, X + c * kUP + 4 * g);
+          if (kon) u16_gemm<K, true>(ab, Ly.W, Ly.ld, coff, w0, w1, Ly.out_dim >> 4, ZB + c * kUP + 4 * g);
         }
         PINN_STAMP(ST_BWD_DX);
         // activation adjoint of layer l-1; the record is read here, not ahead of a GEMM
@@ -797,16 +823,25 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           f32x4 rec[K];
           u16_get<K>(REC + (l - 1) * img + ioff, rec);
           cadd(u16_ew_backward<ACT, NT, NX, MRG>(ab, pw, rec, mcoef()), true);
+          if constexpr (KEEP) u16_put<K>(REC + (l - 1) * img + ioff, ab);  // zbar_{l-1} over its record: this lane's word
         }
         PINN_STAMP(ST_BWD_EW);
       }
+      if constexpr (KEEP) {
+        // Three MFMA layers: a_1 has taken the encoding's place in X.  dW_2 was X's last reader (a barrier ago), dW_0
+        // reads the encoding behind the next barrier: it is formed again here, beside the partner wave's GEMMs.
+        if (l == 1 && nl > 2) {
+          u16_encode<ACT, NT, NX, MRG>(net, ep, xin, X, u16_opaque(tid), mcoef());
+          PINN_STAMP(ST_ENCODE);
+        }
+      }
       if constexpr (MRG && COEF) {
         // Fourier features depend on c through their w stream: dL/dc += sum_j abar_w,j e_j with e_j = -b_x^2 (value
-        // feature j).  abar_w = W0^T zbar_w is one single-stream GEMM; the value features are stream 0 of A2.
+        // feature j).  abar_w = W0^T zbar_w is one single-stream GEMM; the value features are stream 0 of the encoding.
         if (l == 0 && net.enc == ENC_FOURIER && kon) {
           f32x4 aw[1] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
           {  // a rolled loop: the unrolled, prefetching form of u16_gemm_n costs this unit scratch
-            const float* xl = X + kUImgS + c * kUP + 4 * g;
+            const float* xl = ZB + kUImgS + c * kUP + 4 * g;
             const int nb = Ly.out_dim >> 4;
 #pragma unroll 1
             for (int b = 0; b < nb; ++b) {
@@ -817,7 +852,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
             }
           }
           const int M = net.enc_out >> 1;
-          const f32x4 val = *reinterpret_cast<const f32x4*>(A2 + ioff);
+          const f32x4 val = *reinterpret_cast<const f32x4*>(AP + ioff);
           float part = 0.0f;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -1382,8 +1417,16 @@ inline size_t jet_u16_lds_bytes(int K) {
   return sizeof(float) * ((size_t)4 * K * kUImgS + kUWaves * K * kU + 2 * kMaxDin * kU + (1 + kPersist) * kUH +
                           (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH + 4 * kUThreads + 2 * kU + kMaxDin * kU);
 }
-// the merged units: K = 3; the COEF form has its per-lane dL/dc sums (pcl) behind everything else
-inline size_t jet_u16m_lds_bytes(bool coef) { return jet_u16_lds_bytes(3) + (coef ? sizeof(float) * kUThreads : 0); }
+// the merged units: K = 3; reverse launches have the fifth image S behind the record images; the COEF form has its
+// per-lane dL/dc sums (pcl) behind everything else
+constexpr size_t jet_u16m_lds_bytes(bool coef, bool bwd) {
+  return sizeof(float) * ((size_t)(bwd ? 5 : 4) * 3 * kUImgS + kUWaves * 3 * kU + 2 * kMaxDin * kU + (1 + kPersist) * kUH +
+                          (kMaxDin + 1) * kUH + (kPersist + kMaxDin + 1) * kUH + 4 * kUThreads + 2 * kU + kMaxDin * kU +
+                          (coef ? kUThreads : 0));
+}
+static_assert(jet_u16m_lds_bytes(true, true) <= 160 * 1024 && jet_u16m_lds_bytes(false, true) == 146048 &&
+                  jet_u16m_lds_bytes(false, false) == 120704,
+              "the merged units' five images and running sums fit the CU's LDS");
 
 
 // The 16-point kernel can run the reverse launch of this network, and then runs its forward-only launches too (the
@@ -1425,7 +1468,7 @@ hipError_t launch_jet_u16m_act(const KernelArgs& a, bool bwd, int grid, hipStrea
   auto kern = bwd ? jet_kernel_u16<ACT, 1, 1, true, 4, false, true> : jet_kernel_u16<ACT, 1, 1, false, 4, false, true>;
   hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(false), stream, a);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(false, bwd), stream, a);
   return hipGetLastError();
 }
 template <int ACT>
@@ -1433,7 +1476,7 @@ hipError_t launch_jet_u16m_coef(const KernelArgs& a, int grid, hipStream_t strea
   auto kern = jet_kernel_u16<ACT, 1, 1, true, 4, true, true>;
   hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(true), stream, a);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(true, true), stream, a);
   return hipGetLastError();
 }
 
