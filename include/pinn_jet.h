@@ -334,6 +334,44 @@ int pinn_fd_stencil_points(const float* x, const float* t, int64_t N, double eps
 int pinn_fd_smoothness(const float* u3, int64_t N, double eps, float weight, float* loss_out, float* cotangent3, float* summary4,
                        double* scratch, void* stream);
 
+/* ---- causal residual weights (no counterpart in pinnrl; Wang, Sankaran, Perdikaris 2022, "Respecting causality is all
+ * you need for training physics-informed neural networks") -----------------------------------------------------------
+ * The residual loss of late times is held back until the loss of earlier times is small.  The time domain [t_lo, t_hi] is
+ * cut into n_bins equal bins; the middle of the chain pinn_residual_forward -> pinn_causal_weights -> pinn_residual_backward.
+ *   bin of a point    b(n) = (int) min(max((t_n - (float)t_lo) * s, 0), n_bins - 1), s = (float)(n_bins / (t_hi - t_lo)) with the
+ *                     quotient in double; the subtraction and the product are one rounded fp32 operation each (no FMA):
+ *                     bit-equal to torch's ((t - lo) * s).clamp(0, n_bins - 1).to(int32).  t_hi and beyond: the last bin;
+ *                     below t_lo: bin 0.  t must be finite;
+ *   bin statistics    S_i = sum_{b(n) = i} l(r_n), c_i = the count, L_i = S_i / c_i (0 for an empty bin), in double, l = PinnLoss
+ *                     `loss` with l and l' as pinn_residual_loss_grad has them (sgn(0) = 0, Huber's quadratic branch on
+ *                     |r| < delta);
+ *   weights           w_i = (float) exp(-(double)eps_dev[0] * sum_{k < i} L_k), w_0 = 1: constants of the differentiation.
+ *                     eps_dev is a DEVICE scalar (>= 0, finite) read at launch time — the `lr` convention of
+ *                     pinn_adam_clip_step — so a captured graph follows a schedule of the sharpness;
+ *   cotangent         N floats, overwritten: cotangent[n] = grad_scale * w_b(n) * l'(r_n), fp32, the product taken as
+ *                     (grad_scale * w) * l' — the residual_cotangent of pinn_residual_backward;
+ *   loss_sum_out      nullable: loss_sum_out[0] += sum_i w_i S_i, the UNnormalised, count-weighted loss (the convention of
+ *                     pinn_residual_loss_grad: the caller divides by N).  With eps = 0 every weight is exactly 1 and this is
+ *                     the plain residual loss;
+ *   plain_sum_out     nullable: plain_sum_out[0] += sum_i S_i;  both are double sums in bin order, rounded once;
+ *   bin_losses        nullable, n_bins floats: L_i;   bin_weights: n_bins floats, REQUIRED (the third launch reads it);
+ *   scratch           PINN_CAUSAL_SCRATCH_DOUBLES doubles, 8-byte aligned.
+ * Three launches on `stream`, no synchronisation, no allocation, no atomics: a fixed grid of at most 64 blocks x 256 threads
+ * writes per-block, per-bin partial sums and counts (inside a wave the lanes of one bin are summed by a fixed butterfly,
+ * bin after bin; the four wave rows are added in wave order); one workgroup adds the partials in block order, takes the
+ * serial prefix in double and writes the weights and the two sums (the only launch that reads eps_dev); the third writes
+ * the cotangents, 16 bytes at a time where a buffer is 16-byte aligned and the quad is whole, scalar accesses otherwise.
+ * Two calls on the same inputs are bit-identical, whatever the alignment of the buffers.
+ * Checked on the host before any HIP call: n_bins outside [1, PINN_CAUSAL_MAX_BINS], t_hi <= t_lo or a non-finite bound, an
+ * unknown loss, N < 0, null residual / t / eps_dev / cotangent / bin_weights / scratch with N > 0: PINN_ERR_BAD_DESC;
+ * misaligned scratch: PINN_ERR_MISALIGNED.  N == 0: no-op. */
+#define PINN_CAUSAL_MAX_BINS 64
+#define PINN_CAUSAL_SCRATCH_DOUBLES (64 * 2 * PINN_CAUSAL_MAX_BINS) /* 64 blocks x (sum, count) x 64 bins; the finish pass works in LDS */
+int pinn_causal_weights(const float* residual, const float* t, int64_t N, int32_t n_bins, double t_lo, double t_hi,
+                        const float* eps_dev, int32_t loss, float huber_delta, float grad_scale, float* cotangent,
+                        float* loss_sum_out, float* plain_sum_out, float* bin_losses, float* bin_weights, double* scratch,
+                        void* stream);
+
 /* ---- residuals given as data (pinnrl: a user's PDEBase subclass, pinnrl/pdes/pde_base.py:574-588) ---------------------
  * A residual outside the nine compiled PDEs, as a sum of products of streams, coordinates and sin / cos of the value:
  *   r = sum_{m < n_terms} c_m prod_{f < n_factors[m]} phi_{m,f}

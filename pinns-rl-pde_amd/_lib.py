@@ -35,6 +35,8 @@ PINN_LBFGS_RECORD_DOUBLES = 72
 PINN_TERM_MAX_TERMS = 16
 PINN_TERM_MAX_FACTORS = 4
 PINN_TERM_SCRATCH_DOUBLES = 64 * (1 + PINN_TERM_MAX_TERMS)
+PINN_CAUSAL_MAX_BINS = 64
+PINN_CAUSAL_SCRATCH_DOUBLES = 64 * 2 * PINN_CAUSAL_MAX_BINS
 # PinnTermFactor: the factor codes of a residual given as data (pinn_term_residual)
 TERM_FACTOR = {"u": 0, "u_t": 1, "u_tt": 2, "u_x": 3, "u_xx": 4, "u_xxx": 5, "u_xxxx": 6, "x": 7, "t": 8, "sin(u)": 9, "cos(u)": 10}
 # the record of pinn_lbfgs_direction / pinn_lbfgs_eval_stats (doubles); from "dmax" on: 64 per-block partials of max|d|
@@ -47,7 +49,7 @@ EXPORTS = (
     "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name", "pinn_residual_loss_grad_inverse",
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
-    "pinn_unit_tail_plan", "pinn_term_residual",
+    "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights",
 )
 
 
@@ -196,6 +198,8 @@ def load():
         lib.pinn_unit_tail_plan.argtypes = [i64, i32, P(i64), P(i32), P(i64)]
         lib.pinn_term_residual.restype = ctypes.c_int
         lib.pinn_term_residual.argtypes = [P(PinnTermPde), vp, vp, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, vp]
+        lib.pinn_causal_weights.restype = ctypes.c_int
+        lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:
             raise JetLibraryError(f"libpinnjet.so ABI {lib.pinn_abi_version()} != expected {PINN_ABI_VERSION}: rebuild")
         _lib = lib

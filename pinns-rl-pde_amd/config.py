@@ -8,6 +8,7 @@ The YAML loader / validator (config/__init__.py:363-794) is orchestration and ou
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
@@ -53,6 +54,41 @@ class AdaptiveWeightsConfig:  # config/__init__.py:67-87
 
 
 @dataclass
+class CausalWeightingConfig:
+    """Causal (time-weighted) residual loss (Wang, Sankaran, Perdikaris 2022); no counterpart in `pinnrl.config`.
+
+    The time domain is cut into `num_bins` equal bins and the residual loss of bin i is weighted by
+    exp(-eps * sum of the mean losses of the earlier bins), the weights detached (pdes/pde_base.py::_residual_loss).
+    """
+
+    enabled: bool = False
+    num_bins: int = 16
+    eps: float = 1.0
+
+    MAX_BINS = 64  # PINN_CAUSAL_MAX_BINS
+
+    def __post_init__(self):
+        validate_causal_bins(self.num_bins)
+        self.eps = validate_causal_eps(self.eps)
+
+
+def validate_causal_bins(num_bins) -> int:
+    if isinstance(num_bins, bool) or not isinstance(num_bins, int) or not 1 <= num_bins <= CausalWeightingConfig.MAX_BINS:
+        raise ValueError(f"causal_weighting.num_bins must be an integer in [1, {CausalWeightingConfig.MAX_BINS}], got {num_bins!r}")
+    return num_bins
+
+
+def validate_causal_eps(eps) -> float:
+    try:
+        value = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"causal_weighting.eps must be a finite number >= 0, got {eps!r}") from None
+    if not math.isfinite(value) or value < 0.0:
+        raise ValueError(f"causal_weighting.eps must be a finite number >= 0, got {eps!r}")
+    return value
+
+
+@dataclass
 class TrainingConfig:  # config/__init__.py:90-169
     num_epochs: int = 100
     batch_size: int = 1024
@@ -73,6 +109,7 @@ class TrainingConfig:  # config/__init__.py:90-169
     mode: str = "forward"
     loss_function: str = "mse"
     huber_delta: float = 1.0
+    causal_weighting: CausalWeightingConfig = None
 
     def __post_init__(self):
         if self.early_stopping is None:
@@ -87,6 +124,10 @@ class TrainingConfig:  # config/__init__.py:90-169
             self.adaptive_weights = AdaptiveWeightsConfig()
         if self.lbfgs is None:
             self.lbfgs = LBFGSConfig()
+        if self.causal_weighting is None:
+            self.causal_weighting = CausalWeightingConfig()
+        elif isinstance(self.causal_weighting, dict):
+            self.causal_weighting = CausalWeightingConfig(**self.causal_weighting)
         if self.optimizer not in ("adam", "lbfgs", "adam_lbfgs"):
             raise ValueError(f"Invalid optimizer '{self.optimizer}'. Choose from 'adam', 'lbfgs', or 'adam_lbfgs'.")
         if self.mode not in ("forward", "inverse", "data_only", "data_augmented"):

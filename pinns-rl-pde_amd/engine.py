@@ -351,25 +351,28 @@ def term_residual(td: TermDesc, jets: Tensor, x: Tensor, t: Tensor, grad_scale: 
     return r, cot
 
 
-def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: bool = True) -> Tuple[Optional[Tensor], Tensor]:
-    """(residual (N,1) | None, loss_sum (1,)) with loss_sum = sum_n l(r_n) over THESE points."""
+def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: bool = True,
+                     want_loss_sum: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """(residual (N,1) | None, loss_sum (1,)) with loss_sum = sum_n l(r_n) over THESE points.  `want_loss_sum=False`: the
+    residual field alone, (residual, None) — no reduction, no zero-fill (what a launch list that reduces the residual
+    itself asks for)."""
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
     if isinstance(pd, TermDesc) and N:  # the chain: jets, then the element-wise residual
-        s = torch.zeros(1, dtype=torch.float32, device=dev)
+        s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
         r, _ = term_residual(pd, jets_forward(prog, x, t, pd.nt, pd.nx), x, t, want_residual=want_residual, loss_sum=s)
         return r, s
     r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
-    s = torch.zeros(1, dtype=torch.float32, device=dev)
+    s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
     if N:
         nt, nx = pde_streams(pd)
         ws, wptr, wn = _scratch(prog, dev, N, nt, nx, False)
         with torch.cuda.device(dev):
             _lib.check(lib.pinn_residual_forward(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors,
                                                  ctypes.byref(pd), x.data_ptr(), t.data_ptr(), N,
-                                                 r.data_ptr() if want_residual else None, s.data_ptr(), wptr, wn,
-                                                 _stream(dev)))
+                                                 r.data_ptr() if want_residual else None,
+                                                 s.data_ptr() if want_loss_sum else None, wptr, wn, _stream(dev)))
     return r, s
 
 
@@ -549,6 +552,50 @@ def fd_smoothness(u3: Tensor, eps: float, weight: float, loss_out: Tensor, cot3:
     with torch.cuda.device(dev):
         _lib.check(lib.pinn_fd_smoothness(u3.data_ptr(), N, float(eps), float(weight), loss_out.data_ptr(), cot3.data_ptr(),
                                           summary4.data_ptr() if summary4 is not None else None, scratch.data_ptr(), _stream(dev)))
+
+
+def causal_weights(r: Tensor, t: Tensor, n_bins: int, t_lo: float, t_hi: float, eps_dev: Tensor, loss: str, huber_delta: float,
+                   grad_scale: float, loss_sum: Optional[Tensor] = None, plain_sum: Optional[Tensor] = None,
+                   cot: Optional[Tensor] = None, bin_losses: Optional[Tensor] = None, bin_weights: Optional[Tensor] = None,
+                   scratch: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Causal (time-weighted) residual loss on a residual field (`pinn_causal_weights`): returns (cot (N,), bin_losses (M,),
+    bin_weights (M,)) with M = n_bins bins of [t_lo, t_hi], bin_losses[i] = the mean of l(r) over bin i (0 when empty),
+    bin_weights[i] = exp(-eps * sum_{k<i} bin_losses[k]) (detached; eps = eps_dev[0], a device scalar read at launch time) and
+    cot[n] = grad_scale * bin_weights[b(n)] * l'(r_n), the `res_bar` of `residual_backward`.  loss_sum[0] += sum_n w l(r_n)
+    and plain_sum[0] += sum_n l(r_n) where given (unnormalised).  r, t: N contiguous float32 values; cot / bin_losses /
+    bin_weights / scratch (PINN_CAUSAL_SCRATCH_DOUBLES float64): caller-owned buffers to write into, allocated when None.
+    Three launches, no atomics: bit-identical across runs and alignments."""
+    lib = _lib.load()
+    dev = _require_device(r, t, eps_dev, loss_sum, plain_sum, cot, bin_losses, bin_weights, scratch)
+    if loss not in _lib.LOSS:
+        raise ValueError(f"causal_weights: unknown loss '{loss}'")
+    M = int(n_bins)
+    if not 1 <= M <= _lib.PINN_CAUSAL_MAX_BINS:
+        raise ValueError(f"causal_weights: n_bins must be in [1, {_lib.PINN_CAUSAL_MAX_BINS}], got {n_bins}")
+    for tns in (r, t, eps_dev, loss_sum, plain_sum, cot, bin_losses, bin_weights):
+        if tns is not None and (tns.dtype != torch.float32 or not tns.is_contiguous()):
+            raise ValueError("causal_weights: contiguous float32 buffers only")
+    N = r.numel()
+    if t.numel() != N:
+        raise ValueError(f"causal_weights: r holds {N} values, t {t.numel()}")
+    if eps_dev.numel() < 1 or (loss_sum is not None and loss_sum.numel() < 1) or (plain_sum is not None and plain_sum.numel() < 1):
+        raise ValueError("causal_weights: eps_dev, loss_sum and plain_sum hold at least one value")
+    cot = torch.empty(N, dtype=torch.float32, device=dev) if cot is None else cot
+    bin_losses = torch.zeros(M, dtype=torch.float32, device=dev) if bin_losses is None else bin_losses
+    bin_weights = torch.ones(M, dtype=torch.float32, device=dev) if bin_weights is None else bin_weights
+    if cot.numel() != N or bin_losses.numel() != M or bin_weights.numel() != M:
+        raise ValueError("causal_weights: cot holds N values, bin_losses and bin_weights n_bins each")
+    if scratch is None:
+        scratch = torch.empty(_lib.PINN_CAUSAL_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)
+    if scratch.dtype != torch.float64 or not scratch.is_contiguous() or scratch.numel() < _lib.PINN_CAUSAL_SCRATCH_DOUBLES:
+        raise ValueError("causal_weights: scratch holds PINN_CAUSAL_SCRATCH_DOUBLES contiguous float64 values")
+    opt = lambda a: a.data_ptr() if a is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_causal_weights(r.data_ptr(), t.data_ptr(), N, M, float(t_lo), float(t_hi), eps_dev.data_ptr(),
+                                           _lib.LOSS[loss], float(huber_delta), float(grad_scale), cot.data_ptr(), opt(loss_sum),
+                                           opt(plain_sum), bin_losses.data_ptr(), bin_weights.data_ptr(), scratch.data_ptr(),
+                                           _stream(dev)))
+    return cot, bin_losses, bin_weights
 
 
 def adam_clip_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, lr: Tensor, step: Tensor,

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import engine as _E
+from ..config import validate_causal_bins, validate_causal_eps
 
 # compiled (time_order, space_order) stream sets, see csrc/Makefile
 _STREAM_SETS = [(0, 0), (1, 0), (1, 1), (1, 2), (1, 3), (1, 4), (2, 0), (2, 2)]
@@ -53,6 +54,30 @@ def _pick_stream_set(nt: int, nx: int) -> Tuple[int, int]:
     if best is None:
         raise NotImplementedError(f"pinnrl_amd: no compiled jet kernel covers time order {nt} with space order {nx}")
     return best
+
+
+def causal_bins(t: torch.Tensor, num_bins: int, t_lo: float, t_hi: float) -> torch.Tensor:
+    """Time bin of every point, int32 in [0, num_bins): the fp32 formula of `pinn_causal_weights` (include/pinn_jet.h), one
+    rounded operation each — a subtraction of (float)t_lo, a product with (float)(num_bins / (t_hi - t_lo)), the clamp."""
+    lo = torch.tensor(float(t_lo), dtype=torch.float32).item()
+    scale = torch.tensor(float(num_bins) / (float(t_hi) - float(t_lo)), dtype=torch.float64).to(torch.float32).item()
+    return ((t.reshape(-1).to(torch.float32) - lo) * scale).clamp(0, num_bins - 1).to(torch.int32)
+
+
+def causal_residual_loss(point_losses: torch.Tensor, t: torch.Tensor, num_bins: int, eps: float, t_lo: float,
+                         t_hi: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(L, w): the causal residual loss L = (1/N) sum_n w_b(n) l_n of per-point losses l_n = l(r_n) and its (num_bins,) float32
+    weights w_i = exp(-eps sum_{k<i} L_k), L_k the mean of l over bin k (0 when empty); sums, means, prefix and exp in
+    float64, the weights detached.  Count-weighted (a mean over points, not over bins): eps = 0 gives the plain mean."""
+    l = point_losses.reshape(-1)
+    b = causal_bins(t, num_bins, t_lo, t_hi).to(torch.int64)
+    with torch.no_grad():
+        sums = torch.zeros(num_bins, dtype=torch.float64, device=l.device).index_add_(0, b, l.detach().to(torch.float64))
+        counts = torch.bincount(b, minlength=num_bins).to(torch.float64)
+        means = torch.where(counts > 0, sums / counts.clamp(min=1.0), torch.zeros_like(sums))
+        prefix = torch.cumsum(means, 0) - means
+        weights = torch.exp(-float(eps) * prefix).to(torch.float32)
+    return (weights[b] * l).sum() / float(l.numel()), weights
 
 
 def _jets_of(model) -> Any:
@@ -169,6 +194,26 @@ class PDEBase:
 
     def _training_mode(self) -> str:
         return str(self._training_attr("mode", "forward"))
+
+    def _causal_weighting(self) -> Optional[Tuple[int, float]]:
+        """(num_bins, eps) of `config.training.causal_weighting` when it is enabled (config.CausalWeightingConfig or a dict of
+        its fields), else None."""
+        cw = self._training_attr("causal_weighting", None)
+        if cw is None:
+            return None
+        get = cw.get if isinstance(cw, dict) else (lambda key, default=None: getattr(cw, key, default))
+        if not get("enabled", False):
+            return None
+        return validate_causal_bins(get("num_bins", 16)), validate_causal_eps(get("eps", 1.0))
+
+    def _pointwise_loss(self, error: torch.Tensor) -> torch.Tensor:
+        """l(error) per sample: `_apply_loss_fn` without its mean."""
+        name = self._loss_function_name()
+        if name == "mae":
+            return torch.abs(error)
+        if name == "huber":
+            return torch.nn.functional.huber_loss(error, torch.zeros_like(error), reduction="none", delta=self._huber_delta())
+        return error**2
 
     def _apply_loss_fn(self, error: torch.Tensor) -> torch.Tensor:  # pde_base.py:309-326
         name = self._loss_function_name()
@@ -555,7 +600,18 @@ class PDEBase:
 
     # ---------------------------------------------------------------- losses (pde_base.py:1086-1235)
     def _residual_loss(self, model, x: torch.Tensor, t: torch.Tensor, n_total: Optional[int] = None) -> torch.Tensor:
-        """mean_n l(r_n): residual, reduction AND dL/dtheta in one launch when the coefficients are plain numbers."""
+        """mean_n l(r_n): residual, reduction AND dL/dtheta in one launch when the coefficients are plain numbers.  With
+        `training.causal_weighting` enabled: the time-weighted mean (1/N) sum_n w_b(n) l(r_n) of `causal_residual_loss` on the
+        residual field of `compute_residual` — differentiable in theta and in trainable coefficients, the weights detached."""
+        causal = self._causal_weighting()
+        if causal is not None:
+            r = self.compute_residual(model, x, t)
+            loss, weights = causal_residual_loss(self._pointwise_loss(r), t.detach().to(r.device), causal[0], causal[1],
+                                                 self.time_domain[0], self.time_domain[1])
+            self._causal_last_weights = weights
+            if n_total is not None and int(n_total) != x.shape[0]:
+                loss = loss * (float(x.shape[0]) / float(n_total))
+            return loss
         if self._has_trainable_coefficients():
             coefs = [c if isinstance(c, torch.Tensor) else torch.tensor(float(c), dtype=torch.float32, device=self.device)
                      for c in self._coefficients()]

@@ -159,7 +159,9 @@ class TermPDE(PDEBase):
         return self._residual_from_jets(jets, x, self._nt, self._nx, t).unsqueeze(1)
 
     def _residual_loss(self, model, x, t, n_total=None):
-        if not self._has_trainable_coefficients():
+        if not self._has_trainable_coefficients() or self._causal_weighting() is not None:
+            # causal weighting: the base method weights the residual field of `compute_residual` above, whose torch
+            # formula keeps a trainable coefficient in the graph
             return super()._residual_loss(model, x, t, n_total)
         loss = self._apply_loss_fn(self.compute_residual(model, x, t))
         if n_total is not None and int(n_total) != x.shape[0]:  # shard of a data-parallel batch: local SUM / global N

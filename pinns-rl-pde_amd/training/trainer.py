@@ -27,7 +27,8 @@ import torch.optim as optim
 
 from .. import distributed as _D
 from .. import engine as _E
-from .._lib import LBFGS_REC, PINN_ADAPTIVE_SCRATCH_FLOATS, PINN_FD_SCRATCH_DOUBLES, PINN_LBFGS_MAX_HISTORY, PINN_LBFGS_RECORD_DOUBLES
+from .._lib import LBFGS_REC, PINN_ADAPTIVE_SCRATCH_FLOATS, PINN_CAUSAL_SCRATCH_DOUBLES, PINN_FD_SCRATCH_DOUBLES, PINN_LBFGS_MAX_HISTORY, PINN_LBFGS_RECORD_DOUBLES
+from ..config import validate_causal_eps
 from .lbfgs import LBFGSDriver
 
 
@@ -121,6 +122,15 @@ class PDETrainer:
         # fast_step: None = `train()` takes the autograd-free launch list whenever it covers the configuration
         # (`_manual_step_unsupported()` is None) and the device is a GPU; False = always the autograd step; True = require it
         self.fast_step = fast_step
+        if self._causal is not None:
+            if process_group is not None:
+                raise NotImplementedError("causal weighting under a process group: the bin means would need their own collective")
+            if getattr(config.training, "optimizer", "adam") != "adam":
+                raise NotImplementedError("causal weighting with L-BFGS: the weights are detached, so the function the line "
+                                          "search sees is not the one the gradient belongs to")
+            t_lo, t_hi = float(self.pde.time_domain[0]), float(self.pde.time_domain[1])
+            if not (np.isfinite(t_lo) and np.isfinite(t_hi) and t_hi > t_lo):
+                raise ValueError(f"causal weighting needs a finite time domain with t_hi > t_lo, got ({t_lo}, {t_hi})")
         if process_group is not None:
             # replicas must start from ONE theta_0 and apply identical updates: broadcast rank 0's parameters,
             # and refuse the modes whose per-rank quantities this path does not reduce
@@ -148,6 +158,24 @@ class PDETrainer:
         )
         self._pending_weights: List[torch.Tensor] = []  # device copies of the launch-list steps' weights, see `_flush_loss_weights`
         self.points_history: List[np.ndarray] = []
+
+    @property
+    def _causal(self):
+        """(num_bins, eps) of the causal weighting, or None when it is off — read from the PDE's training config on every
+        use, the one place the autograd path (`PDEBase._residual_loss`) reads it from too."""
+        return self.pde._causal_weighting() if hasattr(self.pde, "_causal_weighting") else None
+
+    def _sync_causal_state(self, F, causal):
+        """Bring the launch list's device-side sharpness in step with the config before an eager step.  The bin count sizes
+        persistent buffers, so it is fixed once the flat state exists.  Not during graph capture: a captured fill would
+        reset the sharpness on every replay; a captured step follows `set_causal_eps` alone."""
+        built = F.get("causal_host")
+        if built is None or built[0] != causal[0]:
+            raise RuntimeError("causal_weighting was enabled, or its num_bins changed, after the trainer's flat state was built: "
+                               "build a new PDETrainer")
+        if built[1] != causal[1] and not (F["causal_eps"].is_cuda and torch.cuda.is_current_stream_capturing()):
+            F["causal_eps"].fill_(causal[1])
+            F["causal_host"] = causal
 
     # ---------------------------------------------------------------- optimizer / scheduler (trainer.py:281-371)
     def _collect_optimizable_params(self):
@@ -449,6 +477,17 @@ class PDETrainer:
             return "RL agent without a device-side action selection"
         if getattr(tc, "collocation_distribution", "uniform") not in ("uniform", "stratified", "residual_based"):
             return "unknown sampler"
+        if self._causal is not None:
+            # causal weighting: the residual launch becomes forward -> pinn_causal_weights -> reverse; that chain covers a
+            # forward problem with fixed loss weights and coefficients by value
+            if self.use_adaptive_weights:
+                return "causal weighting with adaptive loss weights"
+            if len(getattr(self.pde, "_trainable_params", {})) or self.pde._has_trainable_coefficients():
+                return "causal weighting with trainable PDE coefficients"
+            if self.pde._training_mode() != "forward" or getattr(self.pde, "observation_data", None):
+                return "causal weighting with a data mode or an observation-data term"
+            if (self.pde._loss_weights() or {}).get("smoothness", 0.0) > 0 and type(self.pde).compute_loss is not PDEBase.compute_loss:
+                return "causal weighting with a smoothness term"
         if isinstance(self.pde, TermPDE):
             # a residual given as data runs the launch list through the chain jets -> pinn_term_residual -> reverse sweep
             # (engine.residual_loss_grad dispatches on the descriptor), with its coefficients by value on the device
@@ -616,6 +655,14 @@ class PDETrainer:
                                                 self.pde._huber_delta())})
         F = self._flat
         F["extra"] = torch.zeros(2, dtype=torch.float32, device=dev)  # {initial, data} when the chain carries a data term
+        if self._causal is not None:
+            # causal weighting: the sharpness as a device scalar (read at launch time: `set_causal_eps`), the bin means and
+            # weights of the last step and the partial sums of pinn_causal_weights
+            M, eps = self._causal
+            F.update({"causal_host": (M, eps), "causal_eps": torch.tensor([eps], dtype=torch.float32, device=dev),
+                      "causal_losses": torch.zeros(M, dtype=torch.float32, device=dev),
+                      "causal_w": torch.ones(M, dtype=torch.float32, device=dev),
+                      "causal_scratch": torch.zeros(PINN_CAUSAL_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)})
         if self.pde._manual_smoothness() is not None:
             F["smooth_loss"] = torch.zeros(1, dtype=torch.float32, device=dev)  # the unweighted smoothness term of the last step
         if self.use_adaptive_weights:
@@ -675,6 +722,8 @@ class PDETrainer:
                     ch["term_losses_" + half] = torch.zeros(len(terms), dtype=torch.float32, device=dev)
                     ch["cot_" + half] = torch.zeros(K, npts, dtype=torch.float32, device=dev)
                     ch["summary_" + half] = torch.zeros(4, dtype=torch.float32, device=dev)
+            if "causal_eps" in F:
+                ch["causal_cot"] = torch.zeros(int(n_batch), dtype=torch.float32, device=dev)  # the residual's cotangents
             sm = self.pde._manual_smoothness()
             if sm is not None:
                 # the finite-difference smoothness term on the collocation batch: its 3 n_batch stencil points, the
@@ -729,6 +778,19 @@ class PDETrainer:
         loss_name, delta = self.pde._loss_function_name(), self.pde._huber_delta()
 
         def residual_launch():
+            causal = self._causal
+            if causal is not None:
+                # causal weighting: the residual field, its time-bin weights and weighted cotangents (the loss sum lands
+                # where the fused launch leaves it), the reverse sweep of the residual
+                self._sync_causal_state(F, causal)
+                r, _ = _E.residual_forward(prog, pd, x, t, want_loss_sum=False)
+                td = self.pde.time_domain
+                _E.causal_weights(r.reshape(-1), t.detach().float().contiguous().reshape(-1), causal[0], td[0], td[1],
+                                  F["causal_eps"], loss_name, delta, F["rw"] / float(N), loss_sum=F["grad"][n : n + 1],
+                                  cot=ch["causal_cot"], bin_losses=F["causal_losses"], bin_weights=F["causal_w"],
+                                  scratch=F["causal_scratch"])
+                _E.residual_backward(prog, pd, x, t, ch["causal_cot"], F["grad"][:n])
+                return
             if "coef" in F:  # trainable coefficients: read from the device buffer, cotangents into their gradient slots
                 _E.residual_loss_grad_inverse(prog, F["pd_inverse"], F["coef"], x, t, F["rw"] / float(N), F["grad"][:n],
                                               F["coef_grad"], loss_sum=F["grad"][n : n + 1])
@@ -892,7 +954,9 @@ class PDETrainer:
         the captured step (`_manual_launches_adaptive`: the EMA state lives on the device; `losses["weights"]` is the
         static 4-vector of the last replay).  HeatEquation's finite-difference smoothness term (1-D, fixed loss weights) is
         part of it too: four more launches on the main stream after the join (`losses["smoothness"]` is the static,
-        unweighted term of the last replay).  Steps the fixed sequence does not cover (`_manual_step_unsupported()`:
+        unweighted term of the last replay).  With causal weighting the residual launch is the chain forward ->
+        `pinn_causal_weights` -> reverse on the main stream; a replay follows `set_causal_eps`, and `causal_weights()` is the
+        static weight vector of the last replay.  Steps the fixed sequence does not cover (`_manual_step_unsupported()`:
         L-BFGS, adaptive weights in inverse / data modes or with a smoothness component, >= 2-D problems, data-parallel
         training) raise."""
         why = self._manual_step_unsupported()
@@ -921,6 +985,38 @@ class PDETrainer:
             step()
         self._step_graph = graph  # keeps the captured allocations alive
         return graph.replay, self._manual_losses(static=True)
+
+    def set_causal_eps(self, value: float) -> None:
+        """Set the sharpness of the causal weighting (finite, >= 0): written into the training config the PDE reads, which
+        is where the autograd step and the eager launch list take it from, and in place into the launch list's device
+        scalar, so a captured step follows it from its next replay.  A captured step follows no other way of changing it."""
+        causal = self._causal
+        if causal is None:
+            raise RuntimeError("set_causal_eps: training.causal_weighting is not enabled")
+        eps = validate_causal_eps(value)
+        cw = self.pde._training_attr("causal_weighting", None)
+        if isinstance(cw, dict):
+            cw["eps"] = eps
+        else:
+            cw.eps = eps
+        F = getattr(self, "_flat", None)
+        if F is not None and "causal_eps" in F:
+            F["causal_eps"].fill_(eps)
+            F["causal_host"] = (F["causal_host"][0], eps)
+
+    def causal_weights(self) -> torch.Tensor:
+        """The (num_bins,) weights of the causal residual loss: on the launch list those of the last step; on the autograd
+        path those of the PDE's last `compute_loss`, a validation pass included.  Ones before the first evaluation.  The last
+        entry is the convergence indicator of causal training: it approaches 1 as the residual is resolved over the whole
+        time domain."""
+        causal = self._causal
+        if causal is None:
+            raise RuntimeError("causal_weights: training.causal_weighting is not enabled")
+        F = getattr(self, "_flat", None)
+        if F is not None and "causal_w" in F:
+            return F["causal_w"]
+        last = getattr(self.pde, "_causal_last_weights", None)
+        return last if last is not None else torch.ones(causal[0], dtype=torch.float32, device=self.device)
 
     def set_learning_rate(self, lr: float) -> None:
         """Propagate a scheduler's learning rate to the device scalar the captured / manual step reads."""
