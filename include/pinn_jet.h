@@ -63,6 +63,16 @@ extern "C" {
 #define PINN_FLAG_PLAIN_STREAMS 16 /* engine hint: every call of the descriptor keeps one stream per derivative where the
                                       16-point kernel would run 1-D Burgers on the merged set u, u_t - nu u_xx, u_x (A/B
                                       runs and tests; same results to rounding) */
+/* Space axis of a jet launch: with axis a (1 or 2) the space streams of pinn_jet_forward, pinn_jet_backward and
+   pinn_jet_backward_inputs are d^k/dx_a^k, seeded from column a of x instead of column 0; the stream order stays
+   [u, d/dt.., d/dx_a..].  The weight gradient and the input cotangents (every column, mixed terms included) stay exact.
+   A non-zero axis always takes the layer-major engine (pinn_kernel_for / pinn_kernel_name report it, pinn_workspace_bytes
+   sizes for it) and also admits the stream sets (0, 1) and (0, 2), which have layer-major units only: with axis 0 those two
+   sets are refused like any other uncompiled set.  axis >= input_dim - 1: PINN_ERR_BAD_DESC.  The pinn_residual_* entry
+   points (the compiled PDE kinds, whose >= 2-D behaviour is the reference's) refuse a non-zero axis with
+   PINN_ERR_UNSUPPORTED.  Axis bits zero: nothing changes. */
+#define PINN_FLAG_SPACE_AXIS(a) ((a) << 8)
+#define PINN_FLAG_SPACE_AXIS_MASK 0x300
 
 typedef enum PinnStatus {
   PINN_OK = 0,
@@ -433,6 +443,50 @@ typedef struct PinnTermPde {
 int pinn_term_residual(const PinnTermPde* pde, const float* coef_values, const float* jets, const float* x, const float* t,
                        int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out, float* loss_sum_out,
                        float* jet_cotangents, float* coef_grads, double* scratch, void* stream);
+
+/* ---- term residuals along every space axis (no counterpart in pinnrl: there every spatial derivative of a >= 2-D problem
+ * is zero) -------------------------------------------------------------------------------------------------
+ * The multi-axis form of pinn_term_residual for 2 or 3 space dimensions: a Laplacian, advection along y, ...  A pure
+ * derivative along axis a is the jet recursion seeded from column a (PINN_FLAG_SPACE_AXIS), so the chain is
+ *   pinn_jet_forward (axis 0, set (time_order, space_order[0])) and, for every axis a >= 1 with space_order[a] > 0, one more
+ *   pinn_jet_forward (axis a, set (0, space_order[a]))  ->  pinn_term_residual_axes  ->  one pinn_jet_backward per launch,
+ * all of them accumulating into the same weight gradients.  Mixed derivatives (u_xy) are not available.
+ * Factor codes: 0 .. 10 keep their meaning (PinnTermFactor; U_X .. U_XXXX and X refer to axis 0), then PINN_TERM_UY ..
+ * PINN_TERM_Z below.  Axis 0 takes any compiled set; the axes 1 and 2 take order 0, 1 or 2.
+ *   jets               HOST table of `dimension` device pointers: jets[0] the (1 + time_order + space_order[0]) x N block of
+ *                      the axis-0 launch, jets[a] (a >= 1) the (1 + space_order[a]) x N block [u, d/dx_a, d2/dx_a2] of the
+ *                      axis-a launch (its row 0 is not read), NULL when space_order[a] is 0;
+ *   x                  N x dimension, row-major; t: N floats; each read only when a term names X / Y / Z or T;
+ *   jet_cotangents     nullable HOST table of blocks with the shapes of `jets`, overwritten.  The whole cotangent of u,
+ *                      sin(u) and cos(u) goes to row 0 of block 0; row 0 of every other block is written as zeros, so each
+ *                      block goes straight into pinn_jet_backward;
+ *   coefficients, residual_out, loss_sum_out, coef_grads, residual_cotangent, grad_scale, scratch
+ *                      (PINN_TERM_SCRATCH_DOUBLES), launches, grid and determinism: as pinn_term_residual.
+ * Checked on the host before any HIP call: dimension outside {2, 3}, n_terms or n_factors out of range, an uncompiled
+ * axis-0 set, space_order[a] outside [0, 2] for a >= 1 (or non-zero for a >= dimension), an unknown factor code, a factor
+ * naming a stream or coordinate the descriptor does not hold, N < 0, a null jets table / coef_values / required block of
+ * either table (or x / t under a coordinate factor, or scratch where it is needed) with N > 0: PINN_ERR_BAD_DESC;
+ * misaligned scratch: PINN_ERR_MISALIGNED.  N == 0: no-op. */
+#define PINN_TERM_UY 11
+#define PINN_TERM_UYY 12
+#define PINN_TERM_UZ 13
+#define PINN_TERM_UZZ 14
+#define PINN_TERM_Y 15
+#define PINN_TERM_Z 16
+
+typedef struct PinnTermPdeAxes {
+  int32_t dimension;      /* 2 or 3 */
+  int32_t time_order;     /* (time_order, space_order[0]): the stream set of jets[0] */
+  int32_t space_order[3]; /* per axis; [1], [2]: 0 .. 2, 0 beyond `dimension` */
+  int32_t n_terms;        /* 0 .. PINN_TERM_MAX_TERMS */
+  int32_t loss;           /* PinnLoss */
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_TERM_MAX_TERMS];
+} PinnTermPdeAxes;
+
+int pinn_term_residual_axes(const PinnTermPdeAxes* pde, const float* coef_values, const float* const* jets, const float* x,
+                            const float* t, int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out,
+                            float* loss_sum_out, float* const* jet_cotangents, float* coef_grads, double* scratch, void* stream);
 
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.

@@ -19,6 +19,13 @@ PINN_FLAG_DETERMINISTIC = 2
 PINN_FLAG_LAYER_MAJOR = 4
 PINN_FLAG_WIDE_TILE32 = 8
 PINN_FLAG_PLAIN_STREAMS = 16
+PINN_FLAG_SPACE_AXIS_MASK = 0x300
+
+
+def PINN_FLAG_SPACE_AXIS(axis: int) -> int:
+    """Descriptor flag bits that make the space streams of a jet launch d^k/dx_axis^k (axis 0: no bits, the first column)."""
+    return (int(axis) << 8) & PINN_FLAG_SPACE_AXIS_MASK
+
 
 ARCH = {"feedforward": 0, "fourier": 1, "siren": 2, "resnet": 3, "attention": 4, "autoencoder": 5}
 ACT = {"tanh": 0, "sin": 1, "gelu": 2, "sigmoid": 3, "relu": 4, "leaky_relu": 5, "identity": 6}
@@ -39,6 +46,8 @@ PINN_CAUSAL_MAX_BINS = 64
 PINN_CAUSAL_SCRATCH_DOUBLES = 64 * 2 * PINN_CAUSAL_MAX_BINS
 # PinnTermFactor: the factor codes of a residual given as data (pinn_term_residual)
 TERM_FACTOR = {"u": 0, "u_t": 1, "u_tt": 2, "u_x": 3, "u_xx": 4, "u_xxx": 5, "u_xxxx": 6, "x": 7, "t": 8, "sin(u)": 9, "cos(u)": 10}
+# the factor codes of pinn_term_residual_axes (2-D / 3-D): PinnTermFactor, then the streams and coordinates of the axes y and z
+TERM_FACTOR_ND = dict(TERM_FACTOR, **{"u_y": 11, "u_yy": 12, "u_z": 13, "u_zz": 14, "y": 15, "z": 16})
 # the record of pinn_lbfgs_direction / pinn_lbfgs_eval_stats (doubles); from "dmax" on: 64 per-block partials of max|d|
 LBFGS_REC = {"loss": 0, "gtd": 1, "gmax": 2, "gsum": 3, "accepted": 4, "count": 5, "n_iter": 6, "h_diag": 7, "dmax": 8}
 
@@ -49,7 +58,7 @@ EXPORTS = (
     "pinn_jet_backward_inputs", "pinn_kernel_for", "pinn_kernel_name", "pinn_residual_loss_grad_inverse",
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
-    "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights",
+    "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
 )
 
 
@@ -77,6 +86,14 @@ class PinnTermPde(ctypes.Structure):
     _fields_ = [
         ("time_order", ctypes.c_int32), ("space_order", ctypes.c_int32), ("n_terms", ctypes.c_int32), ("loss", ctypes.c_int32),
         ("huber_delta", ctypes.c_float), ("terms", PinnTermPdeTerm * PINN_TERM_MAX_TERMS),
+    ]
+
+
+class PinnTermPdeAxes(ctypes.Structure):
+    _fields_ = [
+        ("dimension", ctypes.c_int32), ("time_order", ctypes.c_int32), ("space_order", ctypes.c_int32 * 3),
+        ("n_terms", ctypes.c_int32), ("loss", ctypes.c_int32), ("huber_delta", ctypes.c_float),
+        ("terms", PinnTermPdeTerm * PINN_TERM_MAX_TERMS),
     ]
 
 
@@ -198,6 +215,8 @@ def load():
         lib.pinn_unit_tail_plan.argtypes = [i64, i32, P(i64), P(i32), P(i64)]
         lib.pinn_term_residual.restype = ctypes.c_int
         lib.pinn_term_residual.argtypes = [P(PinnTermPde), vp, vp, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, vp]
+        lib.pinn_term_residual_axes.restype = ctypes.c_int
+        lib.pinn_term_residual_axes.argtypes = [P(PinnTermPdeAxes), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, P(vp), vp, vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:

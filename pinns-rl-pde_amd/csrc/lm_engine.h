@@ -56,6 +56,8 @@ PINN_LM_DECL(1, 3)
 PINN_LM_DECL(1, 4)
 PINN_LM_DECL(2, 0)
 PINN_LM_DECL(2, 2)
+PINN_LM_DECL(0, 1)  // space streams alone: the launches of a further space axis (PINN_FLAG_SPACE_AXIS; csrc/Makefile: ASETS)
+PINN_LM_DECL(0, 2)
 #undef PINN_LM_DECL
 
 }  // namespace lm

@@ -18,18 +18,28 @@ namespace lm {
 
 namespace {
 
-__global__ void lm_pack_kernel(const PackTable tab, float* packed) {
+// Space axis of a jet launch (PINN_FLAG_SPACE_AXIS): the element-wise kernels seed their space streams from column 0 of the
+// packed coordinate map ([H_p][4] first Linear, [M_p][4] Fourier B^T) and of x.  Along axis a the engine hands them the
+// network with columns 0 and a exchanged — in the packed map (here), in a copy of x, and back again in the map's gradient
+// (lm_unpack_kernel) and in x_grad (lm_swap_cols_kernel) — which IS the derivative along axis a of the network as given,
+// with every cotangent exact.  The kernels themselves are the ones of axis 0, instruction for instruction.
+__host__ __device__ inline int axis_swapped(int c, int axis) { return c == 0 ? axis : (c == axis ? 0 : c); }
+
+// swap_item: index of the coordinate map whose packed columns 0 and swap_axis are exchanged (-1: none)
+__global__ void lm_pack_kernel(const PackTable tab, float* packed, int swap_item, int swap_axis) {
   const PackItem it = tab.item[blockIdx.y];
   if (!it.src) return;
+  const bool swap = (int)blockIdx.y == swap_item;
   const int total = it.rows_p * it.cols_p;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int r = i / it.cols_p, c = i - r * it.cols_p;
+    const int cs = swap ? axis_swapped(c, swap_axis) : c;  // the coordinate this packed column holds
     float v = 0.0f;
     long long dst = i;
     if (it.transpose == 1 || it.transpose == 3 || it.transpose == 5) {
-      if (c < it.rows && r < it.cols) v = it.src[c * it.cols + r];
+      if (cs < it.rows && r < it.cols) v = it.src[cs * it.cols + r];
     } else {
-      if (r < it.rows && c < it.cols) v = it.src[r * it.cols + c];
+      if (r < it.rows && cs < it.cols) v = it.src[r * it.cols + cs];
     }
     if (it.transpose >= 4) dst = frag16_index(r, c, it.cols_p >> 4);
     else if (it.transpose >= 2) dst = frag_index(r, c, it.cols_p >> 5);
@@ -38,14 +48,26 @@ __global__ void lm_pack_kernel(const PackTable tab, float* packed) {
 }
 
 // user_grad += packed_grad (logical window only)
-__global__ void lm_unpack_kernel(const PackTable tab, const float* packed_grad) {
+__global__ void lm_unpack_kernel(const PackTable tab, const float* packed_grad, int swap_item, int swap_axis) {
   const PackItem it = tab.item[blockIdx.y];
   if (!it.user_grad) return;
+  const bool swap = (int)blockIdx.y == swap_item;  // a first Linear (never transposed): its packed columns are exchanged
   const int total = it.rows * it.cols;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int r = i / it.cols, c = i - r * it.cols;
-    const float g = it.transpose ? packed_grad[it.off + c * it.cols_p + r] : packed_grad[it.off + r * it.cols_p + c];
+    const int cp = swap ? axis_swapped(c, swap_axis) : c;
+    const float g = it.transpose ? packed_grad[it.off + c * it.cols_p + r] : packed_grad[it.off + r * it.cols_p + cp];
     it.user_grad[i] += g;
+  }
+}
+
+// dst[n][c] = src[n][c with 0 and axis exchanged], n < N, c < cols (the coordinates going in, x_grad coming out)
+__global__ void lm_swap_cols_kernel(const float* __restrict__ src, float* __restrict__ dst, long long N, int cols, int axis) {
+  const long long total = N * cols;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long n = i / cols;
+    const int c = (int)(i - n * cols);
+    dst[i] = src[n * cols + axis_swapped(c, axis)];
   }
 }
 
@@ -199,6 +221,7 @@ struct Node {
 
 struct Program {
   int din = 0;
+  int space_axis = 0;  // PINN_FLAG_SPACE_AXIS of the descriptor: the column of x the space streams are seeded from
   int n_nodes = 0;
   Node node[kMaxNodes];
   Prologue head;
@@ -252,6 +275,9 @@ int build_program(const PinnNetDesc* d, Program& P, char* err, size_t en) {
   if (d->widths[d->num_linear - 1] != 1) return failf(err, en, PINN_ERR_UNSUPPORTED, "output_dim must be 1");
   if (d->activation < PINN_ACT_TANH || d->activation > PINN_ACT_IDENTITY) return failf(err, en, PINN_ERR_BAD_DESC, "unknown activation id %d", d->activation);
   P.din = d->input_dim;
+  P.space_axis = (d->flags & PINN_FLAG_SPACE_AXIS_MASK) >> 8;
+  if (P.space_axis != 0 && P.space_axis >= d->input_dim - 1)
+    return failf(err, en, PINN_ERR_BAD_DESC, "space axis %d: input_dim=%d has the space axes 0 .. %d", P.space_axis, d->input_dim, d->input_dim - 2);
   P.n_tensors = expected_tensors(d);
   if (P.n_tensors < 0) return failf(err, en, PINN_ERR_UNSUPPORTED, "architecture id %d has no kernel", d->arch);
   if (P.n_tensors + 2 * kMaxNodes > kMaxPack) return failf(err, en, PINN_ERR_UNSUPPORTED, "%d tensors exceed the pack table (%d)", P.n_tensors, kMaxPack - 2 * kMaxNodes);
@@ -507,7 +533,8 @@ bool fused_off() {
   return v;
 }
 
-bool fused_set_built(int nt, int nx) { return !(nt == 2); }  // time order 2 (wave, pendulum) stays unfused: see the Makefile
+// time order 2 (wave, pendulum) and the space-only sets (0, 1), (0, 2) of a further space axis stay unfused: see the Makefile
+bool fused_set_built(int nt, int nx) { return !(nt == 2) && !(nt == 0 && nx > 0); }
 
 // Which node kinds take the fused kernels.  Measured on MI355X (tools/micro/fused_bench.hip, tools/bench_configs.py): without
 // LayerNorm the fused launch beats GEMM + element-wise launch in both directions (C4 30.8 -> 26.1 ms); with LayerNorm the
@@ -609,6 +636,7 @@ struct Layout {
   size_t Zbar[kMaxNodes], Vbar[kMaxNodes], Pbar[kMaxNodes + 1];  // Pbar[m]: skip cotangent produced by node m's prologue (kMaxNodes = head)
   size_t Stats[kMaxNodes + 1];  // LayerNorm prologues: per-point sums kept by the forward launch ([tile][2 K][32]); 0 = none
   size_t partial = 0, partial_floats = 0, det = 0;
+  size_t xswap = 0, xgswap = 0;  // non-zero space axis: x with columns 0 and axis exchanged, and x_grad in that order (N x (din - 1) each)
   size_t total = 0;          // floats
 };
 
@@ -761,6 +789,17 @@ void make_layout(const Program& P, long long N, int K, bool bwd, bool determinis
       o += L.partial_floats;
     }
   }
+  L.xswap = L.xgswap = 0;
+  if (P.space_axis != 0) {  // axis 0: not a float more than before
+    const size_t cols = (size_t)(P.din - 1);
+    o = (o + 3) & ~(size_t)3;
+    L.xswap = o;
+    o += ((size_t)N * cols + 3) & ~(size_t)3;
+    if (bwd) {
+      L.xgswap = o;
+      o += ((size_t)N * cols + 3) & ~(size_t)3;
+    }
+  }
   L.total = o;
 }
 
@@ -784,7 +823,7 @@ hipError_t launch_ew(int nt, int nx, const EwArgs& a, bool bwd, int act, int fpt
 #define PINN_LM_CASE(NT_, NX_) \
   if (nt == NT_ && nx == NX_) return launch_lm_ew_##NT_##_##NX_(a, bwd, act, fpt, grid, st);
   PINN_LM_CASE(0, 0) PINN_LM_CASE(1, 0) PINN_LM_CASE(1, 1) PINN_LM_CASE(1, 2) PINN_LM_CASE(1, 3) PINN_LM_CASE(1, 4)
-  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2)
+  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2) PINN_LM_CASE(0, 1) PINN_LM_CASE(0, 2)
 #undef PINN_LM_CASE
   return hipErrorInvalidValue;
 }
@@ -793,7 +832,7 @@ hipError_t launch_head(int nt, int nx, const HeadArgs& a, int fpt, int grid, hip
 #define PINN_LM_CASE(NT_, NX_) \
   if (nt == NT_ && nx == NX_) return launch_lm_head_##NT_##_##NX_(a, fpt, grid, st);
   PINN_LM_CASE(0, 0) PINN_LM_CASE(1, 0) PINN_LM_CASE(1, 1) PINN_LM_CASE(1, 2) PINN_LM_CASE(1, 3) PINN_LM_CASE(1, 4)
-  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2)
+  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2) PINN_LM_CASE(0, 1) PINN_LM_CASE(0, 2)
 #undef PINN_LM_CASE
   return hipErrorInvalidValue;
 }
@@ -945,7 +984,21 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
       }
     }
   }
-  hipLaunchKernelGGL(lm_pack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, params);
+  // Non-zero space axis: the coordinate map (tensor 0 of every architecture: the first Linear, or Fourier B) is packed with
+  // its columns 0 and axis exchanged, and the kernels read a copy of x with the same two columns exchanged
+  const int swap_axis = P.space_axis, swap_item = P.space_axis != 0 ? 0 : -1;
+  const float* x_in = c.x;
+  float* xg_out = c.x_grad;
+  if (swap_axis != 0) {
+    float* xs = ws + L.xswap;
+    const long long total = c.N * (long long)(P.din - 1);
+    hipLaunchKernelGGL(lm_swap_cols_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, st,
+                       c.x, xs, c.N, P.din - 1, swap_axis);
+    LM_CHECK(hipGetLastError());
+    x_in = xs;
+    if (c.bwd && c.x_grad) xg_out = ws + L.xgswap;
+  }
+  hipLaunchKernelGGL(lm_pack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, params, swap_item, swap_axis);
   LM_CHECK(hipGetLastError());
   MergeTable merge;
   merge.n = P.n_derived;
@@ -962,7 +1015,7 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
   if (P.n_derived > 0) {
     hipLaunchKernelGGL(lm_merge_pv_kernel, dim3(16, P.n_derived), dim3(256), 0, st, merge, params);
     LM_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(lm_pack_kernel, dim3(8, second.n), dim3(256), 0, st, second, params);
+    hipLaunchKernelGGL(lm_pack_kernel, dim3(8, second.n), dim3(256), 0, st, second, params, -1, 0);
     LM_CHECK(hipGetLastError());
   }
   // input cotangents only (pinn_jet_backward_inputs without a gradient table): no dW / db GEMM, no packed-gradient traffic
@@ -992,7 +1045,7 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     a.src_kind = pro.src_kind;
     a.din = P.din;
     a.M = pro.M;
-    a.x = c.x;
+    a.x = x_in;
     a.t = c.t;
     a.eps = P.ln_eps;
     a.has_act = pro.act >= 0;
@@ -1159,7 +1212,7 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
       a.d_ln_g = gp(pro.ln_g);
       a.d_ln_b = gp(pro.ln_b);
       if (xg) {
-        a.x_grad = c.x_grad;
+        a.x_grad = xg_out;
         a.t_grad = c.t_grad;
       }
       if (pro.src_kind == SRC_COORDS_LINEAR) {
@@ -1381,7 +1434,13 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     LM_CHECK(hipGetLastError());
   }
   if (wgrads) {
-    hipLaunchKernelGGL(lm_unpack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, grads);
+    hipLaunchKernelGGL(lm_unpack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, grads, swap_item, swap_axis);
+    LM_CHECK(hipGetLastError());
+  }
+  if (swap_axis != 0 && c.bwd && c.x_grad) {  // x_grad back into the caller's column order
+    const long long total = c.N * (long long)(P.din - 1);
+    hipLaunchKernelGGL(lm_swap_cols_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, st,
+                       xg_out, c.x_grad, c.N, P.din - 1, swap_axis);
     LM_CHECK(hipGetLastError());
   }
 #undef LM_CHECK

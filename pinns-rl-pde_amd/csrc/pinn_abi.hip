@@ -332,6 +332,24 @@ static bool stream_set_compiled(int nt, int nx) {
   return false;
 }
 
+// PINN_FLAG_SPACE_AXIS of a descriptor: the column of x its space streams differentiate along (0: the first, as ever)
+static int space_axis_of(const PinnNetDesc* d) { return (d->flags & PINN_FLAG_SPACE_AXIS_MASK) >> 8; }
+
+// A non-zero axis runs the layer-major engine, which also has units for the space-only sets (0, 1) and (0, 2): the launches
+// of a further space axis (csrc/Makefile: ASETS).  With axis 0 they stay refused like any other uncompiled set.
+static bool stream_set_admitted(const PinnNetDesc* d, int nt, int nx) {
+  if (stream_set_compiled(nt, nx)) return true;
+  return space_axis_of(d) != 0 && nt == 0 && (nx == 1 || nx == 2);
+}
+
+// the compiled PDE kinds keep the reference's >= 2-D behaviour (every spatial derivative zero): no axis for them
+static int refuse_axis(const PinnNetDesc* d, const char* entry) {
+  if (d && space_axis_of(d) != 0)
+    return fail(PINN_ERR_UNSUPPORTED, "%s: PINN_FLAG_SPACE_AXIS(%d) is set, and the compiled PDE kinds differentiate along the first "
+                "space axis only (derivatives along further axes: pinn_jet_forward + pinn_term_residual_axes)", entry, space_axis_of(d));
+  return PINN_OK;
+}
+
 static hipError_t dispatch_wide(int nt, int nx, const KernelArgs& a, bool bwd, int grid, hipStream_t st) {
 #define PINN_CASE2(NT_, NX_) \
   if (nt == NT_ && nx == NX_) return launch_jetw_##NT_##_##NX_(a, bwd, grid, st);
@@ -349,6 +367,7 @@ static hipError_t dispatch_wide(int nt, int nx, const KernelArgs& a, bool bwd, i
 // the wide kernel runs this problem: program built, all K streams fit the LDS, engine not overridden
 static bool use_wide(const PinnNetDesc* d, const float* const* w, float* const* g, int K, bool bwd, NetDev* n, int* misaligned = nullptr) {
   if (force_lm()) return false;
+  if (space_axis_of(d) != 0) return false;  // the tile-major kernels seed their space streams from column 0 only
   if (!build_wide(d, w, g, n, misaligned)) return false;
   return jet_wide_fits(K, n->hmax, bwd, n->n_layers);
 }
@@ -525,7 +544,7 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
   if (!x && net->input_dim > 1) return fail(PINN_ERR_BAD_DESC, "x is null");
   if (!t) return fail(PINN_ERR_BAD_DESC, "t is null");
   if ((rc = check_orders(nt, nx))) return rc;
-  if (!stream_set_compiled(nt, nx)) return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", nt, nx);
+  if (!stream_set_admitted(net, nt, nx)) return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", nt, nx);
   char lerr[256] = "";
   if ((rc = lm::lm_check(net, lerr, sizeof(lerr)))) return fail(rc, "%s", lerr);
   const int K = 1 + nt + nx;
@@ -748,7 +767,7 @@ int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32
   if (backward < 0 || backward > 2) return fail(PINN_ERR_BAD_DESC, "backward = %d: 0, 1 or 2", backward);
   int rc = check_orders(time_order, space_order);
   if (rc) return rc;
-  if (!stream_set_compiled(time_order, space_order))
+  if (!stream_set_admitted(net, time_order, space_order))
     return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", time_order, space_order);
   char lerr[256] = "";
   if ((rc = lm::lm_check(net, lerr, sizeof(lerr)))) return fail(rc, "%s", lerr);
@@ -833,7 +852,7 @@ int pinn_jet_backward_inputs(const PinnNetDesc* net, const float* const* weights
     int rc = validate_table(net, weights, num_tensors, "weights");
     if (rc || N <= 0) return rc;
     if ((rc = check_orders(time_order, space_order))) return rc;
-    if (!stream_set_compiled(time_order, space_order))
+    if (!stream_set_admitted(net, time_order, space_order))
       return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", time_order, space_order);
     char lerr[256] = "";
     if ((rc = lm::lm_check(net, lerr, sizeof(lerr)))) return fail(rc, "%s", lerr);
@@ -847,7 +866,9 @@ int pinn_residual_forward(const PinnNetDesc* net, const float* const* weights, i
                           const PinnPdeDesc* pde, const float* x, const float* t, int64_t N, float* residual_out,
                           float* loss_sum_out, void* workspace, size_t ws_bytes, void* stream) {
   int32_t nt, nx;
-  int rc = pinn_pde_streams(pde, &nt, &nx);
+  int rc = refuse_axis(net, "pinn_residual_forward");
+  if (rc) return rc;
+  rc = pinn_pde_streams(pde, &nt, &nx);
   if (rc) return rc;
   return run(net, weights, nullptr, num_tensors, pde, x, t, N, nt, nx, MODE_PDE, 0.0f, nullptr, nullptr, residual_out,
              loss_sum_out, workspace, ws_bytes, false, stream);
@@ -859,7 +880,9 @@ int pinn_residual_loss_grad(const PinnNetDesc* net, const float* const* weights,
                             size_t ws_bytes, void* stream) {
   if (!weight_grads) return fail(PINN_ERR_BAD_DESC, "weight_grads is null");
   int32_t nt, nx;
-  int rc = pinn_pde_streams(pde, &nt, &nx);
+  int rc = refuse_axis(net, "pinn_residual_loss_grad");
+  if (rc) return rc;
+  rc = pinn_pde_streams(pde, &nt, &nx);
   if (rc) return rc;
   return run(net, weights, weight_grads, num_tensors, pde, x, t, N, nt, nx, MODE_PDE, grad_scale, nullptr, nullptr,
              residual_out, loss_sum_out, workspace, ws_bytes, true, stream);
@@ -871,7 +894,9 @@ int pinn_residual_loss_grad_coef(const PinnNetDesc* net, const float* const* wei
                                  void* workspace, size_t ws_bytes, void* stream) {
   if (!weight_grads) return fail(PINN_ERR_BAD_DESC, "weight_grads is null");
   int32_t nt, nx;
-  int rc = pinn_pde_streams(pde, &nt, &nx);
+  int rc = refuse_axis(net, "pinn_residual_loss_grad_coef");
+  if (rc) return rc;
+  rc = pinn_pde_streams(pde, &nt, &nx);
   if (rc) return rc;
   return run(net, weights, weight_grads, num_tensors, pde, x, t, N, nt, nx, MODE_PDE, grad_scale, nullptr, nullptr,
              residual_out, loss_sum_out, workspace, ws_bytes, true, stream, nullptr, coef_grads);
@@ -887,7 +912,9 @@ static int inverse_route(const PinnNetDesc* net, int nt, int nx, NetDev* n) {
 static int inverse_query(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N, int32_t* nt, int32_t* nx) {
   if (!net || !pde) return fail(PINN_ERR_BAD_DESC, "null descriptor");
   if (N <= 0) return fail(PINN_ERR_BAD_DESC, "N = %lld: a call on no points launches nothing", (long long)N);
-  int rc = pinn_pde_streams(pde, nt, nx);
+  int rc = refuse_axis(net, "pinn_residual_loss_grad_inverse");
+  if (rc) return rc;
+  rc = pinn_pde_streams(pde, nt, nx);
   if (rc) return rc;
   if (!stream_set_compiled(*nt, *nx)) return fail(PINN_ERR_UNSUPPORTED, "stream set (nt=%d, nx=%d) is not compiled", *nt, *nx);
   char lerr[256] = "";
@@ -903,7 +930,9 @@ int pinn_residual_loss_grad_inverse(const PinnNetDesc* net, const float* const* 
   if (!weight_grads) return fail(PINN_ERR_BAD_DESC, "weight_grads is null");
   if (!coef_values) return fail(PINN_ERR_BAD_DESC, "coef_values is null: the coefficients of this call live on the device");
   int32_t nt, nx;
-  int rc = pinn_pde_streams(pde, &nt, &nx);
+  int rc = refuse_axis(net, "pinn_residual_loss_grad_inverse");
+  if (rc) return rc;
+  rc = pinn_pde_streams(pde, &nt, &nx);
   if (rc) return rc;
   PinnPdeDesc p = *pde;  // pde->coef is ignored: every value comes from coef_values at launch time
   p.coef[0] = p.coef[1] = p.coef[2] = p.coef[3] = 0.0f;
@@ -950,7 +979,9 @@ int pinn_residual_backward(const PinnNetDesc* net, const float* const* weights, 
                            size_t ws_bytes, void* stream) {
   if (!weight_grads || !residual_cotangent) return fail(PINN_ERR_BAD_DESC, "null cotangent or weight_grads");
   int32_t nt, nx;
-  int rc = pinn_pde_streams(pde, &nt, &nx);
+  int rc = refuse_axis(net, "pinn_residual_backward");
+  if (rc) return rc;
+  rc = pinn_pde_streams(pde, &nt, &nx);
   if (rc) return rc;
   return run(net, weights, weight_grads, num_tensors, pde, x, t, N, nt, nx, MODE_PDE, 0.0f, nullptr, nullptr, nullptr,
              nullptr, workspace, ws_bytes, true, stream, residual_cotangent);

@@ -159,9 +159,24 @@ def _stream(dev: torch.device) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def _scratch(prog: "NetProgram", dev: torch.device, N: int, nt: int, nx: int, backward: bool):
-    """(tensor | None, data_ptr, nbytes) of the scratch one call needs (records of the layer-major engine / tape)."""
-    nbytes = _lib.load().pinn_workspace_bytes(ctypes.byref(prog.desc), N, nt, nx, 1 if backward else 0)
+def _axis_desc(prog: "NetProgram", axis: int):
+    """The descriptor of a jet launch along space axis `axis`: the program's own for axis 0, else a BY-VALUE copy with
+    PINN_FLAG_SPACE_AXIS(axis) set.  The shared descriptor is never written: another stream may be sizing or launching with
+    it.  The same copy sizes the workspace and makes the call, so the engine that is sized is the engine that runs."""
+    axis = int(axis)
+    if axis == 0:
+        return prog.desc
+    if not 0 < axis < prog.input_dim - 1:
+        raise ValueError(f"space axis {axis}: a model with input_dim={prog.input_dim} has the axes 0 .. {prog.input_dim - 2}")
+    d = _lib.PinnNetDesc.from_buffer_copy(prog.desc)
+    d.flags = (d.flags & ~_lib.PINN_FLAG_SPACE_AXIS_MASK) | _lib.PINN_FLAG_SPACE_AXIS(axis)
+    return d
+
+
+def _scratch(prog: "NetProgram", dev: torch.device, N: int, nt: int, nx: int, backward: bool, desc=None):
+    """(tensor | None, data_ptr, nbytes) of the scratch one call needs (records of the layer-major engine / tape).
+    `desc`: the descriptor of the call where it is not the program's own (`_axis_desc`)."""
+    nbytes = _lib.load().pinn_workspace_bytes(ctypes.byref(prog.desc if desc is None else desc), N, nt, nx, 1 if backward else 0)
     if nbytes == 0:
         return None, None, 0
     ws = _workspace(dev, nbytes)
@@ -225,7 +240,58 @@ class TermDesc:
         return TermDesc(self.terms, self.coef_values, self.nt, self.nx, loss, huber_delta)
 
 
+class AxisTermDesc:
+    """A residual given as data in 2 or 3 space dimensions (`pinn_term_residual_axes`), with pure derivatives along every
+    space axis: `TermDesc`'s factor names plus "u_y", "u_yy", "u_z", "u_zz", "y", "z" (`_lib.TERM_FACTOR_ND`).
+
+    dimension: 2 or 3; nt: the time order; nx: the space order per axis — (nt, nx[0]) is a compiled stream set (the axis-0
+    launch), nx[1] and nx[2] are 0, 1 or 2 (one more launch of the set (0, nx[a]) along axis a where nx[a] > 0).  Wherever the
+    engine takes a `PinnPdeDesc` it takes an `AxisTermDesc` too and runs the chain: one jets_forward per axis that has
+    streams, term_residual_axes, one jets_backward per axis."""
+
+    def __init__(self, terms: Sequence[Sequence[str]], coef_values: Tensor, dimension: int, nt: int, nx: Sequence[int],
+                 loss: str = "mse", huber_delta: float = 1.0):
+        if int(dimension) not in (2, 3):
+            raise ValueError(f"an axis term residual has dimension 2 or 3 (got {dimension}); TermDesc is the 1-D form")
+        if len(terms) > _lib.PINN_TERM_MAX_TERMS:
+            raise ValueError(f"a term residual has at most {_lib.PINN_TERM_MAX_TERMS} terms (got {len(terms)})")
+        nx = tuple(int(v) for v in nx) + (0,) * (3 - len(nx))
+        if len(nx) != 3 or any(not 0 <= v <= 2 for v in nx[1:]) or any(v for v in nx[int(dimension):]):
+            raise ValueError(f"space orders {nx}: one per axis, 0 .. 2 on the axes y and z, 0 beyond the dimension")
+        d = _lib.PinnTermPdeAxes()
+        d.dimension, d.time_order, d.n_terms = int(dimension), int(nt), len(terms)
+        for a in range(3):
+            d.space_order[a] = nx[a]
+        d.loss = _lib.LOSS.get(loss, 0)  # unknown names fall back to mse (pde_base.py:313-315)
+        d.huber_delta = float(huber_delta)
+        for m, factors in enumerate(terms):
+            if len(factors) > _lib.PINN_TERM_MAX_FACTORS:
+                raise ValueError(f"term {m}: at most {_lib.PINN_TERM_MAX_FACTORS} factors (got {len(factors)})")
+            d.terms[m].n_factors = len(factors)
+            for f, name in enumerate(factors):
+                if name not in _lib.TERM_FACTOR_ND:
+                    raise ValueError(f"term {m}: unknown factor '{name}' (one of {', '.join(_lib.TERM_FACTOR_ND)})")
+                d.terms[m].factor[f] = _lib.TERM_FACTOR_ND[name]
+        if coef_values.dtype != torch.float32 or not coef_values.is_contiguous() or coef_values.numel() < len(terms):
+            raise ValueError("coef_values: one contiguous float32 value per term")
+        self.desc = d
+        self.terms = [tuple(f) for f in terms]
+        self.coef_values = coef_values
+        self.dimension, self.nt, self.nx = int(dimension), int(nt), nx
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "AxisTermDesc":
+        """The same program and the same coefficient tensor under another loss kind."""
+        return AxisTermDesc(self.terms, self.coef_values, self.dimension, self.nt, self.nx, loss, huber_delta)
+
+    def launches(self) -> List[Tuple[int, int, int]]:
+        """(axis, nt, nx) of the jet launches of the chain: axis 0 always (it carries the value stream), then every further
+        axis that has streams, on the set (0, nx[axis])."""
+        return [(0, self.nt, self.nx[0])] + [(a, 0, self.nx[a]) for a in range(1, self.dimension) if self.nx[a] > 0]
+
+
 def pde_streams(pd) -> Tuple[int, int]:
+    if isinstance(pd, AxisTermDesc):  # the set of the axis-0 launch
+        return pd.nt, pd.nx[0]
     if isinstance(pd, TermDesc):
         return pd.nt, pd.nx
     nt, nx = ctypes.c_int32(), ctypes.c_int32()
@@ -236,19 +302,21 @@ def pde_streams(pd) -> Tuple[int, int]:
 # ---------------------------------------------------------------------------------------------
 # raw launches
 # ---------------------------------------------------------------------------------------------
-def jets_forward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int) -> Tensor:
-    """(K, N) tensor of [u, d/dt.., d/dx..] — one launch, no graph."""
+def jets_forward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, axis: int = 0) -> Tensor:
+    """(K, N) tensor of [u, d/dt.., d/dx_axis..] — one launch, no graph.  `axis`: the column of x the space streams
+    differentiate along (non-zero: the layer-major engine; also the sets (0, 1) and (0, 2))."""
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    desc = _axis_desc(prog, axis)
     K = 1 + nt + nx
     out = torch.empty((K, N), dtype=torch.float32, device=dev)
     if N == 0:
         return out
     optr = (ctypes.c_void_p * K)(*[out[s].data_ptr() for s in range(K)])
-    ws, wptr, wn = _scratch(prog, dev, N, nt, nx, False)
+    ws, wptr, wn = _scratch(prog, dev, N, nt, nx, False, desc)
     with torch.cuda.device(dev):
-        _lib.check(lib.pinn_jet_forward(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
+        _lib.check(lib.pinn_jet_forward(ctypes.byref(desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
                                         t.data_ptr(), N, nt, nx, optr, wptr, wn, _stream(dev)))
     return out
 
@@ -269,30 +337,34 @@ def split_flat_grad(prog: NetProgram, flat: Tensor) -> List[Optional[Tensor]]:
     return [flat[o : o + p.numel()].view_as(p) if o >= 0 else None for o, p in zip(offs, prog.tensors)]
 
 
-def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, flat_grad: Tensor) -> None:
-    """flat_grad += d<cot, jets>/d(theta).  cot: (K, N)."""
+def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, flat_grad: Tensor, axis: int = 0) -> None:
+    """flat_grad += d<cot, jets>/d(theta).  cot: (K, N); `axis` as for `jets_forward`."""
     lib = _lib.load()
     dev = _require_device(x, t, cot, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    desc = _axis_desc(prog, axis)
     if N == 0:
         return
     K = 1 + nt + nx
     cot = _f32c(cot)
     assert cot.shape == (K, N)
     cptr = (ctypes.c_void_p * K)(*[cot[s].data_ptr() for s in range(K)])
-    ws, wptr, wn = _scratch(prog, dev, N, nt, nx, True)
+    ws, wptr, wn = _scratch(prog, dev, N, nt, nx, True, desc)
     with torch.cuda.device(dev):
-        _lib.check(lib.pinn_jet_backward(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
+        _lib.check(lib.pinn_jet_backward(ctypes.byref(desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
                                          t.data_ptr(), N, nt, nx, cptr, _grad_ptrs(prog, flat_grad), wptr, wn, _stream(dev)))
 
 
 def jets_backward_inputs(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor,
-                         flat_grad: Optional[Tensor], want_x: bool, want_t: bool) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+                         flat_grad: Optional[Tensor], want_x: bool, want_t: bool,
+                         axis: int = 0) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """(x_grad (N, dim) | None, t_grad (N, 1) | None) = d<cot, jets>/d(x, t), and flat_grad += d<cot, jets>/d(theta) when
-    given — one `pinn_jet_backward_inputs` launch on the layer-major engine (the descriptor is not touched).  cot: (K, N)."""
+    given — one `pinn_jet_backward_inputs` launch on the layer-major engine (the descriptor is not touched).  cot: (K, N);
+    `axis` as for `jets_forward` (every column of x_grad stays exact, mixed terms included)."""
     lib = _lib.load()
     dev = _require_device(x, t, cot, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    desc = _axis_desc(prog, axis)
     want_x = bool(want_x) and x.shape[1] > 0
     xg = torch.empty_like(x) if want_x else None
     tg = torch.empty_like(t) if want_t else None
@@ -302,10 +374,10 @@ def jets_backward_inputs(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: in
     cot = _f32c(cot)
     assert cot.shape == (K, N)
     cptr = (ctypes.c_void_p * K)(*[cot[s].data_ptr() for s in range(K)])
-    nbytes = lib.pinn_workspace_bytes(ctypes.byref(prog.desc), N, nt, nx, 2)
+    nbytes = lib.pinn_workspace_bytes(ctypes.byref(desc), N, nt, nx, 2)
     ws = _workspace(dev, nbytes) if nbytes else None
     with torch.cuda.device(dev):
-        _lib.check(lib.pinn_jet_backward_inputs(ctypes.byref(prog.desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
+        _lib.check(lib.pinn_jet_backward_inputs(ctypes.byref(desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
                                                 t.data_ptr(), N, nt, nx, cptr,
                                                 _grad_ptrs(prog, flat_grad) if flat_grad is not None else None,
                                                 xg.data_ptr() if xg is not None else None,
@@ -351,6 +423,67 @@ def term_residual(td: TermDesc, jets: Tensor, x: Tensor, t: Tensor, grad_scale: 
     return r, cot
 
 
+def term_residual_axes(td: AxisTermDesc, jets: Sequence[Optional[Tensor]], x: Tensor, t: Tensor, grad_scale: float = 0.0,
+                       residual_cotangent: Optional[Tensor] = None, want_residual: bool = True,
+                       loss_sum: Optional[Tensor] = None, want_cotangents: bool = False,
+                       coef_grads: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[List[Optional[Tensor]]]]:
+    """`pinn_term_residual_axes`: (residual (N, 1) | None, cotangent blocks | None).  jets: one block per axis — jets[0] the
+    (1 + nt + nx[0], N) block of the axis-0 launch, jets[a] the (1 + nx[a], N) block of the set (0, nx[a]) launched along axis
+    a, None where nx[a] = 0; x: (N, dimension), t: N values.  The cotangent blocks have the shapes of the jets (None where
+    the jets are); row 0 of every block >= 1 is zero, so each goes straight into `jets_backward`.  Sums and launches as
+    `term_residual`."""
+    lib = _lib.load()
+    dim = td.dimension
+    jets = list(jets) + [None] * (3 - len(jets))
+    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads)
+    rows = [1 + td.nt + td.nx[0]] + [(1 + td.nx[a]) if (a < dim and td.nx[a] > 0) else 0 for a in (1, 2)]
+    if jets[0] is None or jets[0].dim() != 2:
+        raise ValueError("term_residual_axes: jets[0] is the (1 + nt + nx[0], N) block of the axis-0 launch")
+    N = jets[0].shape[1]
+    for a in range(3):
+        j = jets[a]
+        if (j is None) != (rows[a] == 0) or (j is not None and (tuple(j.shape) != (rows[a], N) or j.dtype != torch.float32
+                                                               or not j.is_contiguous())):
+            raise ValueError(f"term_residual_axes: block {a} must be {'None' if rows[a] == 0 else f'a contiguous float32 ({rows[a]}, {N}) tensor'}")
+    x, t = _f32c(x.detach()), _f32c(t.detach())
+    if x.numel() != N * dim or t.numel() != N:
+        raise ValueError(f"term_residual_axes: x is (N, {dim}) and t holds N values (N = {N}; got {tuple(x.shape)}, {tuple(t.shape)})")
+    if residual_cotangent is not None:
+        residual_cotangent = _f32c(residual_cotangent).reshape(-1)
+        assert residual_cotangent.numel() == N
+    for tns in (loss_sum, coef_grads):
+        assert tns is None or (tns.dtype == torch.float32 and tns.is_contiguous())
+    assert coef_grads is None or coef_grads.numel() >= td.desc.n_terms
+    r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
+    cot = [torch.empty((k, N), dtype=torch.float32, device=dev) if k else None for k in rows] if want_cotangents else None
+    if N == 0:
+        return r, cot
+    reduce = loss_sum is not None or coef_grads is not None
+    scratch = torch.empty(_lib.PINN_TERM_SCRATCH_DOUBLES, dtype=torch.float64, device=dev) if reduce else None
+    opt = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
+    jptr = (ctypes.c_void_p * 3)(*[opt(j) for j in jets])
+    cptr = (ctypes.c_void_p * 3)(*[opt(c) for c in cot]) if cot is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_term_residual_axes(ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(),
+                                               N, float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum), cptr,
+                                               opt(coef_grads), opt(scratch), _stream(dev)))
+    return r, cot
+
+
+def _axes_jets(prog: NetProgram, td: AxisTermDesc, x: Tensor, t: Tensor) -> List[Optional[Tensor]]:
+    """The forward half of an `AxisTermDesc` chain: one jets_forward per axis that has streams."""
+    jets: List[Optional[Tensor]] = [None, None, None]
+    for a, nt, nx in td.launches():
+        jets[a] = jets_forward(prog, x, t, nt, nx, axis=a)
+    return jets
+
+
+def _axes_backward(prog: NetProgram, td: AxisTermDesc, x: Tensor, t: Tensor, cot: Sequence[Optional[Tensor]], flat_grad: Tensor) -> None:
+    """The reverse half: one jets_backward per axis, all accumulating into the same flat gradient."""
+    for a, nt, nx in td.launches():
+        jets_backward(prog, x, t, nt, nx, cot[a], flat_grad, axis=a)
+
+
 def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: bool = True,
                      want_loss_sum: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """(residual (N,1) | None, loss_sum (1,)) with loss_sum = sum_n l(r_n) over THESE points.  `want_loss_sum=False`: the
@@ -359,6 +492,10 @@ def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: 
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    if isinstance(pd, AxisTermDesc) and N:  # the chain over the axes: one jet launch each, then the element-wise residual
+        s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
+        r, _ = term_residual_axes(pd, _axes_jets(prog, pd, x, t), x, t, want_residual=want_residual, loss_sum=s)
+        return r, s
     if isinstance(pd, TermDesc) and N:  # the chain: jets, then the element-wise residual
         s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
         r, _ = term_residual(pd, jets_forward(prog, x, t, pd.nt, pd.nx), x, t, want_residual=want_residual, loss_sum=s)
@@ -386,6 +523,14 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
     lib = _lib.load()
     dev = _require_device(x, t, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    if isinstance(pd, AxisTermDesc) and N:
+        # the chain over the axes: one jet launch per axis, the element-wise residual with its loss sum and one block of
+        # cotangents per launch, one reverse sweep per axis into the same flat gradient
+        s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
+        r, cot = term_residual_axes(pd, _axes_jets(prog, pd, x, t), x, t, grad_scale=grad_scale, want_residual=want_residual,
+                                    loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
+        _axes_backward(prog, pd, x, t, cot, flat_grad)
+        return r, s
     if isinstance(pd, TermDesc) and N:
         # the chain: jets, the element-wise residual with its loss sum and cotangents (coef_grads: one sum per term), the
         # reverse sweep of the jets
@@ -458,6 +603,11 @@ def residual_backward(prog: NetProgram, pd, x: Tensor, t: Tensor, res_bar: Tenso
         return
     res_bar = _f32c(res_bar).reshape(-1)
     assert res_bar.numel() == N
+    if isinstance(pd, AxisTermDesc):  # the chain over the axes with the caller's cotangent in place of grad_scale l'(r)
+        _, cot = term_residual_axes(pd, _axes_jets(prog, pd, x, t), x, t, residual_cotangent=res_bar, want_residual=False,
+                                    want_cotangents=True)
+        _axes_backward(prog, pd, x, t, cot, flat_grad)
+        return
     if isinstance(pd, TermDesc):  # the chain with the caller's cotangent in place of grad_scale l'(r)
         _, cot = term_residual(pd, jets_forward(prog, x, t, pd.nt, pd.nx), x, t, residual_cotangent=res_bar,
                                want_residual=False, want_cotangents=True)

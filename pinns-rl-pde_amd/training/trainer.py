@@ -464,6 +464,7 @@ class PDETrainer:
         """None when the step can run as the fixed launch sequence below; else the reason (callers fall back)."""
         from ..pdes.pde_base import PDEBase
         from ..pdes.term_pde import TermPDE
+        from ..pdes.term_pde_nd import TermPDEnD
 
         tc = self.config.training
         kind = getattr(tc, "optimizer", "adam")
@@ -473,6 +474,18 @@ class PDETrainer:
             why = self._lbfgs_step_unsupported()
             if why is not None:
                 return why
+        nd = isinstance(self.pde, TermPDEnD)
+        if nd:
+            # a term residual in 2 or 3 space dimensions: the chain of `engine.residual_loss_grad` over the axes and the class's
+            # own boundary / initial chain cover Adam with fixed loss weights and L-BFGS on one device
+            if self.use_adaptive_weights:
+                return "TermPDEnD with adaptive loss weights"
+            if self._causal is not None:
+                return "TermPDEnD with causal weighting"
+            if self.process_group is not None:
+                return "TermPDEnD under a process group"
+            if self.rl_agent is not None:
+                return "TermPDEnD with an RL agent (the agent's grid sampler is the 1-D launch list's)"
         if self.rl_agent is not None and not hasattr(self.rl_agent, "action_probabilities"):
             return "RL agent without a device-side action selection"
         if getattr(tc, "collocation_distribution", "uniform") not in ("uniform", "stratified", "residual_based"):
@@ -506,7 +519,7 @@ class PDETrainer:
                 return "smoothness term"
             if self.process_group is not None:
                 return "smoothness term under a process group"
-        if self.pde.dimension != 1:
+        if self.pde.dimension != 1 and not nd:
             return "multi-dimensional problem"
         mode = self.pde._training_mode()
         if mode == "data_only":
@@ -957,8 +970,8 @@ class PDETrainer:
         unweighted term of the last replay).  With causal weighting the residual launch is the chain forward ->
         `pinn_causal_weights` -> reverse on the main stream; a replay follows `set_causal_eps`, and `causal_weights()` is the
         static weight vector of the last replay.  Steps the fixed sequence does not cover (`_manual_step_unsupported()`:
-        L-BFGS, adaptive weights in inverse / data modes or with a smoothness component, >= 2-D problems, data-parallel
-        training) raise."""
+        L-BFGS, adaptive weights in inverse / data modes or with a smoothness component, >= 2-D problems other than a
+        `TermPDEnD`, data-parallel training) raise."""
         why = self._manual_step_unsupported()
         if why is None and (self._is_lbfgs or getattr(self.config.training, "optimizer", "adam") != "adam"):
             why = "L-BFGS: its line search decides on the host"

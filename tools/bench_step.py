@@ -2,7 +2,7 @@
 
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
-                               [--term-pde] [--causal M,EPS]
+                               [--term-pde] [--term-nd] [--causal M,EPS]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -25,6 +25,10 @@ step is then the chain pinn_jet_forward -> pinn_term_residual -> pinn_jet_backwa
 the step table it times those three launches on their own (device time between two events, the step's batch) next to the
 compiled kind's `pinn_residual_loss_grad`.
 
+`--term-nd` runs N1 and N2 instead of C1..C4: the heat equation u_t - a Laplacian(u) on fourier 4x128 with 49 729 points, in
+1-D as a `TermPDE` (the yardstick) and in 2-D as a `TermPDEnD`, whose residual part is one jet launch per space axis in each
+sweep around `pinn_term_residual_axes` (the launch along y on the layer-major engine).
+
 `--causal M,EPS` turns on the causal (time-weighted) residual loss (`training.causal_weighting`: M time bins, sharpness
 EPS): the autograd mode builds the weighted loss with torch ops on the residual tensor, the other two run the residual part
 of the step as the chain pinn_residual_forward -> pinn_causal_weights -> pinn_residual_backward in place of the one fused
@@ -46,8 +50,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: E402
 
+import math  # noqa: E402
+
 import bench_configs as B  # noqa: E402
 from pinnrl_amd import engine as E  # noqa: E402
+from pinnrl_amd import pdes as P  # noqa: E402
 from pinnrl_amd.config import AdaptiveWeightsConfig, CausalWeightingConfig, Config, TrainingConfig  # noqa: E402
 from pinnrl_amd.pdes import TermPDE  # noqa: E402
 from pinnrl_amd.rl import RLAgent  # noqa: E402
@@ -57,8 +64,28 @@ from pinnrl_amd.training import PDETrainer  # noqa: E402
 BURGERS_TERMS = [(1.0, ("u_t",)), (1.0, ("u", "u_x")), ((-1.0, "nu"), ("u_xx",))]
 
 
+def _heat_terms(axes):
+    return [(1.0, ("u_t",))] + [((-1.0, "alpha"), (f,)) for f in ("u_xx", "u_yy", "u_zz")[:axes]]
+
+
+def _heat_nd(dim):
+    """Heat equation with the Laplacian of `dim` space dimensions on fourier 4x128, 49 729 points: dim 1 as a `TermPDE` (the
+    yardstick: one jet launch per sweep), dim 2 as a `TermPDEnD` (one more launch per sweep along y, on the layer-major engine)."""
+    net = B.model("fourier", 128, 4, "tanh", input_dim=dim + 1)
+    pc = P.PDEConfig(name="heat", domain=[(0.0, 1.0)] * dim, time_domain=(0.0, 1.0), parameters={"alpha": 0.01},
+                     boundary_conditions={"dirichlet": {"type": "fixed", "value": 0.0}}, initial_condition={"type": "sine"},
+                     exact_solution={}, dimension=dim, device=B.dev)
+    if dim == 1:
+        return "Heat 1D (u_t - a u_xx) as TermPDE, fourier 4x128", net, TermPDE(pc, _heat_terms(1)), 49729
+    ic = lambda x: torch.prod(torch.sin(math.pi * x), dim=1)  # noqa: E731
+    return f"Heat {dim}D (u_t - a Laplacian u) as TermPDEnD, fourier 4x128", net, P.TermPDEnD(pc, _heat_terms(dim), ic), 49729
+
+
+ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2)}
+
+
 def build(tag, adaptive="none", smoothness=0.0, term_pde=False, causal=None):
-    name, net, eq, n_req = B.CONFIGS[tag]()
+    name, net, eq, n_req = (ND_CONFIGS.get(tag) or B.CONFIGS[tag])()
     if term_pde:  # the same configuration object, the residual given as data
         eq = TermPDE(eq.config, BURGERS_TERMS)
         name += ", as TermPDE"
@@ -248,7 +275,10 @@ def main():
     ap.add_argument("--smoothness", type=float, default=0.0, help="C1 only: weight of HeatEquation's smoothness term")
     ap.add_argument("--term-pde", action="store_true", help="C2 only: Burgers as a TermPDE, and the chain's launches on their own")
     ap.add_argument("--causal", default="", metavar="M,EPS", help="causal residual weighting: M time bins, sharpness EPS")
+    ap.add_argument("--term-nd", action="store_true", help="N1, N2: the heat Laplacian in 1-D (TermPDE) and 2-D (TermPDEnD), fourier 4x128")
     args = ap.parse_args()
+    if args.term_nd and args.configs == "C1,C2,C3,C4":
+        args.configs = "N1,N2"
     causal = None
     if args.causal:
         m, e = args.causal.split(",")
