@@ -67,12 +67,34 @@ extern "C" {
    pinn_jet_backward_inputs are d^k/dx_a^k, seeded from column a of x instead of column 0; the stream order stays
    [u, d/dt.., d/dx_a..].  The weight gradient and the input cotangents (every column, mixed terms included) stay exact.
    A non-zero axis always takes the layer-major engine (pinn_kernel_for / pinn_kernel_name report it, pinn_workspace_bytes
-   sizes for it) and also admits the stream sets (0, 1) and (0, 2), which have layer-major units only: with axis 0 those two
+   sizes for it) and also admits the stream sets (0, 1) .. (0, 4), which have layer-major units only: with axis 0 those four
    sets are refused like any other uncompiled set.  axis >= input_dim - 1: PINN_ERR_BAD_DESC.  The pinn_residual_* entry
    points (the compiled PDE kinds, whose >= 2-D behaviour is the reference's) refuse a non-zero axis with
    PINN_ERR_UNSUPPORTED.  Axis bits zero: nothing changes. */
 #define PINN_FLAG_SPACE_AXIS(a) ((a) << 8)
 #define PINN_FLAG_SPACE_AXIS_MASK 0x300
+/* Space direction of a jet launch: two bits per space axis (0 -> 0, 1 -> +1, 2 -> -1; 3 is PINN_ERR_BAD_DESC).  With the
+   direction d the space streams of pinn_jet_forward, pinn_jet_backward and pinn_jet_backward_inputs are
+   (sum_c d_c d/dx_c)^k u; the stream order stays [u, d/ds, d2/ds2, ..].  Mixed derivatives are fixed linear combinations of
+   such streams (pinn_term_residual_mixed).  A direction launch always takes the layer-major engine (pinn_kernel_for /
+   pinn_kernel_name report it; pinn_workspace_bytes sizes it as an axis launch: one N x (input_dim - 1) copy of the
+   coordinates and one more on reverse calls) and admits the space-only sets (0, 1) .. (0, 4) and no other.  A non-zero
+   AXIS admits (0, 3) and (0, 4) as well.  Valid: at least two non-zero entries, the first of them +1 (the negated direction
+   adds nothing), none on an axis >= input_dim - 1, axis bits zero; anything else is PINN_ERR_BAD_DESC, reported by every
+   query and entry point before a table entry is read.  The pinn_residual_* entry points refuse direction bits with
+   PINN_ERR_UNSUPPORTED.  Direction bits zero: nothing changes.
+   How it runs — the exchange of columns of an axis launch, generalised to a unimodular shear; no compute kernel differs.
+   With p the first axis with d_p = +1 and s(.) the exchange of columns 0 and p, in fp32 and in exactly this order:
+     packed coordinate map (the first Linear, or the rows of Fourier B):
+       column 0 = W[:,p] + sum_{c != p, d_c != 0} d_c W[:,c], one add or subtract per c in ascending c; column j != 0 = W[:,s(j)];
+     coordinates the kernels read: x'_0 = x_p;  x'_j = x_{s(j)} - d_{s(j)} x_p (one add or subtract);  t untouched;
+     map gradient coming back: dW[:,p] += g[:,0];  dW[:,c] += g[:,s(c)] + d_c g[:,0] for c != p;
+     x_grad coming back: xbar_c = xbar'_{s(c)} for c != p;  xbar_p = xbar'_0 - sum_{c != p} d_c xbar'_{s(c)}, ascending c.
+   u(x) = u'(x') for every x, so the streams along column 0 of the sheared network ARE the directional derivatives of the
+   network as given and every cotangent is exact.  PINN_FLAG_DETERMINISTIC holds as for an axis launch. */
+#define PINN_FLAG_SPACE_DIRECTION(d0, d1, d2) \
+  (((((d0) < 0 ? 2 : (d0)) & 3) << 10) | ((((d1) < 0 ? 2 : (d1)) & 3) << 12) | ((((d2) < 0 ? 2 : (d2)) & 3) << 14))
+#define PINN_FLAG_SPACE_DIRECTION_MASK 0xFC00
 
 typedef enum PinnStatus {
   PINN_OK = 0,
@@ -450,7 +472,8 @@ int pinn_term_residual(const PinnTermPde* pde, const float* coef_values, const f
  * derivative along axis a is the jet recursion seeded from column a (PINN_FLAG_SPACE_AXIS), so the chain is
  *   pinn_jet_forward (axis 0, set (time_order, space_order[0])) and, for every axis a >= 1 with space_order[a] > 0, one more
  *   pinn_jet_forward (axis a, set (0, space_order[a]))  ->  pinn_term_residual_axes  ->  one pinn_jet_backward per launch,
- * all of them accumulating into the same weight gradients.  Mixed derivatives (u_xy) are not available.
+ * all of them accumulating into the same weight gradients.  Mixed derivatives (u_xy) are not available here:
+ * pinn_term_residual_mixed below has them.
  * Factor codes: 0 .. 10 keep their meaning (PinnTermFactor; U_X .. U_XXXX and X refer to axis 0), then PINN_TERM_UY ..
  * PINN_TERM_Z below.  Axis 0 takes any compiled set; the axes 1 and 2 take order 0, 1 or 2.
  *   jets               HOST table of `dimension` device pointers: jets[0] the (1 + time_order + space_order[0]) x N block of
@@ -487,6 +510,59 @@ typedef struct PinnTermPdeAxes {
 int pinn_term_residual_axes(const PinnTermPdeAxes* pde, const float* coef_values, const float* const* jets, const float* x,
                             const float* t, int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out,
                             float* loss_sum_out, float* const* jet_cotangents, float* coef_grads, double* scratch, void* stream);
+
+/* ---- term residuals with mixed derivatives (u_xy, u_xxyy) -----------------------------------------------------------------
+ * pinn_term_residual_axes plus the orders 3 and 4 along y and z and the mixed factors u_ab, u_aabb of every pair of axes.
+ * A mixed derivative is a fixed linear combination of pure derivatives along a few lines (polarisation): with
+ * P_k = (d_a + d_b)^k u and Q_k = (d_a - d_b)^k u, the streams of the jet launches along e_a + e_b and e_a - e_b
+ * (PINN_FLAG_SPACE_DIRECTION),
+ *   u_ab   = 0.5f * ((P_2 - A_2) - B_2)
+ *   u_aabb = ((P_4 + Q_4) - 2.0f * (A_4 + B_4)) * (float)(1.0 / 12.0)
+ * evaluated in fp32 in exactly this order; A_k, B_k are the order-k rows of the two axis blocks (axis 0: row time_order + k).
+ * The chain is one pinn_jet_forward per block -> pinn_term_residual_mixed -> one pinn_jet_backward per block.
+ *   jets, jet_cotangents   HOST tables of 9 device pointers [axis0, axis1, axis2, P_xy, P_xz, P_yz, Q_xy, Q_xz, Q_yz]:
+ *                      axis blocks as for pinn_term_residual_axes, (1 + space_order[a]) x N for a >= 1; P_ab the
+ *                      (1 + pair_order) x N block of the launch along e_a + e_b, Q_ab the same along e_a - e_b, required
+ *                      only when pair_order = 4; blocks that are not needed are NULL.  From a P / Q block only the rows 2
+ *                      and 4 are read.
+ *   cotangents         the transposes, added to whatever the pure factors put there: with g = rbar dr/du_ab, +g/2 to row 2 of
+ *                      P_ab and -g/2 to the order-2 rows of both axis blocks; with h for u_aabb, +h/12 to row 4 of P_ab and of
+ *                      Q_ab and -h/6 to both order-4 rows.  Every row of a cotangent block that the program never reads —
+ *                      row 0 of every block >= 1 among them — is written as zeros, so each block goes straight into
+ *                      pinn_jet_backward.
+ * Factor codes 0 .. 16 keep their meaning; PINN_TERM_UYYY .. PINN_TERM_UYYZZ below.
+ * Everything else — coefficients, residual_out, loss_sum_out, coef_grads, residual_cotangent, grad_scale, scratch
+ * (PINN_TERM_SCRATCH_DOUBLES), the loss kinds, sgn(0) = 0, launches, grid and determinism — as pinn_term_residual_axes.
+ * Checked on the host before any HIP call: what pinn_term_residual_axes checks (space_order[a] in [0, 4] for a >= 1), a
+ * pair_order outside {0, 2, 4} or non-zero on a pair touching an axis >= dimension, u_ab without pair_order >= 2 and order >= 2
+ * on both axes, u_aabb without pair_order = 4 and order 4 on both axes, a null required block: PINN_ERR_BAD_DESC.
+ * Not available: mixed space-time derivatives, third-order mixed (u_xxy) and u_xxxy-type factors. */
+#define PINN_TERM_UYYY 17
+#define PINN_TERM_UYYYY 18
+#define PINN_TERM_UZZZ 19
+#define PINN_TERM_UZZZZ 20
+#define PINN_TERM_UXY 21
+#define PINN_TERM_UXZ 22
+#define PINN_TERM_UYZ 23
+#define PINN_TERM_UXXYY 24
+#define PINN_TERM_UXXZZ 25
+#define PINN_TERM_UYYZZ 26
+#define PINN_TERM_MIXED_BLOCKS 9
+
+typedef struct PinnTermPdeMixed {
+  int32_t dimension;      /* 2 or 3 */
+  int32_t time_order;     /* (time_order, space_order[0]): the stream set of jets[0] */
+  int32_t space_order[3]; /* per axis; [1], [2]: 0 .. 4, 0 beyond `dimension` */
+  int32_t pair_order[3];  /* pairs (x,y), (x,z), (y,z): 0, 2 or 4; 0 for a pair touching an axis >= dimension */
+  int32_t n_terms;        /* 0 .. PINN_TERM_MAX_TERMS */
+  int32_t loss;           /* PinnLoss */
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_TERM_MAX_TERMS];
+} PinnTermPdeMixed;
+
+int pinn_term_residual_mixed(const PinnTermPdeMixed* pde, const float* coef_values, const float* const* jets, const float* x,
+                             const float* t, int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out,
+                             float* loss_sum_out, float* const* jet_cotangents, float* coef_grads, double* scratch, void* stream);
 
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.

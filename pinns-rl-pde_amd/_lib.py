@@ -27,6 +27,20 @@ def PINN_FLAG_SPACE_AXIS(axis: int) -> int:
     return (int(axis) << 8) & PINN_FLAG_SPACE_AXIS_MASK
 
 
+PINN_FLAG_SPACE_DIRECTION_MASK = 0xFC00
+
+
+def PINN_FLAG_SPACE_DIRECTION(d0: int = 0, d1: int = 0, d2: int = 0) -> int:
+    """Descriptor flag bits that make the space streams of a jet launch (sum_c d_c d/dx_c)^k: two bits per space axis,
+    0 -> 0, +1 -> 1, -1 -> 2 (all zero: no bits)."""
+    bits = 0
+    for a, d in enumerate((d0, d1, d2)):
+        if d not in (-1, 0, 1):
+            raise ValueError(f"direction entry {d!r}: -1, 0 or +1")
+        bits |= (2 if d < 0 else int(d)) << (10 + 2 * a)
+    return bits
+
+
 ARCH = {"feedforward": 0, "fourier": 1, "siren": 2, "resnet": 3, "attention": 4, "autoencoder": 5}
 ACT = {"tanh": 0, "sin": 1, "gelu": 2, "sigmoid": 3, "relu": 4, "leaky_relu": 5, "identity": 6}
 PDE = {
@@ -48,6 +62,10 @@ PINN_CAUSAL_SCRATCH_DOUBLES = 64 * 2 * PINN_CAUSAL_MAX_BINS
 TERM_FACTOR = {"u": 0, "u_t": 1, "u_tt": 2, "u_x": 3, "u_xx": 4, "u_xxx": 5, "u_xxxx": 6, "x": 7, "t": 8, "sin(u)": 9, "cos(u)": 10}
 # the factor codes of pinn_term_residual_axes (2-D / 3-D): PinnTermFactor, then the streams and coordinates of the axes y and z
 TERM_FACTOR_ND = dict(TERM_FACTOR, **{"u_y": 11, "u_yy": 12, "u_z": 13, "u_zz": 14, "y": 15, "z": 16})
+# the factor codes of pinn_term_residual_mixed: the above, the orders 3 and 4 along y and z, and the mixed derivatives
+TERM_FACTOR_MIXED = dict(TERM_FACTOR_ND, **{"u_yyy": 17, "u_yyyy": 18, "u_zzz": 19, "u_zzzz": 20, "u_xy": 21, "u_xz": 22, "u_yz": 23,
+                                            "u_xxyy": 24, "u_xxzz": 25, "u_yyzz": 26})
+PINN_TERM_MIXED_BLOCKS = 9  # [axis0, axis1, axis2, P_xy, P_xz, P_yz, Q_xy, Q_xz, Q_yz]
 # the record of pinn_lbfgs_direction / pinn_lbfgs_eval_stats (doubles); from "dmax" on: 64 per-block partials of max|d|
 LBFGS_REC = {"loss": 0, "gtd": 1, "gmax": 2, "gsum": 3, "accepted": 4, "count": 5, "n_iter": 6, "h_diag": 7, "dmax": 8}
 
@@ -59,6 +77,7 @@ EXPORTS = (
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
+    "pinn_term_residual_mixed",
 )
 
 
@@ -94,6 +113,14 @@ class PinnTermPdeAxes(ctypes.Structure):
         ("dimension", ctypes.c_int32), ("time_order", ctypes.c_int32), ("space_order", ctypes.c_int32 * 3),
         ("n_terms", ctypes.c_int32), ("loss", ctypes.c_int32), ("huber_delta", ctypes.c_float),
         ("terms", PinnTermPdeTerm * PINN_TERM_MAX_TERMS),
+    ]
+
+
+class PinnTermPdeMixed(ctypes.Structure):
+    _fields_ = [
+        ("dimension", ctypes.c_int32), ("time_order", ctypes.c_int32), ("space_order", ctypes.c_int32 * 3),
+        ("pair_order", ctypes.c_int32 * 3), ("n_terms", ctypes.c_int32), ("loss", ctypes.c_int32),
+        ("huber_delta", ctypes.c_float), ("terms", PinnTermPdeTerm * PINN_TERM_MAX_TERMS),
     ]
 
 
@@ -217,6 +244,8 @@ def load():
         lib.pinn_term_residual.argtypes = [P(PinnTermPde), vp, vp, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, vp]
         lib.pinn_term_residual_axes.restype = ctypes.c_int
         lib.pinn_term_residual_axes.argtypes = [P(PinnTermPdeAxes), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, P(vp), vp, vp, vp]
+        lib.pinn_term_residual_mixed.restype = ctypes.c_int
+        lib.pinn_term_residual_mixed.argtypes = [P(PinnTermPdeMixed), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, P(vp), vp, vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:

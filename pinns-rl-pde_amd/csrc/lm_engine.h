@@ -58,6 +58,8 @@ PINN_LM_DECL(2, 0)
 PINN_LM_DECL(2, 2)
 PINN_LM_DECL(0, 1)  // space streams alone: the launches of a further space axis (PINN_FLAG_SPACE_AXIS; csrc/Makefile: ASETS)
 PINN_LM_DECL(0, 2)
+PINN_LM_DECL(0, 3)  // orders 3 and 4 of a further axis, and of a direction launch (PINN_FLAG_SPACE_DIRECTION)
+PINN_LM_DECL(0, 4)
 #undef PINN_LM_DECL
 
 }  // namespace lm

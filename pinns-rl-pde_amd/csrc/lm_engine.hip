@@ -21,25 +21,52 @@ namespace {
 // Space axis of a jet launch (PINN_FLAG_SPACE_AXIS): the element-wise kernels seed their space streams from column 0 of the
 // packed coordinate map ([H_p][4] first Linear, [M_p][4] Fourier B^T) and of x.  Along axis a the engine hands them the
 // network with columns 0 and a exchanged — in the packed map (here), in a copy of x, and back again in the map's gradient
-// (lm_unpack_kernel) and in x_grad (lm_swap_cols_kernel) — which IS the derivative along axis a of the network as given,
+// (lm_unpack_kernel) and in x_grad (lm_shear_xgrad_kernel) — which IS the derivative along axis a of the network as given,
 // with every cotangent exact.  The kernels themselves are the ones of axis 0, instruction for instruction.
+//
+// Space direction (PINN_FLAG_SPACE_DIRECTION): the exchange generalised to a unimodular shear.  With p the first axis of the
+// direction d (d_p = +1) the engine hands the kernels the network in the coordinates x'_0 = x_p, x'_j = x_s(j) - d_s(j) x_p
+// (s = the exchange of 0 and p), whose column 0 of the coordinate map is sum_c d_c W[:,c]: u(x) = u'(x'), and d/dx'_0 of u'
+// is the derivative of u along d.  An axis launch is the direction e_a with p = a: every d_c below is then zero and the
+// four kernels do exactly the exchange.  The rounding order is the one include/pinn_jet.h states.
 __host__ __device__ inline int axis_swapped(int c, int axis) { return c == 0 ? axis : (c == axis ? 0 : c); }
 
-// swap_item: index of the coordinate map whose packed columns 0 and swap_axis are exchanged (-1: none)
-__global__ void lm_pack_kernel(const PackTable tab, float* packed, int swap_item, int swap_axis) {
+// the shear of one launch: p = pivot axis, d[c] = direction entry of space axis c with d[p] = 0 (the entries ADDED to the pivot)
+struct Shear {
+  int p;
+  int d[4];
+};
+__host__ __device__ inline float shear_add(float a, int d, float b) { return d > 0 ? a + b : (d < 0 ? a - b : a); }
+
+// swap_item: index of the coordinate map whose packed columns are sheared (-1: none)
+__global__ void lm_pack_kernel(const PackTable tab, float* packed, int swap_item, const Shear sh) {
   const PackItem it = tab.item[blockIdx.y];
   if (!it.src) return;
   const bool swap = (int)blockIdx.y == swap_item;
   const int total = it.rows_p * it.cols_p;
+  const bool tr = it.transpose == 1 || it.transpose == 3 || it.transpose == 5;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int r = i / it.cols_p, c = i - r * it.cols_p;
-    const int cs = swap ? axis_swapped(c, swap_axis) : c;  // the coordinate this packed column holds
+    const int cs = swap ? axis_swapped(c, sh.p) : c;  // the coordinate this packed column holds
     float v = 0.0f;
     long long dst = i;
-    if (it.transpose == 1 || it.transpose == 3 || it.transpose == 5) {
+    if (tr) {
       if (cs < it.rows && r < it.cols) v = it.src[cs * it.cols + r];
     } else {
       if (r < it.rows && cs < it.cols) v = it.src[r * it.cols + cs];
+    }
+    if (swap && c == 0) {  // column 0 of a direction launch: + sum d_c W[:,c] in ascending c (nothing along an axis)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (sh.d[a] == 0) continue;
+        float w = 0.0f;
+        if (tr) {
+          if (a < it.rows && r < it.cols) w = it.src[a * it.cols + r];
+        } else {
+          if (r < it.rows && a < it.cols) w = it.src[r * it.cols + a];
+        }
+        v = shear_add(v, sh.d[a], w);
+      }
     }
     if (it.transpose >= 4) dst = frag16_index(r, c, it.cols_p >> 4);
     else if (it.transpose >= 2) dst = frag_index(r, c, it.cols_p >> 5);
@@ -48,26 +75,46 @@ __global__ void lm_pack_kernel(const PackTable tab, float* packed, int swap_item
 }
 
 // user_grad += packed_grad (logical window only)
-__global__ void lm_unpack_kernel(const PackTable tab, const float* packed_grad, int swap_item, int swap_axis) {
+__global__ void lm_unpack_kernel(const PackTable tab, const float* packed_grad, int swap_item, const Shear sh) {
   const PackItem it = tab.item[blockIdx.y];
   if (!it.user_grad) return;
-  const bool swap = (int)blockIdx.y == swap_item;  // a first Linear (never transposed): its packed columns are exchanged
+  const bool swap = (int)blockIdx.y == swap_item;  // a first Linear (never transposed): its packed columns are sheared
   const int total = it.rows * it.cols;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int r = i / it.cols, c = i - r * it.cols;
-    const int cp = swap ? axis_swapped(c, swap_axis) : c;
-    const float g = it.transpose ? packed_grad[it.off + c * it.cols_p + r] : packed_grad[it.off + r * it.cols_p + cp];
+    const int cp = swap ? axis_swapped(c, sh.p) : c;
+    float g = it.transpose ? packed_grad[it.off + c * it.cols_p + r] : packed_grad[it.off + r * it.cols_p + cp];
+    if (swap && c < 3 && sh.d[c] != 0) g = shear_add(g, sh.d[c], packed_grad[it.off + r * it.cols_p]);
     it.user_grad[i] += g;
   }
 }
 
-// dst[n][c] = src[n][c with 0 and axis exchanged], n < N, c < cols (the coordinates going in, x_grad coming out)
-__global__ void lm_swap_cols_kernel(const float* __restrict__ src, float* __restrict__ dst, long long N, int cols, int axis) {
+// the coordinates going in: dst[n][0] = x[n][p], dst[n][j] = x[n][s(j)] - d_s(j) x[n][p], n < N, j < cols
+__global__ void lm_shear_x_kernel(const float* __restrict__ src, float* __restrict__ dst, long long N, int cols, const Shear sh) {
   const long long total = N * cols;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long n = i / cols;
     const int c = (int)(i - n * cols);
-    dst[i] = src[n * cols + axis_swapped(c, axis)];
+    const int cs = axis_swapped(c, sh.p);
+    float v = src[n * cols + cs];
+    if (c != 0 && sh.d[cs] != 0) v = shear_add(v, -sh.d[cs], src[n * cols + sh.p]);
+    dst[i] = v;
+  }
+}
+
+// x_grad coming out: dst[n][c] = src[n][s(c)] for c != p, dst[n][p] = src[n][0] - sum_{c != p} d_c src[n][s(c)] in ascending c
+__global__ void lm_shear_xgrad_kernel(const float* __restrict__ src, float* __restrict__ dst, long long N, int cols, const Shear sh) {
+  const long long total = N * cols;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long n = i / cols;
+    const int c = (int)(i - n * cols);
+    float v = src[n * cols + axis_swapped(c, sh.p)];
+    if (c == sh.p) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        if (a < cols && sh.d[a] != 0) v = shear_add(v, -sh.d[a], src[n * cols + axis_swapped(a, sh.p)]);
+    }
+    dst[i] = v;
   }
 }
 
@@ -222,6 +269,8 @@ struct Node {
 struct Program {
   int din = 0;
   int space_axis = 0;  // PINN_FLAG_SPACE_AXIS of the descriptor: the column of x the space streams are seeded from
+  int space_dir[3] = {0, 0, 0};  // PINN_FLAG_SPACE_DIRECTION of the descriptor (all zero: none); exclusive with space_axis
+  bool sheared() const { return space_axis != 0 || space_dir[0] != 0 || space_dir[1] != 0 || space_dir[2] != 0; }
   int n_nodes = 0;
   Node node[kMaxNodes];
   Prologue head;
@@ -278,6 +327,23 @@ int build_program(const PinnNetDesc* d, Program& P, char* err, size_t en) {
   P.space_axis = (d->flags & PINN_FLAG_SPACE_AXIS_MASK) >> 8;
   if (P.space_axis != 0 && P.space_axis >= d->input_dim - 1)
     return failf(err, en, PINN_ERR_BAD_DESC, "space axis %d: input_dim=%d has the space axes 0 .. %d", P.space_axis, d->input_dim, d->input_dim - 2);
+  if (d->flags & PINN_FLAG_SPACE_DIRECTION_MASK) {
+    int nonzero = 0, first = 0;
+    for (int a = 0; a < 3; ++a) {
+      const int code = (d->flags >> (10 + 2 * a)) & 3;
+      if (code == 3) return failf(err, en, PINN_ERR_BAD_DESC, "space direction: entry %d has the code 3 (0, 1 = +1, 2 = -1)", a);
+      P.space_dir[a] = code == 2 ? -1 : code;
+      if (code != 0 && a >= d->input_dim - 1)
+        return failf(err, en, PINN_ERR_BAD_DESC, "space direction: entry %d is non-zero, and input_dim=%d has the space axes 0 .. %d", a, d->input_dim, d->input_dim - 2);
+      if (code != 0 && nonzero++ == 0) first = P.space_dir[a];
+    }
+    if (P.space_axis != 0)
+      return failf(err, en, PINN_ERR_BAD_DESC, "PINN_FLAG_SPACE_DIRECTION and PINN_FLAG_SPACE_AXIS(%d) are both set: a launch runs along one line", P.space_axis);
+    if (nonzero < 2)
+      return failf(err, en, PINN_ERR_BAD_DESC, "space direction (%d, %d, %d) has fewer than two non-zero entries: that is an axis (PINN_FLAG_SPACE_AXIS)", P.space_dir[0], P.space_dir[1], P.space_dir[2]);
+    if (first != 1)
+      return failf(err, en, PINN_ERR_BAD_DESC, "space direction (%d, %d, %d): the first non-zero entry must be +1 (the negated direction adds nothing)", P.space_dir[0], P.space_dir[1], P.space_dir[2]);
+  }
   P.n_tensors = expected_tensors(d);
   if (P.n_tensors < 0) return failf(err, en, PINN_ERR_UNSUPPORTED, "architecture id %d has no kernel", d->arch);
   if (P.n_tensors + 2 * kMaxNodes > kMaxPack) return failf(err, en, PINN_ERR_UNSUPPORTED, "%d tensors exceed the pack table (%d)", P.n_tensors, kMaxPack - 2 * kMaxNodes);
@@ -533,7 +599,7 @@ bool fused_off() {
   return v;
 }
 
-// time order 2 (wave, pendulum) and the space-only sets (0, 1), (0, 2) of a further space axis stay unfused: see the Makefile
+// time order 2 (wave, pendulum) and the space-only sets (0, 1) .. (0, 4) of a further space axis or a direction stay unfused: see the Makefile
 bool fused_set_built(int nt, int nx) { return !(nt == 2) && !(nt == 0 && nx > 0); }
 
 // Which node kinds take the fused kernels.  Measured on MI355X (tools/micro/fused_bench.hip, tools/bench_configs.py): without
@@ -636,7 +702,7 @@ struct Layout {
   size_t Zbar[kMaxNodes], Vbar[kMaxNodes], Pbar[kMaxNodes + 1];  // Pbar[m]: skip cotangent produced by node m's prologue (kMaxNodes = head)
   size_t Stats[kMaxNodes + 1];  // LayerNorm prologues: per-point sums kept by the forward launch ([tile][2 K][32]); 0 = none
   size_t partial = 0, partial_floats = 0, det = 0;
-  size_t xswap = 0, xgswap = 0;  // non-zero space axis: x with columns 0 and axis exchanged, and x_grad in that order (N x (din - 1) each)
+  size_t xswap = 0, xgswap = 0;  // non-zero space axis or a direction: the sheared copy of x, and x_grad in its order (N x (din - 1) each)
   size_t total = 0;          // floats
 };
 
@@ -790,7 +856,7 @@ void make_layout(const Program& P, long long N, int K, bool bwd, bool determinis
     }
   }
   L.xswap = L.xgswap = 0;
-  if (P.space_axis != 0) {  // axis 0: not a float more than before
+  if (P.sheared()) {  // axis 0, no direction: not a float more than before
     const size_t cols = (size_t)(P.din - 1);
     o = (o + 3) & ~(size_t)3;
     L.xswap = o;
@@ -823,7 +889,7 @@ hipError_t launch_ew(int nt, int nx, const EwArgs& a, bool bwd, int act, int fpt
 #define PINN_LM_CASE(NT_, NX_) \
   if (nt == NT_ && nx == NX_) return launch_lm_ew_##NT_##_##NX_(a, bwd, act, fpt, grid, st);
   PINN_LM_CASE(0, 0) PINN_LM_CASE(1, 0) PINN_LM_CASE(1, 1) PINN_LM_CASE(1, 2) PINN_LM_CASE(1, 3) PINN_LM_CASE(1, 4)
-  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2) PINN_LM_CASE(0, 1) PINN_LM_CASE(0, 2)
+  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2) PINN_LM_CASE(0, 1) PINN_LM_CASE(0, 2) PINN_LM_CASE(0, 3) PINN_LM_CASE(0, 4)
 #undef PINN_LM_CASE
   return hipErrorInvalidValue;
 }
@@ -832,7 +898,7 @@ hipError_t launch_head(int nt, int nx, const HeadArgs& a, int fpt, int grid, hip
 #define PINN_LM_CASE(NT_, NX_) \
   if (nt == NT_ && nx == NX_) return launch_lm_head_##NT_##_##NX_(a, fpt, grid, st);
   PINN_LM_CASE(0, 0) PINN_LM_CASE(1, 0) PINN_LM_CASE(1, 1) PINN_LM_CASE(1, 2) PINN_LM_CASE(1, 3) PINN_LM_CASE(1, 4)
-  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2) PINN_LM_CASE(0, 1) PINN_LM_CASE(0, 2)
+  PINN_LM_CASE(2, 0) PINN_LM_CASE(2, 2) PINN_LM_CASE(0, 1) PINN_LM_CASE(0, 2) PINN_LM_CASE(0, 3) PINN_LM_CASE(0, 4)
 #undef PINN_LM_CASE
   return hipErrorInvalidValue;
 }
@@ -984,21 +1050,28 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
       }
     }
   }
-  // Non-zero space axis: the coordinate map (tensor 0 of every architecture: the first Linear, or Fourier B) is packed with
-  // its columns 0 and axis exchanged, and the kernels read a copy of x with the same two columns exchanged
-  const int swap_axis = P.space_axis, swap_item = P.space_axis != 0 ? 0 : -1;
+  // Non-zero space axis or a direction: the coordinate map (tensor 0 of every architecture: the first Linear, or Fourier B) is
+  // packed sheared, and the kernels read the sheared copy of x (an axis: columns 0 and axis exchanged in both)
+  Shear sh = {0, {0, 0, 0, 0}};
+  if (P.space_axis != 0) {
+    sh.p = P.space_axis;
+  } else if (P.sheared()) {
+    while (P.space_dir[sh.p] == 0) ++sh.p;
+    for (int a = sh.p + 1; a < 3; ++a) sh.d[a] = P.space_dir[a];
+  }
+  const int swap_item = P.sheared() ? 0 : -1;
   const float* x_in = c.x;
   float* xg_out = c.x_grad;
-  if (swap_axis != 0) {
+  if (P.sheared()) {
     float* xs = ws + L.xswap;
     const long long total = c.N * (long long)(P.din - 1);
-    hipLaunchKernelGGL(lm_swap_cols_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, st,
-                       c.x, xs, c.N, P.din - 1, swap_axis);
+    hipLaunchKernelGGL(lm_shear_x_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, st,
+                       c.x, xs, c.N, P.din - 1, sh);
     LM_CHECK(hipGetLastError());
     x_in = xs;
     if (c.bwd && c.x_grad) xg_out = ws + L.xgswap;
   }
-  hipLaunchKernelGGL(lm_pack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, params, swap_item, swap_axis);
+  hipLaunchKernelGGL(lm_pack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, params, swap_item, sh);
   LM_CHECK(hipGetLastError());
   MergeTable merge;
   merge.n = P.n_derived;
@@ -1015,7 +1088,7 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
   if (P.n_derived > 0) {
     hipLaunchKernelGGL(lm_merge_pv_kernel, dim3(16, P.n_derived), dim3(256), 0, st, merge, params);
     LM_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(lm_pack_kernel, dim3(8, second.n), dim3(256), 0, st, second, params, -1, 0);
+    hipLaunchKernelGGL(lm_pack_kernel, dim3(8, second.n), dim3(256), 0, st, second, params, -1, sh);
     LM_CHECK(hipGetLastError());
   }
   // input cotangents only (pinn_jet_backward_inputs without a gradient table): no dW / db GEMM, no packed-gradient traffic
@@ -1434,13 +1507,13 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     LM_CHECK(hipGetLastError());
   }
   if (wgrads) {
-    hipLaunchKernelGGL(lm_unpack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, grads, swap_item, swap_axis);
+    hipLaunchKernelGGL(lm_unpack_kernel, dim3(8, L.tab.n), dim3(256), 0, st, L.tab, grads, swap_item, sh);
     LM_CHECK(hipGetLastError());
   }
-  if (swap_axis != 0 && c.bwd && c.x_grad) {  // x_grad back into the caller's column order
+  if (P.sheared() && c.bwd && c.x_grad) {  // x_grad back into the caller's coordinates
     const long long total = c.N * (long long)(P.din - 1);
-    hipLaunchKernelGGL(lm_swap_cols_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, st,
-                       xg_out, c.x_grad, c.N, P.din - 1, swap_axis);
+    hipLaunchKernelGGL(lm_shear_xgrad_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, st,
+                       xg_out, c.x_grad, c.N, P.din - 1, sh);
     LM_CHECK(hipGetLastError());
   }
 #undef LM_CHECK

@@ -335,11 +335,20 @@ static bool stream_set_compiled(int nt, int nx) {
 // PINN_FLAG_SPACE_AXIS of a descriptor: the column of x its space streams differentiate along (0: the first, as ever)
 static int space_axis_of(const PinnNetDesc* d) { return (d->flags & PINN_FLAG_SPACE_AXIS_MASK) >> 8; }
 
-// A non-zero axis runs the layer-major engine, which also has units for the space-only sets (0, 1) and (0, 2): the launches
-// of a further space axis (csrc/Makefile: ASETS).  With axis 0 they stay refused like any other uncompiled set.
+// PINN_FLAG_SPACE_DIRECTION bits of a descriptor (0: no direction; lm_engine.hip::build_program validates them)
+static int space_dir_bits(const PinnNetDesc* d) { return d->flags & PINN_FLAG_SPACE_DIRECTION_MASK; }
+
+// A non-zero axis runs the layer-major engine, which also has units for the space-only sets (0, 1) .. (0, 4): the launches
+// of a further space axis (csrc/Makefile: ASETS).  With axis 0 they stay refused like any other uncompiled set.  A
+// direction launch runs there too and admits those four sets alone.
 static bool stream_set_admitted(const PinnNetDesc* d, int nt, int nx) {
+  const bool space_only = nt == 0 && nx >= 1 && nx <= 4;
+  if (space_dir_bits(d) != 0) {  // a descriptor the engine refuses (an invalid direction): lm_check reports that, not the set
+    char lerr[8];
+    return lm::lm_check(d, lerr, sizeof(lerr)) != PINN_OK || space_only;
+  }
   if (stream_set_compiled(nt, nx)) return true;
-  return space_axis_of(d) != 0 && nt == 0 && (nx == 1 || nx == 2);
+  return space_axis_of(d) != 0 && space_only;
 }
 
 // the compiled PDE kinds keep the reference's >= 2-D behaviour (every spatial derivative zero): no axis for them
@@ -347,6 +356,9 @@ static int refuse_axis(const PinnNetDesc* d, const char* entry) {
   if (d && space_axis_of(d) != 0)
     return fail(PINN_ERR_UNSUPPORTED, "%s: PINN_FLAG_SPACE_AXIS(%d) is set, and the compiled PDE kinds differentiate along the first "
                 "space axis only (derivatives along further axes: pinn_jet_forward + pinn_term_residual_axes)", entry, space_axis_of(d));
+  if (d && space_dir_bits(d) != 0)
+    return fail(PINN_ERR_UNSUPPORTED, "%s: PINN_FLAG_SPACE_DIRECTION is set, and the compiled PDE kinds differentiate along the first "
+                "space axis only (mixed derivatives: pinn_jet_forward + pinn_term_residual_mixed)", entry);
   return PINN_OK;
 }
 
@@ -367,7 +379,7 @@ static hipError_t dispatch_wide(int nt, int nx, const KernelArgs& a, bool bwd, i
 // the wide kernel runs this problem: program built, all K streams fit the LDS, engine not overridden
 static bool use_wide(const PinnNetDesc* d, const float* const* w, float* const* g, int K, bool bwd, NetDev* n, int* misaligned = nullptr) {
   if (force_lm()) return false;
-  if (space_axis_of(d) != 0) return false;  // the tile-major kernels seed their space streams from column 0 only
+  if (space_axis_of(d) != 0 || space_dir_bits(d) != 0) return false;  // the tile-major kernels seed their space streams from column 0 only
   if (!build_wide(d, w, g, n, misaligned)) return false;
   return jet_wide_fits(K, n->hmax, bwd, n->n_layers);
 }

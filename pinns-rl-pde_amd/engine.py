@@ -159,11 +159,28 @@ def _stream(dev: torch.device) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def _axis_desc(prog: "NetProgram", axis: int):
+def _axis_desc(prog: "NetProgram", axis: int, direction: Optional[Sequence[int]] = None):
     """The descriptor of a jet launch along space axis `axis`: the program's own for axis 0, else a BY-VALUE copy with
-    PINN_FLAG_SPACE_AXIS(axis) set.  The shared descriptor is never written: another stream may be sizing or launching with
-    it.  The same copy sizes the workspace and makes the call, so the engine that is sized is the engine that runs."""
+    PINN_FLAG_SPACE_AXIS(axis) set; with `direction` (a tuple of -1 / 0 / +1, one per space axis, exclusive with `axis`) a
+    by-value copy with PINN_FLAG_SPACE_DIRECTION set.  The shared descriptor is never written: another stream may be sizing
+    or launching with it.  The same copy sizes the workspace and makes the call, so the engine that is sized is the engine
+    that runs."""
     axis = int(axis)
+    if direction is not None:
+        direction = tuple(int(v) for v in direction)
+        if axis != 0:
+            raise ValueError(f"a jet launch runs along one line: axis={axis} and direction={direction} are exclusive")
+        if len(direction) > 3 or len(direction) > max(prog.input_dim - 1, 0) or any(v not in (-1, 0, 1) for v in direction):
+            raise ValueError(f"direction {direction}: one entry of -1, 0 or +1 per space axis (input_dim={prog.input_dim} has "
+                             f"{prog.input_dim - 1})")
+        nz = [v for v in direction if v]
+        if len(nz) < 2 or nz[0] != 1:
+            raise ValueError(f"direction {direction}: at least two non-zero entries, the first of them +1 (one entry is an axis; "
+                             "the negated direction adds nothing)")
+        d = _lib.PinnNetDesc.from_buffer_copy(prog.desc)
+        d.flags = ((d.flags & ~_lib.PINN_FLAG_SPACE_AXIS_MASK & ~_lib.PINN_FLAG_SPACE_DIRECTION_MASK)
+                   | _lib.PINN_FLAG_SPACE_DIRECTION(*direction))
+        return d
     if axis == 0:
         return prog.desc
     if not 0 < axis < prog.input_dim - 1:
@@ -289,6 +306,86 @@ class AxisTermDesc:
         return [(0, self.nt, self.nx[0])] + [(a, 0, self.nx[a]) for a in range(1, self.dimension) if self.nx[a] > 0]
 
 
+_PAIRS = ((0, 1), (0, 2), (1, 2))  # the pairs of axes of pair_order[k] / the P and Q blocks 3 + k, 6 + k
+_MIXED_2 = {"u_xy": 0, "u_xz": 1, "u_yz": 2}
+_MIXED_4 = {"u_xxyy": 0, "u_xxzz": 1, "u_yyzz": 2}
+
+
+class MixedTermDesc(AxisTermDesc):
+    """An `AxisTermDesc` with mixed derivatives (`pinn_term_residual_mixed`): its factor names plus "u_yyy", "u_yyyy",
+    "u_zzz", "u_zzzz", "u_xy", "u_xz", "u_yz", "u_xxyy", "u_xxzz", "u_yyzz" (`_lib.TERM_FACTOR_MIXED`).
+
+    nx[1] and nx[2] are 0 .. 4; pair: the order 0, 2 or 4 of the pairs (x, y), (x, z), (y, z).  A pair of order k adds one jet
+    launch of the set (0, k) along e_a + e_b (the P block) and, for k = 4, one along e_a - e_b (the Q block): u_ab and u_aabb
+    are fixed linear combinations of their rows 2 and 4 and of the order-2 / order-4 rows of the two axes, so "u_ab" needs
+    pair >= 2 and order >= 2 on both axes, "u_aabb" pair = 4 and order 4 on both.  Mixed space-time derivatives ("u_xt"),
+    third-order mixed ("u_xxy") and "u_xxxy"-type factors are not available."""
+
+    def __init__(self, terms: Sequence[Sequence[str]], coef_values: Tensor, dimension: int, nt: int, nx: Sequence[int],
+                 pair: Sequence[int] = (0, 0, 0), loss: str = "mse", huber_delta: float = 1.0):
+        if int(dimension) not in (2, 3):
+            raise ValueError(f"a mixed term residual has dimension 2 or 3 (got {dimension}); TermDesc is the 1-D form")
+        if len(terms) > _lib.PINN_TERM_MAX_TERMS:
+            raise ValueError(f"a term residual has at most {_lib.PINN_TERM_MAX_TERMS} terms (got {len(terms)})")
+        nx = tuple(int(v) for v in nx) + (0,) * (3 - len(nx))
+        if len(nx) != 3 or any(not 0 <= v <= 4 for v in nx[1:]) or any(v for v in nx[int(dimension):]):
+            raise ValueError(f"space orders {nx}: one per axis, 0 .. 4 on the axes y and z, 0 beyond the dimension")
+        pair = tuple(int(v) for v in pair) + (0,) * (3 - len(pair))
+        if len(pair) != 3 or any(v not in (0, 2, 4) for v in pair) or any(v and _PAIRS[k][1] >= int(dimension) for k, v in enumerate(pair)):
+            raise ValueError(f"pair orders {pair}: 0, 2 or 4 for the pairs (x, y), (x, z), (y, z), 0 for a pair beyond the dimension")
+        d = _lib.PinnTermPdeMixed()
+        d.dimension, d.time_order, d.n_terms = int(dimension), int(nt), len(terms)
+        for a in range(3):
+            d.space_order[a] = nx[a]
+            d.pair_order[a] = pair[a]
+        d.loss = _lib.LOSS.get(loss, 0)  # unknown names fall back to mse (pde_base.py:313-315)
+        d.huber_delta = float(huber_delta)
+        for m, factors in enumerate(terms):
+            if len(factors) > _lib.PINN_TERM_MAX_FACTORS:
+                raise ValueError(f"term {m}: at most {_lib.PINN_TERM_MAX_FACTORS} factors (got {len(factors)})")
+            d.terms[m].n_factors = len(factors)
+            for f, name in enumerate(factors):
+                if name not in _lib.TERM_FACTOR_MIXED:
+                    raise ValueError(f"term {m}: unknown factor '{name}' (one of {', '.join(_lib.TERM_FACTOR_MIXED)})")
+                for table, order in ((_MIXED_2, 2), (_MIXED_4, 4)):
+                    if name in table:
+                        k = table[name]
+                        a, b = _PAIRS[k]
+                        if (pair[k] < order or nx[a] < order or nx[b] < order) if order == 2 else (pair[k] != 4 or nx[a] != 4 or nx[b] != 4):
+                            raise ValueError(f"term {m}: '{name}' needs pair order {'>= 2' if order == 2 else '4'} and space order "
+                                             f"{'>= 2' if order == 2 else '4'} on both axes (pair orders {pair}, space orders {nx})")
+                d.terms[m].factor[f] = _lib.TERM_FACTOR_MIXED[name]
+        if coef_values.dtype != torch.float32 or not coef_values.is_contiguous() or coef_values.numel() < len(terms):
+            raise ValueError("coef_values: one contiguous float32 value per term")
+        self.desc = d
+        self.terms = [tuple(f) for f in terms]
+        self.coef_values = coef_values
+        self.dimension, self.nt, self.nx, self.pair = int(dimension), int(nt), nx, pair
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "MixedTermDesc":
+        """The same program and the same coefficient tensor under another loss kind."""
+        return MixedTermDesc(self.terms, self.coef_values, self.dimension, self.nt, self.nx, self.pair, loss, huber_delta)
+
+    def _direction(self, k: int, sign: int) -> Tuple[int, ...]:
+        a, b = _PAIRS[k]
+        return tuple(1 if c == a else (sign if c == b else 0) for c in range(self.dimension))
+
+    def launches(self) -> List[Tuple[object, int, int]]:
+        """(axis or direction tuple, nt, nx) of the jet launches of the chain: axis 0 first, then the further axes that have
+        streams, then the P blocks (direction e_a + e_b, set (0, pair order)), then the Q blocks (e_a - e_b, order 4 only)."""
+        out: List[Tuple[object, int, int]] = list(AxisTermDesc.launches(self))
+        out += [(self._direction(k, 1), 0, self.pair[k]) for k in range(3) if self.pair[k] >= 2]
+        out += [(self._direction(k, -1), 0, 4) for k in range(3) if self.pair[k] == 4]
+        return out
+
+    def blocks(self) -> List[int]:
+        """Index in the 9-entry tables of `pinn_term_residual_mixed` of every launch of `launches()`, in its order."""
+        out = [0] + [a for a in range(1, self.dimension) if self.nx[a] > 0]
+        out += [3 + k for k in range(3) if self.pair[k] >= 2]
+        out += [6 + k for k in range(3) if self.pair[k] == 4]
+        return out
+
+
 def pde_streams(pd) -> Tuple[int, int]:
     if isinstance(pd, AxisTermDesc):  # the set of the axis-0 launch
         return pd.nt, pd.nx[0]
@@ -302,13 +399,15 @@ def pde_streams(pd) -> Tuple[int, int]:
 # ---------------------------------------------------------------------------------------------
 # raw launches
 # ---------------------------------------------------------------------------------------------
-def jets_forward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, axis: int = 0) -> Tensor:
+def jets_forward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, axis: int = 0,
+                 direction: Optional[Sequence[int]] = None) -> Tensor:
     """(K, N) tensor of [u, d/dt.., d/dx_axis..] — one launch, no graph.  `axis`: the column of x the space streams
-    differentiate along (non-zero: the layer-major engine; also the sets (0, 1) and (0, 2))."""
+    differentiate along (non-zero: the layer-major engine; also the sets (0, 1) .. (0, 4)).  `direction`: a tuple of
+    -1 / 0 / +1 per space axis instead — the space streams are (sum_c d_c d/dx_c)^k u, sets (0, 1) .. (0, 4) only."""
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
-    desc = _axis_desc(prog, axis)
+    desc = _axis_desc(prog, axis, direction)
     K = 1 + nt + nx
     out = torch.empty((K, N), dtype=torch.float32, device=dev)
     if N == 0:
@@ -337,12 +436,13 @@ def split_flat_grad(prog: NetProgram, flat: Tensor) -> List[Optional[Tensor]]:
     return [flat[o : o + p.numel()].view_as(p) if o >= 0 else None for o, p in zip(offs, prog.tensors)]
 
 
-def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, flat_grad: Tensor, axis: int = 0) -> None:
-    """flat_grad += d<cot, jets>/d(theta).  cot: (K, N); `axis` as for `jets_forward`."""
+def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, flat_grad: Tensor, axis: int = 0,
+                  direction: Optional[Sequence[int]] = None) -> None:
+    """flat_grad += d<cot, jets>/d(theta).  cot: (K, N); `axis` and `direction` as for `jets_forward`."""
     lib = _lib.load()
     dev = _require_device(x, t, cot, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
-    desc = _axis_desc(prog, axis)
+    desc = _axis_desc(prog, axis, direction)
     if N == 0:
         return
     K = 1 + nt + nx
@@ -357,14 +457,14 @@ def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot:
 
 def jets_backward_inputs(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor,
                          flat_grad: Optional[Tensor], want_x: bool, want_t: bool,
-                         axis: int = 0) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+                         axis: int = 0, direction: Optional[Sequence[int]] = None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """(x_grad (N, dim) | None, t_grad (N, 1) | None) = d<cot, jets>/d(x, t), and flat_grad += d<cot, jets>/d(theta) when
     given — one `pinn_jet_backward_inputs` launch on the layer-major engine (the descriptor is not touched).  cot: (K, N);
-    `axis` as for `jets_forward` (every column of x_grad stays exact, mixed terms included)."""
+    `axis` and `direction` as for `jets_forward` (every column of x_grad stays exact, mixed terms included)."""
     lib = _lib.load()
     dev = _require_device(x, t, cot, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
-    desc = _axis_desc(prog, axis)
+    desc = _axis_desc(prog, axis, direction)
     want_x = bool(want_x) and x.shape[1] > 0
     xg = torch.empty_like(x) if want_x else None
     tg = torch.empty_like(t) if want_t else None
@@ -470,18 +570,79 @@ def term_residual_axes(td: AxisTermDesc, jets: Sequence[Optional[Tensor]], x: Te
     return r, cot
 
 
+def term_residual_mixed(td: MixedTermDesc, jets: Sequence[Optional[Tensor]], x: Tensor, t: Tensor, grad_scale: float = 0.0,
+                        residual_cotangent: Optional[Tensor] = None, want_residual: bool = True,
+                        loss_sum: Optional[Tensor] = None, want_cotangents: bool = False,
+                        coef_grads: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[List[Optional[Tensor]]]]:
+    """`pinn_term_residual_mixed`: (residual (N, 1) | None, cotangent blocks | None).  jets: the 9 blocks [axis0, axis1, axis2,
+    P_xy, P_xz, P_yz, Q_xy, Q_xz, Q_yz] — the axis blocks as for `term_residual_axes`, P / Q the (1 + pair order, N) blocks of
+    the launches along e_a + e_b / e_a - e_b, None where the descriptor has no such block.  The cotangent blocks have the shapes
+    of the jets; every row the program never reads is zero, so each goes straight into `jets_backward`.  Sums and launches as
+    `term_residual`."""
+    lib = _lib.load()
+    dim, nb = td.dimension, _lib.PINN_TERM_MIXED_BLOCKS
+    jets = list(jets) + [None] * (nb - len(jets))
+    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads)
+    rows = [1 + td.nt + td.nx[0]] + [(1 + td.nx[a]) if (a < dim and td.nx[a] > 0) else 0 for a in (1, 2)]
+    rows += [(1 + td.pair[k]) if td.pair[k] >= 2 else 0 for k in range(3)] + [5 if td.pair[k] == 4 else 0 for k in range(3)]
+    if len(jets) != nb or jets[0] is None or jets[0].dim() != 2:
+        raise ValueError(f"term_residual_mixed: {nb} blocks, jets[0] the (1 + nt + nx[0], N) block of the axis-0 launch")
+    N = jets[0].shape[1]
+    for b in range(nb):
+        j = jets[b]
+        if (j is None) != (rows[b] == 0) or (j is not None and (tuple(j.shape) != (rows[b], N) or j.dtype != torch.float32
+                                                               or not j.is_contiguous())):
+            raise ValueError(f"term_residual_mixed: block {b} must be {'None' if rows[b] == 0 else f'a contiguous float32 ({rows[b]}, {N}) tensor'}")
+    x, t = _f32c(x.detach()), _f32c(t.detach())
+    if x.numel() != N * dim or t.numel() != N:
+        raise ValueError(f"term_residual_mixed: x is (N, {dim}) and t holds N values (N = {N}; got {tuple(x.shape)}, {tuple(t.shape)})")
+    if residual_cotangent is not None:
+        residual_cotangent = _f32c(residual_cotangent).reshape(-1)
+        assert residual_cotangent.numel() == N
+    for tns in (loss_sum, coef_grads):
+        assert tns is None or (tns.dtype == torch.float32 and tns.is_contiguous())
+    assert coef_grads is None or coef_grads.numel() >= td.desc.n_terms
+    r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
+    cot = [torch.empty((k, N), dtype=torch.float32, device=dev) if k else None for k in rows] if want_cotangents else None
+    if N == 0:
+        return r, cot
+    reduce = loss_sum is not None or coef_grads is not None
+    scratch = torch.empty(_lib.PINN_TERM_SCRATCH_DOUBLES, dtype=torch.float64, device=dev) if reduce else None
+    opt = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
+    jptr = (ctypes.c_void_p * nb)(*[opt(j) for j in jets])
+    cptr = (ctypes.c_void_p * nb)(*[opt(c) for c in cot]) if cot is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_term_residual_mixed(ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(),
+                                                N, float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum), cptr,
+                                                opt(coef_grads), opt(scratch), _stream(dev)))
+    return r, cot
+
+
+def _launch_line(key) -> dict:
+    """The keyword of `jets_forward` / `jets_backward` for one entry of `launches()`: an axis, or a direction tuple."""
+    return {"direction": key} if isinstance(key, tuple) else {"axis": key}
+
+
+def _launch_blocks(td: AxisTermDesc) -> List[int]:
+    return td.blocks() if isinstance(td, MixedTermDesc) else [a for a, _, _ in td.launches()]
+
+
+def _term_residual_nd(td: AxisTermDesc, *args, **kwargs):
+    return (term_residual_mixed if isinstance(td, MixedTermDesc) else term_residual_axes)(td, *args, **kwargs)
+
+
 def _axes_jets(prog: NetProgram, td: AxisTermDesc, x: Tensor, t: Tensor) -> List[Optional[Tensor]]:
-    """The forward half of an `AxisTermDesc` chain: one jets_forward per axis that has streams."""
-    jets: List[Optional[Tensor]] = [None, None, None]
-    for a, nt, nx in td.launches():
-        jets[a] = jets_forward(prog, x, t, nt, nx, axis=a)
+    """The forward half of an `AxisTermDesc` / `MixedTermDesc` chain: one jets_forward per launch of the descriptor."""
+    jets: List[Optional[Tensor]] = [None] * (_lib.PINN_TERM_MIXED_BLOCKS if isinstance(td, MixedTermDesc) else 3)
+    for b, (key, nt, nx) in zip(_launch_blocks(td), td.launches()):
+        jets[b] = jets_forward(prog, x, t, nt, nx, **_launch_line(key))
     return jets
 
 
 def _axes_backward(prog: NetProgram, td: AxisTermDesc, x: Tensor, t: Tensor, cot: Sequence[Optional[Tensor]], flat_grad: Tensor) -> None:
-    """The reverse half: one jets_backward per axis, all accumulating into the same flat gradient."""
-    for a, nt, nx in td.launches():
-        jets_backward(prog, x, t, nt, nx, cot[a], flat_grad, axis=a)
+    """The reverse half: one jets_backward per launch, all accumulating into the same flat gradient."""
+    for b, (key, nt, nx) in zip(_launch_blocks(td), td.launches()):
+        jets_backward(prog, x, t, nt, nx, cot[b], flat_grad, **_launch_line(key))
 
 
 def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: bool = True,
@@ -494,7 +655,7 @@ def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: 
     x, t, N = _prep_points(prog, x, t)
     if isinstance(pd, AxisTermDesc) and N:  # the chain over the axes: one jet launch each, then the element-wise residual
         s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
-        r, _ = term_residual_axes(pd, _axes_jets(prog, pd, x, t), x, t, want_residual=want_residual, loss_sum=s)
+        r, _ = _term_residual_nd(pd, _axes_jets(prog, pd, x, t), x, t, want_residual=want_residual, loss_sum=s)
         return r, s
     if isinstance(pd, TermDesc) and N:  # the chain: jets, then the element-wise residual
         s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
@@ -527,8 +688,8 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
         # the chain over the axes: one jet launch per axis, the element-wise residual with its loss sum and one block of
         # cotangents per launch, one reverse sweep per axis into the same flat gradient
         s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
-        r, cot = term_residual_axes(pd, _axes_jets(prog, pd, x, t), x, t, grad_scale=grad_scale, want_residual=want_residual,
-                                    loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
+        r, cot = _term_residual_nd(pd, _axes_jets(prog, pd, x, t), x, t, grad_scale=grad_scale, want_residual=want_residual,
+                                   loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
         _axes_backward(prog, pd, x, t, cot, flat_grad)
         return r, s
     if isinstance(pd, TermDesc) and N:
@@ -604,8 +765,8 @@ def residual_backward(prog: NetProgram, pd, x: Tensor, t: Tensor, res_bar: Tenso
     res_bar = _f32c(res_bar).reshape(-1)
     assert res_bar.numel() == N
     if isinstance(pd, AxisTermDesc):  # the chain over the axes with the caller's cotangent in place of grad_scale l'(r)
-        _, cot = term_residual_axes(pd, _axes_jets(prog, pd, x, t), x, t, residual_cotangent=res_bar, want_residual=False,
-                                    want_cotangents=True)
+        _, cot = _term_residual_nd(pd, _axes_jets(prog, pd, x, t), x, t, residual_cotangent=res_bar, want_residual=False,
+                                   want_cotangents=True)
         _axes_backward(prog, pd, x, t, cot, flat_grad)
         return
     if isinstance(pd, TermDesc):  # the chain with the caller's cotangent in place of grad_scale l'(r)

@@ -6,6 +6,7 @@ from .equations import (  # noqa: F401
 )
 from .pde_base import PDEBase, PDEConfig  # noqa: F401
 from .term_pde import TermPDE  # noqa: F401
+from .term_pde_mixed import TermPDEMixed  # noqa: F401
 from .term_pde_nd import TermPDEnD  # noqa: F401
 
 _BY_TYPE = {

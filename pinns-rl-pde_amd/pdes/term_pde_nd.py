@@ -8,7 +8,8 @@ per axis, and `pinn_term_residual_axes` combines the streams of all launches int
 
 with one block of cotangents per launch for the reverse sweeps.  Residual, loss and gradient stay free of autograd, so the
 launch list, the captured step, the flat L-BFGS closure and the residual-based sampler take such a PDE as they take
-`TermPDE`.  Mixed derivatives (u_xy) and orders above two on the axes y and z are not available.
+`TermPDE`.  Mixed derivatives (u_xy) and orders above two on the axes y and z are not available here: `TermPDEMixed`
+(term_pde_mixed.py) adds them.
 
 Boundary and initial conditions are the class's own: the nine compiled classes keep the reference's behaviour in >= 2-D, where
 its boundary points do not fit the model.  Here every face of the box carries a tensor grid of the other coordinates and of
@@ -27,6 +28,7 @@ from .pde_base import PDEBase, PDEConfig, _pick_stream_set
 from .term_pde import _T_ORDER, _X_ORDER, Coef
 
 _AXIS_ORDER = {"u_y": (1, 1), "u_yy": (1, 2), "u_z": (2, 1), "u_zz": (2, 2)}  # factor -> (axis, order)
+_PAIR_AXES = ((0, 1), (0, 2), (1, 2))  # the pairs of axes a mixed factor can name (`engine.MixedTermDesc`)
 _COORD_AXIS = {"x": 0, "y": 1, "z": 2}
 
 
@@ -47,6 +49,12 @@ class TermPDEnD(PDEBase):
     """
 
     KIND = "term_nd"  # not a `_lib.PDE` kind: the descriptor is an `AxisTermDesc`
+    # what a subclass with more factors replaces (TermPDEMixed): the factor names, the (axis, order) of the names beyond
+    # TermPDE's, the (pair, order) of the mixed names, and the tail of the unknown-factor message
+    _FACTORS = _lib.TERM_FACTOR_ND
+    _AXIS_ORDER = _AXIS_ORDER
+    _PAIR_ORDER: Dict[str, Tuple[int, int]] = {}
+    _FACTOR_NOTE = "mixed derivatives and orders above two along y and z are not available"
 
     def __init__(self, config: PDEConfig, terms: Sequence[Tuple[Coef, Sequence[str]]],
                  initial_condition_fn: Callable[[torch.Tensor], torch.Tensor],
@@ -54,37 +62,44 @@ class TermPDEnD(PDEBase):
                  boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32, **kwargs):
         dim = int(getattr(config, "dimension", 1))
         if dim not in (2, 3):
-            raise NotImplementedError(f"TermPDEnD: dimension {dim}: two or three space dimensions (TermPDE runs 1-D problems)")
+            raise NotImplementedError(f"{type(self).__name__}: dimension {dim}: two or three space dimensions (TermPDE runs 1-D problems)")
         if not callable(initial_condition_fn):
-            raise TypeError("TermPDEnD: initial_condition_fn(x: (n, dim)) -> (n,) is required (the reference's 1-D initial "
+            raise TypeError(f"{type(self).__name__}: initial_condition_fn(x: (n, dim)) -> (n,) is required (the reference's 1-D initial "
                             "condition kinds have no n-D form)")
         if int(boundary_points_per_axis) < 2 or int(initial_points_per_axis) < 2:
-            raise ValueError("TermPDEnD: at least 2 boundary and 2 initial points per axis")
+            raise ValueError(f"{type(self).__name__}: at least 2 boundary and 2 initial points per axis")
         terms = list(terms)
         if len(terms) > _lib.PINN_TERM_MAX_TERMS:
-            raise ValueError(f"TermPDEnD: {len(terms)} terms; a residual has at most {_lib.PINN_TERM_MAX_TERMS}")
+            raise ValueError(f"{type(self).__name__}: {len(terms)} terms; a residual has at most {_lib.PINN_TERM_MAX_TERMS}")
         self._term_coefs: List[Coef] = []
         self._term_factors: List[Tuple[str, ...]] = []
-        nt, nx = 0, [0, 0, 0]
+        nt, nx, pair = 0, [0, 0, 0], [0, 0, 0]
         for m, (coef, factors) in enumerate(terms):
             factors = (factors,) if isinstance(factors, str) else tuple(factors)
             if len(factors) > _lib.PINN_TERM_MAX_FACTORS:
-                raise ValueError(f"TermPDEnD: term {m} has {len(factors)} factors; a term has at most {_lib.PINN_TERM_MAX_FACTORS}")
+                raise ValueError(f"{type(self).__name__}: term {m} has {len(factors)} factors; a term has at most {_lib.PINN_TERM_MAX_FACTORS}")
             for f in factors:
-                if f not in _lib.TERM_FACTOR_ND:
-                    raise ValueError(f"TermPDEnD: term {m}: unknown factor '{f}' (one of {', '.join(_lib.TERM_FACTOR_ND)}; mixed "
-                                     "derivatives and orders above two along y and z are not available)")
-                axis = _AXIS_ORDER[f][0] if f in _AXIS_ORDER else _COORD_AXIS.get(f, 0)
+                if f not in self._FACTORS:
+                    raise ValueError(f"{type(self).__name__}: term {m}: unknown factor '{f}' (one of {', '.join(self._FACTORS)}; "
+                                     f"{self._FACTOR_NOTE})")
+                axis = self._AXIS_ORDER[f][0] if f in self._AXIS_ORDER else _COORD_AXIS.get(f, 0)
+                if f in self._PAIR_ORDER:
+                    axis = _PAIR_AXES[self._PAIR_ORDER[f][0]][1]
                 if axis >= dim:
-                    raise ValueError(f"TermPDEnD: term {m}: factor '{f}' needs dimension {axis + 1}, the problem has {dim}")
+                    raise ValueError(f"{type(self).__name__}: term {m}: factor '{f}' needs dimension {axis + 1}, the problem has {dim}")
                 nt = max(nt, _T_ORDER.get(f, 0))
                 nx[0] = max(nx[0], _X_ORDER.get(f, 0))
-                if f in _AXIS_ORDER:
-                    a, k = _AXIS_ORDER[f]
+                if f in self._AXIS_ORDER:
+                    a, k = self._AXIS_ORDER[f]
                     nx[a] = max(nx[a], k)
+                if f in self._PAIR_ORDER:  # u_ab / u_aabb: the pair's launches and the same order on both of its axes
+                    j, k = self._PAIR_ORDER[f]
+                    pair[j] = max(pair[j], k)
+                    for a in _PAIR_AXES[j]:
+                        nx[a] = max(nx[a], k)
             if isinstance(coef, (tuple, list)):
                 if len(coef) != 2 or not isinstance(coef[1], str):
-                    raise ValueError(f"TermPDEnD: term {m}: a coefficient is a number or (scale, 'parameter name')")
+                    raise ValueError(f"{type(self).__name__}: term {m}: a coefficient is a number or (scale, 'parameter name')")
                 coef = (float(coef[0]), coef[1])
             else:
                 coef = float(coef)
@@ -94,30 +109,31 @@ class TermPDEnD(PDEBase):
             self._nt, nx[0] = _pick_stream_set(nt, nx[0])
         except NotImplementedError:
             raise NotImplementedError(
-                f"TermPDEnD: the factors need time order {nt} together with order {nx[0]} along x, and no compiled stream set "
+                f"{type(self).__name__}: the factors need time order {nt} together with order {nx[0]} along x, and no compiled stream set "
                 "holds both (time order 2 goes with space order 0 or 2)") from None
         self._nx = tuple(nx)
+        self._pair = tuple(pair)
         bcs = dict(getattr(config, "boundary_conditions", None) or {})
         if list(bcs) == ["dirichlet"]:
             p = bcs["dirichlet"] or {}
             if p.get("type", "fixed") != "fixed":
-                raise NotImplementedError(f"TermPDEnD: dirichlet boundary of type '{p.get('type')}': a fixed value on all faces only")
+                raise NotImplementedError(f"{type(self).__name__}: dirichlet boundary of type '{p.get('type')}': a fixed value on all faces only")
             self._bc = ("dirichlet", float(p.get("value", 0.0)))
         elif list(bcs) == ["periodic"]:
             self._bc = ("periodic", 0.0)
         else:
             raise NotImplementedError(
-                f"TermPDEnD: boundary conditions {sorted(bcs)}: exactly one of {{'dirichlet': {{'type': 'fixed', 'value': v}}}} on "
+                f"{type(self).__name__}: boundary conditions {sorted(bcs)}: exactly one of {{'dirichlet': {{'type': 'fixed', 'value': v}}}} on "
                 "all faces or {'periodic': {}} (Neumann and Robin faces read derivative streams on the faces: not available)")
         if list(getattr(config, "trainable_parameters", []) or []):
-            raise NotImplementedError("TermPDEnD: trainable parameters (inverse problems) are not covered: the coefficients of a "
+            raise NotImplementedError(f"{type(self).__name__}: trainable parameters (inverse problems) are not covered: the coefficients of a "
                                       "term residual are read by value")
         super().__init__(config)
         if self._training_mode() != "forward" or self.observation_data:
-            raise NotImplementedError("TermPDEnD: data modes and observation data are not covered (forward problems only)")
+            raise NotImplementedError(f"{type(self).__name__}: data modes and observation data are not covered (forward problems only)")
         for coef in self._term_coefs:
             if isinstance(coef, tuple) and self.get_parameter(coef[1]) is None:
-                raise ValueError(f"TermPDEnD: coefficient parameter '{coef[1]}' is not in config.parameters")
+                raise ValueError(f"{type(self).__name__}: coefficient parameter '{coef[1]}' is not in config.parameters")
         self._initial_condition_fn = initial_condition_fn
         self._exact_solution_fn = exact_solution_fn
         self._nb, self._ni = int(boundary_points_per_axis), int(initial_points_per_axis)
@@ -158,7 +174,7 @@ class TermPDEnD(PDEBase):
 
     def exact_solution(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         if self._exact_solution_fn is None:
-            raise NotImplementedError("TermPDEnD: no exact_solution_fn was given")
+            raise NotImplementedError(f"{type(self).__name__}: no exact_solution_fn was given")
         return self._exact_solution_fn(x, t).reshape(-1, 1)
 
     # ---------------------------------------------------------------- fixed evaluation points
@@ -198,7 +214,7 @@ class TermPDEnD(PDEBase):
         with torch.no_grad():
             u0 = self._initial_condition_fn(xi).reshape(-1).float().contiguous()
         if u0.shape[0] != xi.shape[0]:
-            raise ValueError(f"TermPDEnD: initial_condition_fn returned {u0.shape[0]} values for {xi.shape[0]} points")
+            raise ValueError(f"{type(self).__name__}: initial_condition_fn returned {u0.shape[0]} values for {xi.shape[0]} points")
         pts = {"x": torch.cat(xs, 0).float().contiguous(), "t": torch.cat(ts, 0).float().contiguous(), "n_face": n_face,
                "n_bc": 2 * dim * n_face, "n_ic": xi.shape[0], "u0": u0.to(dev)}
         if self._bc[0] == "dirichlet":

@@ -2,7 +2,7 @@
 
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
-                               [--term-pde] [--term-nd] [--causal M,EPS]
+                               [--term-pde] [--term-nd] [--term-mixed] [--causal M,EPS]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -28,6 +28,12 @@ compiled kind's `pinn_residual_loss_grad`.
 `--term-nd` runs N1 and N2 instead of C1..C4: the heat equation u_t - a Laplacian(u) on fourier 4x128 with 49 729 points, in
 1-D as a `TermPDE` (the yardstick) and in 2-D as a `TermPDEnD`, whose residual part is one jet launch per space axis in each
 sweep around `pinn_term_residual_axes` (the launch along y on the layer-major engine).
+
+`--term-mixed` runs M1, M2 and M3 instead: fourier 4x128 with 49 729 points in 2-D — M1 the heat equation as a `TermPDEnD`
+(N2 above, the yardstick), M2 anisotropic diffusion u_t - a u_xx - 2 b u_xy - c u_yy as a `TermPDEMixed` (one more launch pair,
+along e_x + e_y on the set (0, 2)), M3 the 2-D Cahn-Hilliard equation written out as ten terms (four launch pairs: x on (1, 4),
+y, e_x + e_y and e_x - e_y on (0, 4)).  After the step table it times every launch of each chain on its own (device time
+between two events, the step's batch).
 
 `--causal M,EPS` turns on the causal (time-weighted) residual loss (`training.causal_weighting`: M time bins, sharpness
 EPS): the autograd mode builds the weighted loss with torch ops on the residual tensor, the other two run the residual part
@@ -81,7 +87,27 @@ def _heat_nd(dim):
     return f"Heat {dim}D (u_t - a Laplacian u) as TermPDEnD, fourier 4x128", net, P.TermPDEnD(pc, _heat_terms(dim), ic), 49729
 
 
-ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2)}
+ANISO_TERMS = [(1.0, ("u_t",)), ((-1.0, "a"), ("u_xx",)), ((-2.0, "b"), ("u_xy",)), ((-1.0, "c"), ("u_yy",))]
+# u_t + eps^2 (u_xxxx + 2 u_xxyy + u_yyyy) - 3 u^2 (u_xx + u_yy) - 6 u (u_x^2 + u_y^2) + u_xx + u_yy
+CAHN_HILLIARD_2D_TERMS = [(1.0, ("u_t",)), ((1.0, "eps2"), ("u_xxxx",)), ((2.0, "eps2"), ("u_xxyy",)), ((1.0, "eps2"), ("u_yyyy",)),
+                          (-3.0, ("u", "u", "u_xx")), (-3.0, ("u", "u", "u_yy")), (-6.0, ("u", "u_x", "u_x")),
+                          (-6.0, ("u", "u_y", "u_y")), (1.0, ("u_xx",)), (1.0, ("u_yy",))]
+
+
+def _mixed_2d(which):
+    """2-D problems with mixed derivatives as `TermPDEMixed` on fourier 4x128, 49 729 points."""
+    net = B.model("fourier", 128, 4, "tanh", input_dim=3)
+    params, terms, label = {"aniso": ({"a": 0.01, "b": 0.004, "c": 0.02}, ANISO_TERMS, "Anisotropic diffusion 2D (u_t - a u_xx - 2b u_xy - c u_yy)"),
+                            "ch": ({"eps2": 1e-4}, CAHN_HILLIARD_2D_TERMS, "Cahn-Hilliard 2D (ten terms)")}[which]
+    pc = P.PDEConfig(name=which, domain=[(0.0, 1.0)] * 2, time_domain=(0.0, 1.0), parameters=params,
+                     boundary_conditions={"dirichlet": {"type": "fixed", "value": 0.0}}, initial_condition={"type": "sine"},
+                     exact_solution={}, dimension=2, device=B.dev)
+    ic = lambda x: torch.prod(torch.sin(math.pi * x), dim=1)  # noqa: E731
+    return f"{label} as TermPDEMixed, fourier 4x128", net, P.TermPDEMixed(pc, terms, ic), 49729
+
+
+ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2),
+              "M1": lambda: _heat_nd(2), "M2": lambda: _mixed_2d("aniso"), "M3": lambda: _mixed_2d("ch")}
 
 
 def build(tag, adaptive="none", smoothness=0.0, term_pde=False, causal=None):
@@ -224,6 +250,43 @@ def time_term_launches(tag, iters=20):
         print(f"| {label} | {a.elapsed_time(b) / iters:.4f} |", flush=True)
 
 
+def time_nd_launches(tag, iters=20):
+    """Device time of every launch of an n-D term chain on its own: one jet launch per line forward, the element-wise
+    residual, one reverse sweep per line."""
+    torch.manual_seed(0)
+    name, net, eq, n_req = ND_CONFIGS[tag]()
+    x, t = eq._sample_uniform(n_req)
+    prog, td = net.program(), eq._pde_desc()
+    n = int(x.shape[0])
+    flat, s = E.new_flat_grad(prog, B.dev), torch.zeros(1, device=B.dev)
+    jets = E._axes_jets(prog, td, x, t)
+    _, cot = E._term_residual_nd(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
+    calls = []
+    for b, (key, nt, nx) in zip(E._launch_blocks(td), td.launches()):
+        line = E._launch_line(key)
+        calls.append((f"pinn_jet_forward along {key}, set ({nt}, {nx})", lambda nt=nt, nx=nx, line=line: E.jets_forward(prog, x, t, nt, nx, **line)))
+        calls.append((f"pinn_jet_backward along {key}, set ({nt}, {nx})",
+                      lambda nt=nt, nx=nx, line=line, b=b: E.jets_backward(prog, x, t, nt, nx, cot[b], flat, **line)))
+    kind = "mixed" if isinstance(td, E.MixedTermDesc) else "axes"
+    calls.append((f"pinn_term_residual_{kind} (loss sum + cotangents, two launches)",
+                  lambda: E._term_residual_nd(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
+    calls.append(("the chain through engine.residual_loss_grad", lambda: E.residual_loss_grad(prog, td, x, t, 1.0 / n, flat, loss_sum=s)))
+    print()
+    print(f"| {tag} launch ({n} points) | ms |")
+    print("|---|---|")
+    for label, fn in calls:
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        print(f"| {label} | {a.elapsed_time(b) / iters:.4f} |", flush=True)
+
+
 def time_causal_launches(tag, causal, iters=20):
     """Device time of the launches of the causal chain, each on its own, and of the one fused launch they replace."""
     torch.manual_seed(0)
@@ -276,9 +339,13 @@ def main():
     ap.add_argument("--term-pde", action="store_true", help="C2 only: Burgers as a TermPDE, and the chain's launches on their own")
     ap.add_argument("--causal", default="", metavar="M,EPS", help="causal residual weighting: M time bins, sharpness EPS")
     ap.add_argument("--term-nd", action="store_true", help="N1, N2: the heat Laplacian in 1-D (TermPDE) and 2-D (TermPDEnD), fourier 4x128")
+    ap.add_argument("--term-mixed", action="store_true",
+                    help="M1, M2, M3: 2-D heat (TermPDEnD), anisotropic diffusion and Cahn-Hilliard (TermPDEMixed), fourier 4x128")
     args = ap.parse_args()
     if args.term_nd and args.configs == "C1,C2,C3,C4":
         args.configs = "N1,N2"
+    if args.term_mixed and args.configs == "C1,C2,C3,C4":
+        args.configs = "M1,M2,M3"
     causal = None
     if args.causal:
         m, e = args.causal.split(",")
@@ -335,6 +402,8 @@ def main():
             torch.cuda.empty_cache()
         if args.term_pde and tag == "C2":
             time_term_launches(tag)
+        if args.term_mixed and tag in ND_CONFIGS:
+            time_nd_launches(tag)
         if causal is not None and not args.term_pde:
             time_causal_launches(tag, causal)
 
