@@ -212,6 +212,38 @@ int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32
 int pinn_kernel_name(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
                      char* buf, size_t len);
 
+/* Launch plan of the layer-major engine for the call pinn_kernel_for describes — from the functions the engine launches
+ * from (fusion plan, features per thread, AUX choice of the fused kernels, LDS-DMA predicate of the LayerNorm adjoint),
+ * under the policy this process read from its environment.  The engine is planned whether or not the call would take it
+ * (what PINN_FLAG_LAYER_MAJOR selects; pinn_kernel_for says which engine runs).  Record m < n describes GEMM node m and
+ * its prologue ([LayerNorm] [+ skip record] [activation] of the node's input); record n is the head: the prologue of the
+ * output layer, and lm_head.  A prologue runs forward either in the epilogue of the GEMM before it (lm_fused forward of
+ * node m - 1) or as an element-wise launch of its own; its adjoint runs in the epilogue of its own node's reverse GEMM
+ * (lm_fused reverse of node m) or as an element-wise launch.  `backward` = 0: the reverse fields are -1 / 0.
+ * Returns n (the number of GEMM nodes; n + 1 records are written, at most PINN_LM_MAX_PLAN), or a negative PinnStatus. */
+#define PINN_LM_MAX_PLAN 41
+typedef struct PinnLmNodePlan {
+  int32_t rows, depth;    /* the node's GEMM: padded out- and in-features (head: 1, padded width) */
+  int32_t width;          /* padded features of the prologue (= depth) */
+  int32_t has_ln, has_skip, has_add;  /* prologue: LayerNorm, skip record; node: epilogue add record */
+  int32_t act_family;     /* compiled family of the prologue: PinnAct 0..4 (leaky_relu, identity and "no activation" run
+                             relu's), -1 for Fourier features and for an identity prologue (no launch) */
+  int32_t src_kind;       /* 0 record, 1 first Linear of the coordinates, 2 Fourier features of the coordinates */
+  /* forward: how the prologue is computed */
+  int32_t fwd_fused;      /* 1: by lm_fused<nch, rt, .., LN, forward, aux> of the node before, on gy row blocks */
+  int32_t fwd_nch, fwd_rt, fwd_gy, fwd_aux;  /* -1 unless fwd_fused */
+  int32_t fwd_ew_kind;    /* 0 lm_ew_fwd, 2 lm_fourier_fwd, -1 none (fused, or an identity prologue) */
+  int32_t fwd_fpt;        /* features per thread of that launch, -1 if none */
+  /* reverse: how the prologue's adjoint is computed */
+  int32_t bwd_fused;      /* 1: by lm_fused<nch, rt, .., LN, reverse, aux> of this node */
+  int32_t bwd_nch, bwd_rt, bwd_gy, bwd_aux;
+  int32_t bwd_ew_kind;    /* 0 lm_ew_bwd, 1 lm_ew_bwd_dma, 2 lm_fourier_bwd (backward = 2 only), -1 none */
+  int32_t bwd_fpt;
+  int32_t head_fpt;       /* head record: features per thread of lm_head; -1 elsewhere */
+} PinnLmNodePlan;
+int pinn_lm_plan(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
+                 PinnLmNodePlan* out, int32_t max_records);
+
 /* How jet_kernel_u16 deals N points to `grid` workgroups (the grid of pinn_kernel_for).  rounds = R = N / (16 grid):
  * workgroup b runs the 16-point units b, b + grid, ... of R full rounds.  The points from first_tail_point = 16 grid R on
  * are the last round, groups = G = ceil((N - first_tail_point) / (4 grid)) four-point groups per workgroup:

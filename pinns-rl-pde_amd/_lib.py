@@ -77,7 +77,7 @@ EXPORTS = (
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
-    "pinn_term_residual_mixed",
+    "pinn_term_residual_mixed", "pinn_lm_plan",
 )
 
 
@@ -130,6 +130,16 @@ class PinnKernelInfo(ctypes.Structure):
         ("act_family", ctypes.c_int32), ("backward", ctypes.c_int32), ("hmax", ctypes.c_int32), ("na0", ctypes.c_int32),
         ("grid", ctypes.c_int32), ("flush", ctypes.c_int32), ("default_mfma_form", ctypes.c_int32),
     ]
+
+
+PINN_LM_MAX_PLAN = 41
+
+
+class PinnLmNodePlan(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int32) for f in (
+        "rows", "depth", "width", "has_ln", "has_skip", "has_add", "act_family", "src_kind",
+        "fwd_fused", "fwd_nch", "fwd_rt", "fwd_gy", "fwd_aux", "fwd_ew_kind", "fwd_fpt",
+        "bwd_fused", "bwd_nch", "bwd_rt", "bwd_gy", "bwd_aux", "bwd_ew_kind", "bwd_fpt", "head_fpt")]
 
 
 ENGINE_LAYER_MAJOR, ENGINE_TILE_MAJOR = 0, 1
@@ -190,6 +200,8 @@ def load():
         lib.pinn_kernel_for.argtypes = [P(PinnNetDesc), i64, i32, i32, i32, P(PinnKernelInfo)]
         lib.pinn_kernel_name.restype = ctypes.c_int
         lib.pinn_kernel_name.argtypes = [P(PinnNetDesc), i64, i32, i32, i32, ctypes.c_char_p, sz]
+        lib.pinn_lm_plan.restype = ctypes.c_int
+        lib.pinn_lm_plan.argtypes = [P(PinnNetDesc), i64, i32, i32, i32, P(PinnLmNodePlan), i32]
         lib.pinn_jet_forward.restype = ctypes.c_int
         lib.pinn_jet_forward.argtypes = [P(PinnNetDesc), P(vp), i32, vp, vp, i64, i32, i32, P(vp), vp, sz, vp]
         lib.pinn_jet_backward.restype = ctypes.c_int
@@ -272,6 +284,17 @@ def kernel_for(prog, N: int, nt: int, nx: int, backward: int) -> dict:
     out["flush"] = FLUSH.get(info.flush)
     out["default_mfma_form"] = bool(info.default_mfma_form)
     return out
+
+
+def lm_plan(prog, N: int, nt: int, nx: int, backward: int) -> list:
+    """Launch plan of the layer-major engine for such a call (pinn_lm_plan): one dict per GEMM node — the node's prologue,
+    and how it runs forward and in reverse (fused epilogue: nch, rt, gy, aux; element-wise launch: kind, fpt) — and a last
+    one for the head.  The engine is planned whether or not the call takes it (kernel_for says which engine runs)."""
+    recs = (PinnLmNodePlan * PINN_LM_MAX_PLAN)()
+    n = load().pinn_lm_plan(ctypes.byref(prog.desc), int(N), int(nt), int(nx), int(backward), recs, PINN_LM_MAX_PLAN)
+    if n < 0:
+        check(n)
+    return [{f: getattr(recs[m], f) for f, _ in PinnLmNodePlan._fields_} for m in range(n + 1)]
 
 
 def kernel_name(prog, N: int, nt: int, nx: int, backward: int) -> str:

@@ -43,6 +43,8 @@ int lm_expected_tensors(const PinnNetDesc* d);
 int lm_check(const PinnNetDesc* d, char* err, size_t errlen);
 size_t lm_workspace_bytes(const PinnNetDesc* d, long long N, int nt, int nx, bool bwd, bool deterministic);
 int lm_run(const CallArgs& c, char* err, size_t errlen);
+// the launches lm_run makes for this descriptor and stream set, from the same decisions (pinn_lm_plan): nodes, or a PinnStatus
+int lm_plan(const PinnNetDesc* d, int nt, int nx, int backward, PinnLmNodePlan* out, int max_records, char* err, size_t errlen);
 
 // per-stream-set translation units (lm_inst.hip); `act` = PinnAct, -1 = none, -2 = Fourier features (reverse: input cotangents)
 #define PINN_LM_DECL(nt, nx)                                                                              \

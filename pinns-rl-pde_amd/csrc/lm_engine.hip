@@ -643,6 +643,38 @@ bool fuse_shape(int rows, int depth, bool ln, Program::Fuse& f) {
   return false;
 }
 
+// the compiled activation family of a prologue: piecewise linear ones (slope in act_param), "no activation" included, are relu's
+int act_family_of(int act) { return (act == PINN_ACT_TANH || act == PINN_ACT_SIN || act == PINN_ACT_GELU || act == PINN_ACT_SIGMOID) ? act : PINN_ACT_RELU; }
+
+// Does the adjoint of a prologue run at all (as a fused reverse epilogue or an element-wise launch)?  Fourier features
+// straight from the coordinates have nothing upstream to differentiate, and a first Linear nobody wants a gradient of
+// neither — unless the call wants input cotangents.
+bool adjoint_runs(const Prologue& pro, bool want_xg, bool enc_grads) {
+  const bool xg = want_xg && pro.src_kind != SRC_REC;
+  const bool upstream = pro.src_kind == SRC_REC || pro.src_kind == SRC_COORDS_LINEAR || pro.ln_g >= 0 || pro.skip_node >= 0 || xg;
+  if (!upstream) return false;
+  return !(pro.src_kind == SRC_COORDS_LINEAR && !enc_grads && pro.ln_g < 0 && pro.skip_node < 0 && !xg);
+}
+
+// Extra cotangents of the V records, in the order the reverse sweep meets them (head first, then the nodes from the last;
+// per node its epilogue add, then its prologue's skip): kind 1 = Pbar of prologue idx (kMaxNodes: the head's), 2 = Zbar of
+// node idx.  A record has at most two.
+struct ExtraSrc {
+  int kind, idx;
+};
+void plan_extras(const Program& P, ExtraSrc (*ex)[2]) {
+  for (int m = 0; m < kMaxNodes; ++m) ex[m][0] = ex[m][1] = ExtraSrc{0, 0};
+  auto add = [&](int m, ExtraSrc e) {
+    if (!ex[m][0].kind) ex[m][0] = e;
+    else ex[m][1] = e;
+  };
+  if (P.head.skip_node >= 0) add(P.head.skip_node, ExtraSrc{1, kMaxNodes});
+  for (int m = P.n_nodes - 1; m >= 0; --m) {
+    if (P.node[m].add_node >= 0) add(P.node[m].add_node, ExtraSrc{2, m});
+    if (P.node[m].pro.skip_node >= 0) add(P.node[m].pro.skip_node, ExtraSrc{1, m});
+  }
+}
+
 const Prologue& consumer_of(const Program& P, int m) { return m + 1 < P.n_nodes ? P.node[m + 1].pro : P.head; }
 
 void plan_fusion(Program& P, int nt, int nx) {
@@ -678,7 +710,7 @@ PINN_LM_FDECL5(0, 0) PINN_LM_FDECL5(1, 0) PINN_LM_FDECL5(1, 1) PINN_LM_FDECL5(1,
 namespace {
 
 hipError_t launch_fused(int nt, int nx, int act, const FusedArgs& a, bool bwd, bool ln, const Program::Fuse& f, int gx, hipStream_t st) {
-  const int fam = (act == PINN_ACT_TANH || act == PINN_ACT_SIN || act == PINN_ACT_GELU || act == PINN_ACT_SIGMOID) ? act : PINN_ACT_RELU;
+  const int fam = act_family_of(act);
 #define PINN_LM_FCASE(NT_, NX_, A_) \
   if (nt == NT_ && nx == NX_ && fam == A_) return launch_lm_fused_##NT_##_##NX_##_##A_(a, bwd, ln, f.nch, f.rt, gx, f.gy, st);
 #define PINN_LM_FCASE5(NT_, NX_) PINN_LM_FCASE(NT_, NX_, 0) PINN_LM_FCASE(NT_, NX_, 1) PINN_LM_FCASE(NT_, NX_, 2) PINN_LM_FCASE(NT_, NX_, 3) PINN_LM_FCASE(NT_, NX_, 4)
@@ -1000,6 +1032,64 @@ size_t lm_workspace_bytes(const PinnNetDesc* d, long long N, int nt, int nx, boo
   return (L.total * sizeof(float) + 255) & ~(size_t)255;
 }
 
+static_assert(PINN_LM_MAX_PLAN == kMaxNodes + 1, "pinn_jet.h: one plan record per GEMM node and one for the head");
+
+int lm_plan(const PinnNetDesc* d, int nt, int nx, int backward, PinnLmNodePlan* out, int max_records, char* err, size_t en) {
+  Program P;
+  const int rc = build_program(d, P, err, en);
+  if (rc) return rc;
+  if (!out || max_records < P.n_nodes + 1) return failf(err, en, PINN_ERR_BAD_DESC, "plan of %d nodes needs %d records, got %d", P.n_nodes, P.n_nodes + 1, out ? max_records : 0);
+  const int K = 1 + nt + nx;
+  plan_fusion(P, nt, nx);
+  ExtraSrc exs[kMaxNodes][2];
+  plan_extras(P, exs);
+  const bool bwd = backward != 0, want_xg = backward == 2;
+  for (int m = 0; m <= P.n_nodes; ++m) {
+    const bool head = m == P.n_nodes;
+    const Prologue& pro = head ? P.head : P.node[m].pro;
+    const bool fourier = pro.src_kind == SRC_COORDS_FOURIER;
+    const int Hp = round32(pro.H), fpt = fpt_for(Hp);
+    PinnLmNodePlan r;
+    memset(&r, 0, sizeof(r));
+    r.rows = head ? 1 : round32(P.node[m].Hout);
+    r.depth = r.width = Hp;
+    r.has_ln = pro.ln_g >= 0;
+    r.has_skip = pro.skip_node >= 0;
+    r.has_add = !head && P.node[m].add_node >= 0;
+    r.act_family = (pro.identity() || fourier) ? -1 : act_family_of(pro.act);
+    r.src_kind = pro.src_kind;
+    r.fwd_nch = r.fwd_rt = r.fwd_gy = r.fwd_aux = r.fwd_ew_kind = r.fwd_fpt = -1;
+    r.bwd_nch = r.bwd_rt = r.bwd_gy = r.bwd_aux = r.bwd_ew_kind = r.bwd_fpt = -1;
+    r.head_fpt = head ? fpt : -1;
+    if (m > 0 && P.fuse_fwd[m - 1].on) {  // lm_run: v_ready[m]
+      const Program::Fuse& f = P.fuse_fwd[m - 1];
+      r.fwd_fused = 1;
+      r.fwd_nch = f.nch;
+      r.fwd_rt = f.rt;
+      r.fwd_gy = f.gy;
+      r.fwd_aux = lm_fused_aux(false, P.node[m - 1].add_node >= 0, pro.skip_node >= 0);
+    } else if (!pro.identity()) {
+      r.fwd_ew_kind = fourier ? 2 : 0;
+      r.fwd_fpt = fpt;
+    }
+    if (bwd && !pro.identity() && adjoint_runs(pro, want_xg, true)) {
+      if (!head && P.fuse_bwd[m].on) {
+        const Program::Fuse& f = P.fuse_bwd[m];
+        r.bwd_fused = 1;
+        r.bwd_nch = f.nch;
+        r.bwd_rt = f.rt;
+        r.bwd_gy = f.gy;
+        r.bwd_aux = lm_fused_aux(true, exs[m][0].kind != 0, pro.skip_node >= 0);
+      } else {
+        r.bwd_ew_kind = fourier ? 2 : (lm_ew_bwd_dma_shape(pro.ln_g >= 0, pro.src_kind, !head, fpt, K, Hp) ? 1 : 0);
+        r.bwd_fpt = fpt;
+      }
+    }
+    out[m] = r;
+  }
+  return P.n_nodes;
+}
+
 int lm_run(const CallArgs& c, char* err, size_t en) {
   Program P;
   int rc = build_program(c.net, P, err, en);
@@ -1259,12 +1349,12 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     if (!c.bwd) continue;
     // ---------------- reverse ----------------
     // extra cotangents of V records: skip connections (Pbar of the consumer's prologue) and epilogue adds (Zbar of the adding node)
+    ExtraSrc exs[kMaxNodes][2];
+    plan_extras(P, exs);
     const float* extra[kMaxNodes][2];
-    for (int m = 0; m < P.n_nodes; ++m) extra[m][0] = extra[m][1] = nullptr;
-    auto add_extra = [&](int m, const float* rec) {
-      if (!extra[m][0]) extra[m][0] = rec;
-      else extra[m][1] = rec;
-    };
+    for (int m = 0; m < P.n_nodes; ++m)
+      for (int j = 0; j < 2; ++j)
+        extra[m][j] = exs[m][j].kind == 1 ? ws + L.Pbar[exs[m][j].idx] : (exs[m][j].kind == 2 ? ws + L.Zbar[exs[m][j].idx] : nullptr);
     auto run_ew_bwd = [&](const Prologue& pro, int self, const float* vbar) -> int {
       // self = node index (kMaxNodes for the head); vbar = cotangent record of its V, or null for the head's (U, w_out) form
       const bool xg = want_xg && pro.src_kind != SRC_REC;  // coordinate-fed prologue of a call that wants input cotangents
@@ -1278,10 +1368,7 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
         a.w_out = pp(P.w_out);
       }
       if (pro.src_kind == SRC_REC) a.Zbar = ws + L.Zbar[pro.src_node];
-      if (pro.skip_node >= 0) {
-        a.Pbar = ws + L.Pbar[self];
-        add_extra(pro.skip_node, a.Pbar);
-      }
+      if (pro.skip_node >= 0) a.Pbar = ws + L.Pbar[self];
       a.d_ln_g = gp(pro.ln_g);
       a.d_ln_b = gp(pro.ln_b);
       if (xg) {
@@ -1371,7 +1458,6 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
     for (int m = P.n_nodes - 1; m >= 0; --m) {
       const Node& nd = P.node[m];
       const float* zbar = ws + L.Zbar[m];
-      if (nd.add_node >= 0) add_extra(nd.add_node, zbar);
       // weight gradient
       if (gp(nd.w) || gp(nd.b)) {
         GemmNtArgs g;
@@ -1442,10 +1528,7 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
       // cotangent of this node's GEMM input, then through its prologue
       const Prologue& pro = nd.pro;
       // (Fourier node 0: its input cotangent W_1^T Zbar_1 is formed only when the call wants input cotangents)
-      const bool xg_here = want_xg && pro.src_kind != SRC_REC;
-      const bool upstream = pro.src_kind == SRC_REC || pro.src_kind == SRC_COORDS_LINEAR || pro.ln_g >= 0 || pro.skip_node >= 0 || xg_here;
-      if (!upstream) continue;
-      if (pro.src_kind == SRC_COORDS_LINEAR && !gp(pro.enc_w) && !gp(pro.enc_b) && pro.ln_g < 0 && pro.skip_node < 0 && !xg_here) continue;
+      if (!adjoint_runs(pro, want_xg, gp(pro.enc_w) || gp(pro.enc_b))) continue;
       if (P.fuse_bwd[m].on) {  // Vbar = W^T Zbar (+ extras) and the prologue's adjoint in one launch
         FusedArgs f;
         memset(&f, 0, sizeof(f));
@@ -1465,10 +1548,7 @@ int lm_run(const CallArgs& c, char* err, size_t en) {
         f.stats = L.Stats[m] ? ws + L.Stats[m] : nullptr;
         f.Zsrc = ws + L.Y[pro.src_node];
         f.Zbar = ws + L.Zbar[pro.src_node];
-        if (pro.skip_node >= 0) {
-          f.Pbar = ws + L.Pbar[m];
-          add_extra(pro.skip_node, f.Pbar);
-        }
+        if (pro.skip_node >= 0) f.Pbar = ws + L.Pbar[m];
         f.d_ln_g = gp(pro.ln_g);
         f.d_ln_b = gp(pro.ln_b);
         if (c.deterministic && pro.ln_g >= 0) f.det_partial = ws + L.det;

@@ -20,6 +20,8 @@
 // per-feature sums over points (dgamma, dbeta, encoder gradient) are quarter-wave reductions accumulated in LDS
 // across all units of the workgroup and flushed once.
 #pragma once
+#include <cstdlib>
+
 #include "lm_common.h"
 
 namespace pinn {
@@ -969,8 +971,21 @@ __global__ __launch_bounds__(1024) void lm_ew_bwd_dma(const EwArgs a) {
 }
 
 inline size_t lm_ew_bwd_dma_lds_bytes(int K, int Hp) { return sizeof(float) * ((size_t)2 * K * Hp * kPT + 16 * kPT + 2 * 1024 + 2 * kMaxWavesEw * kRedQ * kPT); }
-inline bool lm_ew_bwd_dma_ok(const EwArgs& a, int K) {
-  return a.ln_g && a.src_kind == SRC_REC && a.Vbar && a.Zbar && a.stats && K * a.Hp <= 1024 && (a.Hp % 16) == 0;
+inline bool lm_ew_dma_on() {  // PINN_LM_EWDMA=0: the register-staged LayerNorm adjoint everywhere (experiments), read once
+  static const bool v = [] {
+    const char* e = getenv("PINN_LM_EWDMA");
+    return !(e && atoi(e) == 0);
+  }();
+  return v;
+}
+// Which LayerNorm adjoints take lm_ew_bwd_dma: a decision of the prologue (LayerNorm, fed by a record, with a cotangent
+// record of its own — the head's (U, w_out) form has none), K and Hp.  The launch (lm_inst.hip) and the plan query
+// (lm_engine.hip::lm_plan) both call it; the kernel is instantiated for FPT 4 only.
+inline bool lm_ew_bwd_dma_shape(bool ln, int src_kind, bool has_vbar, int fpt, int K, int Hp) {
+  return lm_ew_dma_on() && ln && fpt == 4 && src_kind == SRC_REC && has_vbar && K * Hp <= 1024 && (Hp % 16) == 0;
+}
+inline bool lm_ew_bwd_dma_ok(const EwArgs& a, int fpt, int K) {  // + the records that prologue always comes with
+  return lm_ew_bwd_dma_shape(a.ln_g != nullptr, a.src_kind, a.Vbar != nullptr, fpt, K, a.Hp) && a.Zbar && a.stats;
 }
 
 }  // namespace lm

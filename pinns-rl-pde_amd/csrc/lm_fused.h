@@ -706,5 +706,9 @@ inline size_t lm_fused_lds_bytes(int nch, int rt, int K, bool bwd, bool aux) {
                           (land ? (size_t)8 * K * 512 : 0));
 }
 
+// The AUX instantiation: forward — a skip or an add record (never both: lm_engine.hip::plan_fusion); reverse — an extra
+// cotangent record.  The launch (lm_fused_inst.hip) and the plan query (lm_engine.hip::lm_plan) both call it.
+inline bool lm_fused_aux(bool bwd, bool has_add0, bool has_skip) { return bwd ? has_add0 : (has_add0 || has_skip); }
+
 }  // namespace lm
 }  // namespace pinn

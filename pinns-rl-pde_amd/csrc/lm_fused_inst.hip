@@ -21,10 +21,9 @@ static hipError_t launch_aux(const FusedArgs& a, int gx, int gy, hipStream_t st)
   return hipGetLastError();
 }
 
-// AUX: forward — a skip or an add record (never both: lm_engine.hip::plan_fusion); reverse — an add record
 template <int NCH, int RT, bool LN, bool BWD>
 static hipError_t launch_one(const FusedArgs& a, int gx, int gy, hipStream_t st) {
-  const bool aux = BWD ? a.add0 != nullptr : (a.add0 != nullptr || a.skip != nullptr);
+  const bool aux = lm_fused_aux(BWD, a.add0 != nullptr, a.skip != nullptr);
   return aux ? launch_aux<NCH, RT, LN, BWD, true>(a, gx, gy, st) : launch_aux<NCH, RT, LN, BWD, false>(a, gx, gy, st);
 }
 

@@ -13,20 +13,12 @@ namespace lm {
 #define PINN_CAT2(a, b, c, d) a##b##c##_##d
 #define PINN_NAME(a, b, c) PINN_CAT2(launch_lm_, a, b, c)
 
-static bool ew_dma_on() {  // PINN_LM_EWDMA=0: the register-staged LayerNorm adjoint everywhere (experiments), read once
-  static const bool v = [] {
-    const char* e = getenv("PINN_LM_EWDMA");
-    return !(e && atoi(e) == 0);
-  }();
-  return v;
-}
-
 template <int ACT, int FPT, bool LN>
 static hipError_t launch_ew(const EwArgs& a, bool bwd, int grid, hipStream_t st) {
   const int threads = kPT * a.G;
   if constexpr (LN && FPT == 4) {
     constexpr int K = 1 + PINN_NT + PINN_NX;
-    if (bwd && ew_dma_on() && lm_ew_bwd_dma_ok(a, K)) {  // next unit prefetched by LDS-DMA (lm_ew.h)
+    if (bwd && lm_ew_bwd_dma_ok(a, FPT, K)) {  // next unit prefetched by LDS-DMA (lm_ew.h)
       auto kern = lm_ew_bwd_dma<ACT, PINN_NT, PINN_NX, FPT>;
       const hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
       if (e != hipSuccess) return e;

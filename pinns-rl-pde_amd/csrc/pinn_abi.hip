@@ -806,6 +806,17 @@ int pinn_kernel_for(const PinnNetDesc* net, int64_t N, int32_t time_order, int32
   return PINN_OK;
 }
 
+int pinn_lm_plan(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
+                 PinnLmNodePlan* out, int32_t max_records) {
+  PinnKernelInfo r;  // the checks of pinn_kernel_for: descriptor, orders, compiled stream set
+  int rc = pinn_kernel_for(net, N, time_order, space_order, backward, &r);
+  if (rc) return rc;
+  char lerr[256] = "";
+  rc = lm::lm_plan(net, time_order, space_order, backward, out, max_records, lerr, sizeof(lerr));
+  if (rc < 0) return fail(rc, "%s", lerr);
+  return rc;
+}
+
 int pinn_kernel_name(const PinnNetDesc* net, int64_t N, int32_t time_order, int32_t space_order, int32_t backward,
                      char* buf, size_t len) {
   if (!buf || len == 0) return fail(PINN_ERR_BAD_DESC, "null or empty name buffer");

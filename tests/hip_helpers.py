@@ -49,3 +49,38 @@ def pde_desc_from_spec(pde):
         "pendulum": [p.get("g", 9.81) / p.get("L", 1.0)],
     }[name]
     return E.pde_desc(name, pde.dimension, coef, pde.loss_function, pde.huber_delta)
+
+
+# Per-tensor gradient bar (relative L2 of one state_dict tensor), so that a bias, a LayerNorm parameter or the output layer
+# cannot hide behind the weight matrices in the concatenated vector.  A tensor above it is compared with the same oracle
+# evaluated in fp32 on the CPU (`floor()`: {name: gradient}): if that floor against fp64 is itself above FLOOR_MIN the
+# tensor may take FLOOR_MARGIN x the floor (the kernels sum in another order), otherwise the excess is a finding.
+TENSOR_TOL = 1e-4
+FLOOR_MIN = 2.5e-5
+FLOOR_MARGIN = 4.0
+
+
+def check_tensors(got, want, what, floor=None, seen=None):
+    """got / want: {name: gradient} (GPU fp32 / fp64 oracle), compared tensor by tensor over the names of `want`; a tensor
+    the oracle's gradient vanishes on identically must be exactly 0.  seen(name, error) is called per compared tensor.
+    Returns the tensors that took a widened bar: [{"where", "tensor", "value", "fp32_floor"}]."""
+    from conftest import rel_l2
+
+    widened = []
+    for k, w in want.items():
+        assert k in got, f"{what}: no gradient for {k}"
+        g = got[k].detach().cpu()
+        if float(w.norm()) == 0.0:
+            assert float(g.abs().max()) == 0.0, f"{what}: {k} must be exactly 0"
+            continue
+        e = rel_l2(g, w, label=f"{what} tensor {k}", tol=TENSOR_TOL)
+        if seen is not None:
+            seen(k, e)
+        if e <= TENSOR_TOL:
+            continue
+        assert floor is not None, f"{what}: tensor {k}: {e:.2e}"
+        fl = float((floor()[k].detach().double().cpu() - w).norm() / w.norm())
+        print(f"{what}: tensor {k}: {e:.2e} above {TENSOR_TOL:.0e}; the fp32 oracle is at {fl:.2e}")
+        assert fl > FLOOR_MIN and e <= FLOOR_MARGIN * fl, f"{what}: tensor {k}: {e:.2e} (fp32 oracle {fl:.2e})"
+        widened.append({"where": what, "tensor": k, "value": e, "fp32_floor": fl})
+    return widened

@@ -3,7 +3,12 @@ and the fused GEMM + prologue kernels (lm_fused.h); which nodes take which is a 
 (PINN_LM_FUSED, PINN_LM_FUSED_LN, lm_engine.hip::plan_fusion).  The default policy runs in every other GPU test; here
 the full-depth / full-width parity tests run again in child processes with everything unfused and with every
 LayerNorm node fused (kernels the default policy leaves to the unfused path must stay correct: they are selectable),
-and with the two GEMM-side choices of lm_engine.hip switched back (PINN_LM_WRES16, PINN_LM_NT_BATCH)."""
+and with the two GEMM-side choices of lm_engine.hip switched back (PINN_LM_WRES16, PINN_LM_NT_BATCH).  The variant matrix
+(test_lm_variants_gpu.py) runs again with everything unfused — the whole element-wise matrix — and with every LayerNorm
+node fused — the LayerNorm reverse epilogues at depth 256, which the default policy never launches.
+
+A child that dies on a signal or runs into its time limit fails its test, and no later test of this file starts another
+child: what faulted the GPU once is not given a second process to fault."""
 import os
 import subprocess
 import sys
@@ -11,6 +16,20 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_STOPPED = []  # why no further child starts
+
+
+def _run_child(cmd, env, timeout):
+    if _STOPPED:
+        pytest.fail(f"not started: {_STOPPED[0]}")
+    try:
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired as e:
+        _STOPPED.append(f"an earlier child ran into its time limit of {timeout} s: {' '.join(cmd[:4])}")
+        pytest.fail(_STOPPED[0] + "\n" + str(e.stdout or "")[-2000:])
+    if r.returncode < 0 or r.returncode in (134, 139):
+        _STOPPED.append(f"an earlier child died on a signal (exit {r.returncode}): {' '.join(cmd[:4])}")
+    return r
 
 
 @pytest.mark.gpu
@@ -20,8 +39,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                               "depth-512-gemm-streamed-and-one-dw-launch-per-layer"])
 def test_width256_parity_under_policy(env):
     e = dict(os.environ, **env)
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_width256_parity.py", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"],
-                       cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
+    r = _run_child([sys.executable, "-m", "pytest", "tests/test_width256_parity.py", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"], e, 900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env", [{"PINN_LM_FUSED": "0"}, {"PINN_LM_FUSED_LN": "15"}], ids=["unfused", "all-layernorm-nodes-fused"])
+def test_lm_variant_matrix_under_policy(env):
+    """tests/test_lm_variants_gpu.py in a child process under the policy: its last test asserts that the variants that ran
+    are the reachable matrix of that policy (tests/lm_variants_model.py::reachable)."""
+    e = dict(os.environ, **env)
+    r = _run_child([sys.executable, "-m", "pytest", "tests/test_lm_variants_gpu.py", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"], e, 600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
 
 
@@ -77,5 +105,5 @@ def test_multi_chunk_loop_of_the_layer_major_engine():
     tile; LayerNorm (ResNet), attention (merged W_p W_v gradient) and SIREN nets, default and deterministic mode, against
     per-chunk launches and the fp64 oracle."""
     e = dict(os.environ, PINN_LM_RECORD_MB="1")
-    r = subprocess.run([sys.executable, "-c", _CHUNK_SCRIPT], cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
+    r = _run_child([sys.executable, "-c", _CHUNK_SCRIPT], e, 900)
     assert r.returncode == 0 and "multi-chunk ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]

@@ -57,6 +57,18 @@ def _oracle64(spec, pde, sd, x, t, layer_norm="composite"):
     return O.residual_loss_and_grad(pde, spec, sd64, x.double(), t.double(), layer_norm=layer_norm)
 
 
+def _per_tensor(g, g_o, what, spec, pde, sd, x, t):
+    """Tensor by tensor at hip_helpers.TENSOR_TOL (the concatenated comparison lets a bias or a LayerNorm parameter hide
+    behind the weight matrices); the fp32 floor of a tensor above it is the same oracle in fp32."""
+    import oracle as O
+    from hip_helpers import check_tensors
+
+    def floor():
+        return O.residual_loss_and_grad(pde, spec, {k: v.float() for k, v in sd.items()}, x.float(), t.float(), layer_norm="composite")[2]
+
+    check_tensors(g, {k: v for k, v in g_o.items() if k in g}, what, floor)
+
+
 @pytest.mark.parametrize("arch,pde_name,kw", [
     ("fourier", "burgers", dict(num_layers=3, mapping_size=32, scale=3.0)),             # K = 4, Fourier encoding
     ("siren", "kdv", dict(num_layers=3, omega_0=6.0)),                                    # K = 5, first Linear + sin
@@ -73,6 +85,7 @@ def test_stream_serial_two_tile_kernel(arch, pde_name, kw, dev):
     want = torch.cat([g_o[k].flatten() for k in keys])
     e_g = rel_l2(got, want, label="gradient", tol=TOL)
     assert e_g <= TOL, f"{e_g:.3e}"
+    _per_tensor(g, g_o, f"{arch} 3x256 {pde_name}", spec, pde, sd, x, t)
 
 
 def test_resnet_width_256(dev):
@@ -88,6 +101,7 @@ def test_resnet_width_256(dev):
     assert rel_l2(got, exact) <= TOL, f"{rel_l2(got, exact):.3e}"
     _, _, g_f = _oracle64(spec, pde, sd, x, t, layer_norm="fused")
     assert rel_l2(got, torch.cat([g_f[k].flatten() for k in keys])) <= 5e-4  # witness of the library error
+    _per_tensor(g, g_o, "resnet 2x256 allen_cahn", spec, pde, sd, x, t)
 
 
 def test_attention_width_256(dev):
@@ -99,6 +113,7 @@ def test_attention_width_256(dev):
     got = torch.cat([g[k].flatten().cpu() for k in keys])
     want = torch.cat([g_o[k].flatten() for k in keys])
     assert rel_l2(got, want) <= TOL, f"{rel_l2(got, want):.3e}"
+    _per_tensor(g, g_o, "attention 2x256 cahn_hilliard 2-D", spec, pde, sd, x, t)
 
 
 @pytest.mark.parametrize("arch,kw", [
@@ -181,6 +196,7 @@ def test_baseline_networks_full_depth_gradient(name, arch, pde_name, dim, kw, de
     for k in keys:  # and tensor by tensor, so that one small tensor cannot hide behind a large one
         if float(g_o[k].norm()) > 1e-12:
             assert rel_l2(g[k].cpu(), g_o[k]) <= 10 * tol, f"{name}: {k} {rel_l2(g[k].cpu(), g_o[k]):.3e}"
+    _per_tensor(g, g_o, name, spec, pde, sd, x, t)
 
 
 @pytest.mark.parametrize("arch,pde_name,kw", [
