@@ -262,7 +262,17 @@ int pinn_unit_tail_plan(int64_t N, int32_t grid, int64_t* rounds, int32_t* group
  * Weight tensors: contiguous fp32, hidden-layer weight matrices 16-byte aligned where the descriptor takes the fused
  * tile-major kernel (plain MLP family, widths multiples of 32 up to 128: it reads them in place with 16-byte loads) —
  * a misaligned view there is refused with PINN_ERR_MISALIGNED rather than silently re-routed to the engine
- * pinn_workspace_bytes did not size for; PINN_FLAG_LAYER_MAJOR selects the packing engine, which takes any alignment. */
+ * pinn_workspace_bytes did not size for; PINN_FLAG_LAYER_MAJOR selects the packing engine, which takes any alignment.
+ *
+ * Components of a multi-output network.  A descriptor always ends in width 1 (another last width is PINN_ERR_UNSUPPORTED):
+ * one launch computes one output.  Output k of a network whose last Linear has C rows (W_out: C x H, b_out: C) is exactly
+ * the one-output network whose output layer is row k of W_out and entry k of b_out, so a component launch is the width-1
+ * descriptor with the two output-layer entries of `weights` pointing at W_out + k H and b_out + k, and — in a reverse
+ * launch — the same two entries of `weight_grads` pointing at row k of the gradients (H floats and 1 float are accumulated;
+ * the other rows are not touched).  Every other entry is the network's own; the trunk is recomputed per component.  Row k
+ * of a width such as 30 is only 4-byte aligned: PINN_FLAG_LAYER_MAJOR is required whenever row k is not 16-byte aligned
+ * (the layer-major engine reads the output layer through its packing pass, at any alignment).  Composes with
+ * PINN_FLAG_SPACE_AXIS and PINN_FLAG_SPACE_DIRECTION. */
 
 /* jets_out[s] : N floats each, stream order [u, d/dt.., d/dx..]; all K = 1+nt+nx entries required. */
 int pinn_jet_forward(const PinnNetDesc* net, const float* const* weights, int32_t num_tensors, const float* x,
@@ -595,6 +605,73 @@ typedef struct PinnTermPdeMixed {
 int pinn_term_residual_mixed(const PinnTermPdeMixed* pde, const float* coef_values, const float* const* jets, const float* x,
                              const float* t, int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out,
                              float* loss_sum_out, float* const* jet_cotangents, float* coef_grads, double* scratch, void* stream);
+
+/* ---- term residuals of coupled systems (several unknowns, several equations) ----------------------------------------------
+ * E residuals in C fields, the fields being the components of one C-output network (component launches, above):
+ *   r_e = sum_{m: equation_of[m] = e} c_m prod_{f < n_factors[m]} phi_{m,f},   e < n_equations,
+ * with one term list of at most PINN_SYSTEM_MAX_TERMS terms shared by all equations.  A factor is ONE BYTE,
+ * PINN_SYSTEM_FACTOR(field, code) = field * 32 + code: `code` is a PinnTermFactor 0 .. 10 or PINN_TERM_UY .. PINN_TERM_Z
+ * (11 .. 16) with its meaning for that field; coordinates ignore the field bits; no mixed derivatives.  Dimension 1 to 3.
+ * Per field c, (time_order[c], space_order[c][0]) is a compiled axis-0 set and the axes 1 and 2 take the orders 0 .. 2
+ * (0 beyond `dimension`).  The chain is one pinn_jet_forward per (field, axis with streams) -> pinn_term_residual_system ->
+ * one pinn_jet_backward per block, all accumulating into the same weight gradients.
+ *   jets, jet_cotangents   HOST tables of 3 C device pointers, entry 3 c + a: block (c, 0) the
+ *                      (1 + time_order[c] + space_order[c][0]) x N block of field c's axis-0 launch (always required), block
+ *                      (c, a >= 1) the (1 + space_order[c][a]) x N block of its axis-a launch (row 0 is not read), NULL when
+ *                      that order is 0.  jet_cotangents is nullable; its blocks are overwritten.  The whole cotangent of field
+ *                      c's value, sin and cos goes to row 0 of block (c, 0); row 0 of every other block of the field and every
+ *                      row the program never reads are written as zeros (a field no term names gets all-zero blocks), so each
+ *                      block goes straight into pinn_jet_backward;
+ *   x, t               N x dimension row-major, N floats; read only under a coordinate factor;
+ *   coef_values        n_terms device floats c_m, read at launch time;
+ *   residual_out       E x N (equation e at residual_out + e N), nullable;
+ *   rbar_e,n           (grad_scale * eq_weight[e]) * l'(r_e,n), the product in parentheses rounded to fp32 once on the host,
+ *                      or residual_cotangent[e N + n] when that array (E x N, nullable) is given; l, l' as pinn_term_residual
+ *                      (sgn(0) = 0, Huber's quadratic branch on |r| < delta);
+ *   loss_sum_out       nullable: loss_sum_out[0] += sum_e eq_weight[e] sum_n l(r_e,n);
+ *   eq_loss_sums       nullable, E floats: eq_loss_sums[e] += sum_n l(r_e,n), unweighted;
+ *   coef_grads         nullable: coef_grads[m] += sum_n rbar_{equation_of[m],n} prod_f phi_{m,f};
+ *   scratch            PINN_SYSTEM_SCRATCH_DOUBLES doubles, 8-byte aligned; may be NULL when no sum is wanted.
+ * Rounding order, per point, in fp32.  Sweep 1: the terms in ascending m, each product formed as ((c_m phi_0) phi_1) ... and
+ * added to r_{equation_of[m]} (the order of pinn_term_residual_axes).  Then l, l' and rbar_e of every equation.  Sweep 2: the
+ * terms in ascending m again; the derivative of term m with respect to factor f is (((c_m phi_g) ...) over g != f in ascending
+ * g, times cos(u) under sin(u), or negated after the product with sin(u) under cos(u); the summands of ONE term that belong
+ * to the same (field, stream) — at most four — are summed first in ascending f, that sum is multiplied by
+ * rbar_{equation_of[m]}, and the product is added to the (field, stream) accumulator, which is what the cotangent row
+ * receives.  The sums over the points are per-block partials in double (one point per thread per grid-stride round,
+ * 256-thread blocks on a fixed grid of at most 64) that a second launch adds in block order; the weighted loss is formed
+ * from the per-equation sums in double, in ascending e.  No atomics, bit-identical across runs; a call that produces no loss
+ * or coefficient sum is ONE launch.
+ * Checked on the host before any HIP call: dimension, n_fields, n_equations, n_terms or n_factors out of range, an
+ * uncompiled axis-0 set, space_order[c][a] outside [0, 2] for a >= 1 (or non-zero for a >= dimension), equation_of[m] outside
+ * [0, E), a negative or non-finite eq_weight, a factor that is not one byte, an unknown code, a field index >= C, a factor
+ * naming a stream or coordinate the descriptor does not hold, N < 0, a null jets table / coef_values / required block of either
+ * table (or x / t under a coordinate factor, or scratch where it is needed) with N > 0: PINN_ERR_BAD_DESC; misaligned
+ * scratch: PINN_ERR_MISALIGNED.  N == 0: no-op. */
+#define PINN_SYSTEM_MAX_FIELDS 4
+#define PINN_SYSTEM_MAX_EQUATIONS 4
+#define PINN_SYSTEM_MAX_TERMS 32
+#define PINN_SYSTEM_SCRATCH_DOUBLES (64 * (4 + 32))
+#define PINN_SYSTEM_FACTOR(field, code) ((field) * 32 + (code))
+
+typedef struct PinnTermPdeSystem {
+  int32_t dimension;                                   /* 1 .. 3 */
+  int32_t n_fields;                                    /* C: 1 .. PINN_SYSTEM_MAX_FIELDS */
+  int32_t n_equations;                                 /* E: 1 .. PINN_SYSTEM_MAX_EQUATIONS */
+  int32_t time_order[PINN_SYSTEM_MAX_FIELDS];          /* per field; with space_order[c][0] the stream set of block (c, 0) */
+  int32_t space_order[PINN_SYSTEM_MAX_FIELDS][3];      /* per field and axis; [c][1], [c][2]: 0 .. 2, 0 beyond `dimension` */
+  int32_t n_terms;                                     /* 0 .. PINN_SYSTEM_MAX_TERMS, shared by all equations */
+  int32_t equation_of[PINN_SYSTEM_MAX_TERMS];          /* the equation of term m */
+  float eq_weight[PINN_SYSTEM_MAX_EQUATIONS];          /* omega_e >= 0, finite */
+  int32_t loss;                                        /* PinnLoss */
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_SYSTEM_MAX_TERMS];        /* factor[f] = PINN_SYSTEM_FACTOR(field, code) */
+} PinnTermPdeSystem;
+
+int pinn_term_residual_system(const PinnTermPdeSystem* pde, const float* coef_values, const float* const* jets, const float* x,
+                              const float* t, int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out,
+                              float* loss_sum_out, float* eq_loss_sums, float* const* jet_cotangents, float* coef_grads,
+                              double* scratch, void* stream);
 
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.

@@ -66,6 +66,18 @@ TERM_FACTOR_ND = dict(TERM_FACTOR, **{"u_y": 11, "u_yy": 12, "u_z": 13, "u_zz": 
 TERM_FACTOR_MIXED = dict(TERM_FACTOR_ND, **{"u_yyy": 17, "u_yyyy": 18, "u_zzz": 19, "u_zzzz": 20, "u_xy": 21, "u_xz": 22, "u_yz": 23,
                                             "u_xxyy": 24, "u_xxzz": 25, "u_yyzz": 26})
 PINN_TERM_MIXED_BLOCKS = 9  # [axis0, axis1, axis2, P_xy, P_xz, P_yz, Q_xy, Q_xz, Q_yz]
+# pinn_term_residual_system: C fields (components of one network), E equations, one shared term list
+PINN_SYSTEM_MAX_FIELDS = 4
+PINN_SYSTEM_MAX_EQUATIONS = 4
+PINN_SYSTEM_MAX_TERMS = 32
+PINN_SYSTEM_SCRATCH_DOUBLES = 64 * (4 + 32)
+
+
+def PINN_SYSTEM_FACTOR(field: int, code: int) -> int:
+    """One byte per factor of a system term: field * 32 + code (a `TERM_FACTOR_ND` code; coordinates ignore the field)."""
+    return int(field) * 32 + int(code)
+
+
 # the record of pinn_lbfgs_direction / pinn_lbfgs_eval_stats (doubles); from "dmax" on: 64 per-block partials of max|d|
 LBFGS_REC = {"loss": 0, "gtd": 1, "gmax": 2, "gsum": 3, "accepted": 4, "count": 5, "n_iter": 6, "h_diag": 7, "dmax": 8}
 
@@ -77,7 +89,7 @@ EXPORTS = (
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
-    "pinn_term_residual_mixed", "pinn_lm_plan",
+    "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system",
 )
 
 
@@ -121,6 +133,16 @@ class PinnTermPdeMixed(ctypes.Structure):
         ("dimension", ctypes.c_int32), ("time_order", ctypes.c_int32), ("space_order", ctypes.c_int32 * 3),
         ("pair_order", ctypes.c_int32 * 3), ("n_terms", ctypes.c_int32), ("loss", ctypes.c_int32),
         ("huber_delta", ctypes.c_float), ("terms", PinnTermPdeTerm * PINN_TERM_MAX_TERMS),
+    ]
+
+
+class PinnTermPdeSystem(ctypes.Structure):
+    _fields_ = [
+        ("dimension", ctypes.c_int32), ("n_fields", ctypes.c_int32), ("n_equations", ctypes.c_int32),
+        ("time_order", ctypes.c_int32 * PINN_SYSTEM_MAX_FIELDS), ("space_order", (ctypes.c_int32 * 3) * PINN_SYSTEM_MAX_FIELDS),
+        ("n_terms", ctypes.c_int32), ("equation_of", ctypes.c_int32 * PINN_SYSTEM_MAX_TERMS),
+        ("eq_weight", ctypes.c_float * PINN_SYSTEM_MAX_EQUATIONS), ("loss", ctypes.c_int32), ("huber_delta", ctypes.c_float),
+        ("terms", PinnTermPdeTerm * PINN_SYSTEM_MAX_TERMS),
     ]
 
 
@@ -258,6 +280,8 @@ def load():
         lib.pinn_term_residual_axes.argtypes = [P(PinnTermPdeAxes), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, P(vp), vp, vp, vp]
         lib.pinn_term_residual_mixed.restype = ctypes.c_int
         lib.pinn_term_residual_mixed.argtypes = [P(PinnTermPdeMixed), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, P(vp), vp, vp, vp]
+        lib.pinn_term_residual_system.restype = ctypes.c_int
+        lib.pinn_term_residual_system.argtypes = [P(PinnTermPdeSystem), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, vp, P(vp), vp, vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:

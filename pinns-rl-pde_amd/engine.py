@@ -49,7 +49,15 @@ class NetProgram:
 
     tensors: parameters AND buffers in the reference's `state_dict` order (fourier: B first).
     trainable[i] is False for buffers (no gradient slot).
+
+    A network whose last Linear has C rows (1 <= C <= `MAX_OUTPUTS`) keeps `n_outputs = C`; its descriptor still says
+    widths[num_linear - 1] = 1, because every launch computes ONE component: output k is exactly the one-output network whose
+    output layer is row k of the output weight and entry k of the output bias, so a component launch is the same launch with
+    the two output-layer entries of the weight table (and of the gradient table) advanced to row k (`component=` of the
+    jets_* functions).  In every architecture the output Linear is the last two tensors of the state_dict.
     """
+
+    MAX_OUTPUTS = 4
 
     def __init__(self, arch: str, activation: str, input_dim: int, widths: Sequence[int], tensors: Sequence[Tensor],
                  trainable: Sequence[bool], mapping_size: int = 0, omega_0: float = 0.0, ln_eps: float = 1e-5,
@@ -60,6 +68,13 @@ class NetProgram:
             raise ValueError(f"Unsupported activation: {activation}")  # base_network.py:104
         if len(widths) > _lib.PINN_MAX_LINEAR:
             raise NotImplementedError(f"pinnrl_amd: more than {_lib.PINN_MAX_LINEAR} Linear layers")
+        # the number of outputs is read off the output weight (the last Linear of the state_dict: C x H); a program built
+        # without tensors (descriptor queries only) keeps its widths as given
+        n_out = 1
+        if len(tensors) >= 2 and tensors[-2].dim() == 2 and len(widths) and int(widths[-1]) == tensors[-2].shape[0]:
+            n_out = int(widths[-1])
+        if not 1 <= n_out <= self.MAX_OUTPUTS:
+            raise NotImplementedError(f"pinnrl_amd: output_dim={n_out}: a network has 1 to {self.MAX_OUTPUTS} outputs")
         d = _lib.PinnNetDesc()
         d.arch = _lib.ARCH[arch]
         d.activation = _lib.ACT[activation]
@@ -67,6 +82,9 @@ class NetProgram:
         d.num_linear = len(widths)
         for i, w in enumerate(widths):
             d.widths[i] = int(w)
+        if n_out > 1:
+            d.widths[len(widths) - 1] = 1  # one component per launch
+        self.n_outputs = n_out
         d.mapping_size = int(mapping_size)
         d.act_param = float(omega_0)
         d.ln_eps = float(ln_eps)
@@ -97,11 +115,23 @@ class NetProgram:
     def num_tensors(self) -> int:
         return len(self.tensors)
 
-    def _weight_ptrs(self):
+    def component_offsets(self, component: int) -> Tuple[int, int]:
+        """(k H, k): the offsets in floats of row k of the output weight and of entry k of the output bias."""
+        k = int(component)
+        if not 0 <= k < self.n_outputs:
+            raise ValueError(f"component {component}: this network has the outputs 0 .. {self.n_outputs - 1}")
+        return (k * int(self.tensors[-2].shape[-1]), k) if k else (0, 0)
+
+    def _weight_ptrs(self, component: int = 0):
         for p in self.tensors:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("pinnrl_amd: parameters must be contiguous float32")
-        return (ctypes.c_void_p * len(self.tensors))(*[p.data_ptr() for p in self.tensors])
+        ptrs = [p.data_ptr() for p in self.tensors]
+        if component:
+            ow, ob = self.component_offsets(component)
+            ptrs[-2] += 4 * ow
+            ptrs[-1] += 4 * ob
+        return (ctypes.c_void_p * len(ptrs))(*ptrs)
 
     def grad_layout(self) -> Tuple[List[int], int]:
         """Offsets (in floats, 16-byte aligned) of every trainable tensor inside one flat gradient buffer."""
@@ -188,6 +218,26 @@ def _axis_desc(prog: "NetProgram", axis: int, direction: Optional[Sequence[int]]
     d = _lib.PinnNetDesc.from_buffer_copy(prog.desc)
     d.flags = (d.flags & ~_lib.PINN_FLAG_SPACE_AXIS_MASK) | _lib.PINN_FLAG_SPACE_AXIS(axis)
     return d
+
+
+def _launch_desc(prog: "NetProgram", axis: int = 0, direction: Optional[Sequence[int]] = None, component: int = 0):
+    """`_axis_desc` of a component launch.  A one-output program: exactly `_axis_desc`.  A program with several outputs
+    always takes the layer-major engine, through a by-value copy with PINN_FLAG_LAYER_MAJOR: row k of a width such as 30 is
+    only 4-byte aligned, and the tile-major kernels read weights with 16-byte loads.  `component` is range-checked here,
+    before any call into the library."""
+    prog.component_offsets(component)
+    desc = _axis_desc(prog, axis, direction)
+    if prog.n_outputs > 1 and not desc.flags & _lib.PINN_FLAG_LAYER_MAJOR:
+        if desc is prog.desc:
+            desc = _lib.PinnNetDesc.from_buffer_copy(prog.desc)
+        desc.flags |= _lib.PINN_FLAG_LAYER_MAJOR
+    return desc
+
+
+def _single_output(prog: "NetProgram", what: str) -> None:
+    if prog.n_outputs != 1:
+        raise NotImplementedError(f"pinnrl_amd: {what} takes a network with one output (this one has {prog.n_outputs}); the "
+                                  "fields of a multi-output network are reached through component jet launches")
 
 
 def _scratch(prog: "NetProgram", dev: torch.device, N: int, nt: int, nx: int, backward: bool, desc=None):
@@ -386,7 +436,100 @@ class MixedTermDesc(AxisTermDesc):
         return out
 
 
+class SystemTermDesc:
+    """E residuals in C fields, the fields being the components of one C-output network (`pinn_term_residual_system`).
+
+    terms: one sequence of factors per term, a factor being a coordinate name ("x", "y", "z", "t") or a pair (field index,
+    name) with the name one of `_lib.TERM_FACTOR_ND` ("u", "u_t", ..., "u_xxxx", "sin(u)", "cos(u)", "u_y", "u_yy", "u_z",
+    "u_zz": the streams of THAT field); at most 32 terms of at most 4 factors, shared by all equations; equation_of[m]: the
+    equation of term m; coef_values: the c_m, float32 on the device, read at LAUNCH time; dimension 1 .. 3; nt[c], nx[c]: the
+    time order and the space order per axis of field c — (nt[c], nx[c][0]) a compiled stream set, nx[c][1] and nx[c][2] 0 .. 2;
+    eq_weights: omega_e (default 1).  No mixed derivatives.  Wherever the engine takes an `AxisTermDesc` it takes a
+    `SystemTermDesc` too and runs the chain: one component jets_forward per (field, axis with streams),
+    term_residual_system, one component jets_backward per block.  Its residual tensor is (N, E) and its loss sum is
+    sum_e omega_e sum_n l(r_e,n)."""
+
+    def __init__(self, terms: Sequence[Sequence[object]], equation_of: Sequence[int], coef_values: Tensor, dimension: int,
+                 n_fields: int, n_equations: int, nt: Sequence[int], nx: Sequence[Sequence[int]],
+                 eq_weights: Optional[Sequence[float]] = None, loss: str = "mse", huber_delta: float = 1.0):
+        dim, C, E = int(dimension), int(n_fields), int(n_equations)
+        if dim not in (1, 2, 3):
+            raise ValueError(f"a system term residual has dimension 1, 2 or 3 (got {dimension})")
+        if not 1 <= C <= _lib.PINN_SYSTEM_MAX_FIELDS or not 1 <= E <= _lib.PINN_SYSTEM_MAX_EQUATIONS:
+            raise ValueError(f"a system has 1 .. {_lib.PINN_SYSTEM_MAX_FIELDS} fields and 1 .. {_lib.PINN_SYSTEM_MAX_EQUATIONS} "
+                             f"equations (got {n_fields} and {n_equations})")
+        if len(terms) > _lib.PINN_SYSTEM_MAX_TERMS:
+            raise ValueError(f"a system term residual has at most {_lib.PINN_SYSTEM_MAX_TERMS} terms (got {len(terms)})")
+        if len(equation_of) != len(terms) or any(not 0 <= int(e) < E for e in equation_of):
+            raise ValueError(f"equation_of: one equation index in [0, {E}) per term")
+        nt = tuple(int(v) for v in nt)
+        nx = tuple(tuple(int(v) for v in row) + (0,) * (3 - len(row)) for row in nx)
+        if len(nt) != C or len(nx) != C:
+            raise ValueError(f"nt and nx: one entry per field ({C})")
+        for c in range(C):
+            if len(nx[c]) != 3 or any(not 0 <= v <= 2 for v in nx[c][1:]) or any(v for v in nx[c][dim:]):
+                raise ValueError(f"field {c}: space orders {nx[c]}: one per axis, 0 .. 2 on the axes y and z, 0 beyond the dimension")
+        w = [1.0] * E if eq_weights is None else [float(v) for v in eq_weights]
+        if len(w) != E or any(not (v >= 0.0 and v != float("inf")) for v in w):
+            raise ValueError(f"eq_weights: {E} finite weights >= 0 (got {eq_weights})")
+        d = _lib.PinnTermPdeSystem()
+        d.dimension, d.n_fields, d.n_equations, d.n_terms = dim, C, E, len(terms)
+        for c in range(C):
+            d.time_order[c] = nt[c]
+            for a in range(3):
+                d.space_order[c][a] = nx[c][a]
+        for e in range(E):
+            d.eq_weight[e] = w[e]
+        d.loss = _lib.LOSS.get(loss, 0)  # unknown names fall back to mse (pde_base.py:313-315)
+        d.huber_delta = float(huber_delta)
+        norm: List[Tuple[object, ...]] = []
+        for m, factors in enumerate(terms):
+            factors = tuple(factors)
+            if len(factors) > _lib.PINN_TERM_MAX_FACTORS:
+                raise ValueError(f"term {m}: at most {_lib.PINN_TERM_MAX_FACTORS} factors (got {len(factors)})")
+            d.equation_of[m] = int(equation_of[m])
+            d.terms[m].n_factors = len(factors)
+            row = []
+            for f, fac in enumerate(factors):
+                field, name = (0, fac) if isinstance(fac, str) else (int(fac[0]), fac[1])
+                if name not in _lib.TERM_FACTOR_ND:
+                    raise ValueError(f"term {m}: unknown factor '{name}' (one of {', '.join(_lib.TERM_FACTOR_ND)}; mixed derivatives "
+                                     "are not available in systems)")
+                coord = name in ("x", "y", "z", "t")
+                if isinstance(fac, str) and not coord:
+                    raise ValueError(f"term {m}: factor '{name}' needs its field: (field index, '{name}')")
+                if not 0 <= field < C:
+                    raise ValueError(f"term {m}: factor '{name}' names field {field} of {C}")
+                d.terms[m].factor[f] = _lib.PINN_SYSTEM_FACTOR(0 if coord else field, _lib.TERM_FACTOR_ND[name])
+                row.append(name if coord else (field, name))
+            norm.append(tuple(row))
+        if coef_values.dtype != torch.float32 or not coef_values.is_contiguous() or coef_values.numel() < len(terms):
+            raise ValueError("coef_values: one contiguous float32 value per term")
+        self.desc = d
+        self.terms = norm
+        self.equation_of = [int(e) for e in equation_of]
+        self.coef_values = coef_values
+        self.dimension, self.n_fields, self.n_equations = dim, C, E
+        self.nt, self.nx, self.eq_weights = nt, nx, tuple(w)
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "SystemTermDesc":
+        """The same program and the same coefficient tensor under another loss kind."""
+        return SystemTermDesc(self.terms, self.equation_of, self.coef_values, self.dimension, self.n_fields, self.n_equations,
+                              self.nt, self.nx, self.eq_weights, loss, huber_delta)
+
+    def launches(self) -> List[Tuple[int, int, int, int]]:
+        """(field, axis, nt, nx) of the jet launches of the chain, block 3 field + axis each: per field the axis-0 launch
+        (always: it carries the value stream), then every further axis that has streams, on the set (0, nx[field][axis])."""
+        out = []
+        for c in range(self.n_fields):
+            out.append((c, 0, self.nt[c], self.nx[c][0]))
+            out += [(c, a, 0, self.nx[c][a]) for a in range(1, self.dimension) if self.nx[c][a] > 0]
+        return out
+
+
 def pde_streams(pd) -> Tuple[int, int]:
+    if isinstance(pd, SystemTermDesc):  # the set of field 0's axis-0 launch
+        return pd.nt[0], pd.nx[0][0]
     if isinstance(pd, AxisTermDesc):  # the set of the axis-0 launch
         return pd.nt, pd.nx[0]
     if isinstance(pd, TermDesc):
@@ -400,14 +543,15 @@ def pde_streams(pd) -> Tuple[int, int]:
 # raw launches
 # ---------------------------------------------------------------------------------------------
 def jets_forward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, axis: int = 0,
-                 direction: Optional[Sequence[int]] = None) -> Tensor:
+                 direction: Optional[Sequence[int]] = None, component: int = 0) -> Tensor:
     """(K, N) tensor of [u, d/dt.., d/dx_axis..] — one launch, no graph.  `axis`: the column of x the space streams
     differentiate along (non-zero: the layer-major engine; also the sets (0, 1) .. (0, 4)).  `direction`: a tuple of
-    -1 / 0 / +1 per space axis instead — the space streams are (sum_c d_c d/dx_c)^k u, sets (0, 1) .. (0, 4) only."""
+    -1 / 0 / +1 per space axis instead — the space streams are (sum_c d_c d/dx_c)^k u, sets (0, 1) .. (0, 4) only.
+    `component`: the output of a multi-output network the jets are of (`NetProgram`); composes with both."""
+    desc = _launch_desc(prog, axis, direction, component)
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
-    desc = _axis_desc(prog, axis, direction)
     K = 1 + nt + nx
     out = torch.empty((K, N), dtype=torch.float32, device=dev)
     if N == 0:
@@ -415,15 +559,22 @@ def jets_forward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, axis:
     optr = (ctypes.c_void_p * K)(*[out[s].data_ptr() for s in range(K)])
     ws, wptr, wn = _scratch(prog, dev, N, nt, nx, False, desc)
     with torch.cuda.device(dev):
-        _lib.check(lib.pinn_jet_forward(ctypes.byref(desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
+        _lib.check(lib.pinn_jet_forward(ctypes.byref(desc), prog._weight_ptrs(component), prog.num_tensors, x.data_ptr(),
                                         t.data_ptr(), N, nt, nx, optr, wptr, wn, _stream(dev)))
     return out
 
 
-def _grad_ptrs(prog: NetProgram, flat: Tensor):
+def _grad_ptrs(prog: NetProgram, flat: Tensor, component: int = 0):
+    """The gradient table over one flat buffer; for `component` k the output weight's entry points at row k of its slot
+    (k H floats in) and the output bias's at entry k, as in the weight table."""
     offs, _ = prog.grad_layout()
     base = flat.data_ptr()
-    return (ctypes.c_void_p * len(offs))(*[(base + 4 * o) if o >= 0 else None for o in offs])
+    ptrs = [(base + 4 * o) if o >= 0 else None for o in offs]
+    if component:
+        ow, ob = prog.component_offsets(component)
+        ptrs[-2] = ptrs[-2] + 4 * ow if ptrs[-2] is not None else None
+        ptrs[-1] = ptrs[-1] + 4 * ob if ptrs[-1] is not None else None
+    return (ctypes.c_void_p * len(offs))(*ptrs)
 
 
 def new_flat_grad(prog: NetProgram, dev: torch.device) -> Tensor:
@@ -437,12 +588,13 @@ def split_flat_grad(prog: NetProgram, flat: Tensor) -> List[Optional[Tensor]]:
 
 
 def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, flat_grad: Tensor, axis: int = 0,
-                  direction: Optional[Sequence[int]] = None) -> None:
-    """flat_grad += d<cot, jets>/d(theta).  cot: (K, N); `axis` and `direction` as for `jets_forward`."""
+                  direction: Optional[Sequence[int]] = None, component: int = 0) -> None:
+    """flat_grad += d<cot, jets>/d(theta).  cot: (K, N); `axis`, `direction` and `component` as for `jets_forward` (of the
+    output layer's gradient slots a component launch touches row `component` alone)."""
+    desc = _launch_desc(prog, axis, direction, component)
     lib = _lib.load()
     dev = _require_device(x, t, cot, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
-    desc = _axis_desc(prog, axis, direction)
     if N == 0:
         return
     K = 1 + nt + nx
@@ -451,20 +603,22 @@ def jets_backward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot:
     cptr = (ctypes.c_void_p * K)(*[cot[s].data_ptr() for s in range(K)])
     ws, wptr, wn = _scratch(prog, dev, N, nt, nx, True, desc)
     with torch.cuda.device(dev):
-        _lib.check(lib.pinn_jet_backward(ctypes.byref(desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
-                                         t.data_ptr(), N, nt, nx, cptr, _grad_ptrs(prog, flat_grad), wptr, wn, _stream(dev)))
+        _lib.check(lib.pinn_jet_backward(ctypes.byref(desc), prog._weight_ptrs(component), prog.num_tensors, x.data_ptr(),
+                                         t.data_ptr(), N, nt, nx, cptr, _grad_ptrs(prog, flat_grad, component), wptr, wn,
+                                         _stream(dev)))
 
 
 def jets_backward_inputs(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor,
                          flat_grad: Optional[Tensor], want_x: bool, want_t: bool,
-                         axis: int = 0, direction: Optional[Sequence[int]] = None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+                         axis: int = 0, direction: Optional[Sequence[int]] = None,
+                         component: int = 0) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """(x_grad (N, dim) | None, t_grad (N, 1) | None) = d<cot, jets>/d(x, t), and flat_grad += d<cot, jets>/d(theta) when
     given — one `pinn_jet_backward_inputs` launch on the layer-major engine (the descriptor is not touched).  cot: (K, N);
-    `axis` and `direction` as for `jets_forward` (every column of x_grad stays exact, mixed terms included)."""
+    `axis`, `direction` and `component` as for `jets_forward` (every column of x_grad stays exact, mixed terms included)."""
+    desc = _launch_desc(prog, axis, direction, component)
     lib = _lib.load()
     dev = _require_device(x, t, cot, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
-    desc = _axis_desc(prog, axis, direction)
     want_x = bool(want_x) and x.shape[1] > 0
     xg = torch.empty_like(x) if want_x else None
     tg = torch.empty_like(t) if want_t else None
@@ -477,9 +631,9 @@ def jets_backward_inputs(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: in
     nbytes = lib.pinn_workspace_bytes(ctypes.byref(desc), N, nt, nx, 2)
     ws = _workspace(dev, nbytes) if nbytes else None
     with torch.cuda.device(dev):
-        _lib.check(lib.pinn_jet_backward_inputs(ctypes.byref(desc), prog._weight_ptrs(), prog.num_tensors, x.data_ptr(),
+        _lib.check(lib.pinn_jet_backward_inputs(ctypes.byref(desc), prog._weight_ptrs(component), prog.num_tensors, x.data_ptr(),
                                                 t.data_ptr(), N, nt, nx, cptr,
-                                                _grad_ptrs(prog, flat_grad) if flat_grad is not None else None,
+                                                _grad_ptrs(prog, flat_grad, component) if flat_grad is not None else None,
                                                 xg.data_ptr() if xg is not None else None,
                                                 tg.data_ptr() if tg is not None else None,
                                                 ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
@@ -618,6 +772,75 @@ def term_residual_mixed(td: MixedTermDesc, jets: Sequence[Optional[Tensor]], x: 
     return r, cot
 
 
+def term_residual_system(td: SystemTermDesc, jets: Sequence[Optional[Tensor]], x: Tensor, t: Tensor, grad_scale: float = 0.0,
+                         residual_cotangent: Optional[Tensor] = None, want_residual: bool = True,
+                         loss_sum: Optional[Tensor] = None, want_cotangents: bool = False, coef_grads: Optional[Tensor] = None,
+                         eq_loss_sums: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[List[Optional[Tensor]]]]:
+    """`pinn_term_residual_system`: (residual (N, E) | None, cotangent blocks | None).  jets: 3 C blocks, entry 3 c + a — block
+    (c, 0) the (1 + nt[c] + nx[c][0], N) block of field c's axis-0 launch, block (c, a >= 1) the (1 + nx[c][a], N) block of its
+    axis-a launch, None where that order is 0; x: (N, dimension), t: N values; residual_cotangent: (N, E).  The cotangent blocks
+    have the shapes of the jets; every row the program never reads is zero, so each goes straight into `jets_backward`.
+    loss_sum[0] += sum_e omega_e sum_n l(r_e,n), eq_loss_sums[e] += sum_n l(r_e,n), coef_grads[m] += sum_n rbar prod_f phi
+    where given.  One launch, two with a sum; the residual is a transposed view of the (E, N) buffer the kernel writes."""
+    lib = _lib.load()
+    dim, C, E = td.dimension, td.n_fields, td.n_equations
+    jets = list(jets) + [None] * (3 * C - len(jets))
+    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums)
+    rows = []
+    for c in range(C):
+        rows += [1 + td.nt[c] + td.nx[c][0]] + [(1 + td.nx[c][a]) if (a < dim and td.nx[c][a] > 0) else 0 for a in (1, 2)]
+    if len(jets) != 3 * C or jets[0] is None or jets[0].dim() != 2:
+        raise ValueError(f"term_residual_system: {3 * C} blocks, jets[0] the (1 + nt + nx[0], N) block of field 0's axis-0 launch")
+    N = jets[0].shape[1]
+    for b in range(3 * C):
+        j = jets[b]
+        if (j is None) != (rows[b] == 0) or (j is not None and (tuple(j.shape) != (rows[b], N) or j.dtype != torch.float32
+                                                               or not j.is_contiguous())):
+            raise ValueError(f"term_residual_system: block {b} (field {b // 3}, axis {b % 3}) must be "
+                             f"{'None' if rows[b] == 0 else f'a contiguous float32 ({rows[b]}, {N}) tensor'}")
+    x, t = _f32c(x.detach()), _f32c(t.detach())
+    if x.numel() != N * dim or t.numel() != N:
+        raise ValueError(f"term_residual_system: x is (N, {dim}) and t holds N values (N = {N}; got {tuple(x.shape)}, {tuple(t.shape)})")
+    if residual_cotangent is not None:
+        if tuple(residual_cotangent.shape) != (N, E):
+            raise ValueError(f"term_residual_system: residual_cotangent is (N, E) = ({N}, {E}); got {tuple(residual_cotangent.shape)}")
+        residual_cotangent = _f32c(residual_cotangent.t())  # (E, N), equation e at e N
+    for tns in (loss_sum, coef_grads, eq_loss_sums):
+        assert tns is None or (tns.dtype == torch.float32 and tns.is_contiguous())
+    assert coef_grads is None or coef_grads.numel() >= td.desc.n_terms
+    assert eq_loss_sums is None or eq_loss_sums.numel() >= E
+    r = torch.empty((E, N), dtype=torch.float32, device=dev) if want_residual else None
+    cot = [torch.empty((k, N), dtype=torch.float32, device=dev) if k else None for k in rows] if want_cotangents else None
+    if N == 0:
+        return (r.t() if r is not None else None), cot
+    reduce = loss_sum is not None or coef_grads is not None or eq_loss_sums is not None
+    scratch = torch.empty(_lib.PINN_SYSTEM_SCRATCH_DOUBLES, dtype=torch.float64, device=dev) if reduce else None
+    opt = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
+    jptr = (ctypes.c_void_p * (3 * C))(*[opt(j) for j in jets])
+    cptr = (ctypes.c_void_p * (3 * C))(*[opt(c) for c in cot]) if cot is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_term_residual_system(ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(),
+                                                 N, float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum),
+                                                 opt(eq_loss_sums), cptr, opt(coef_grads), opt(scratch), _stream(dev)))
+    return (r.t() if r is not None else None), cot
+
+
+def _system_jets(prog: NetProgram, td: SystemTermDesc, x: Tensor, t: Tensor) -> List[Optional[Tensor]]:
+    """The forward half of a `SystemTermDesc` chain: one component jets_forward per (field, axis with streams)."""
+    if prog.n_outputs != td.n_fields:
+        raise ValueError(f"a system of {td.n_fields} fields needs a network with {td.n_fields} outputs (this one has {prog.n_outputs})")
+    jets: List[Optional[Tensor]] = [None] * (3 * td.n_fields)
+    for c, a, nt, nx in td.launches():
+        jets[3 * c + a] = jets_forward(prog, x, t, nt, nx, axis=a, component=c)
+    return jets
+
+
+def _system_backward(prog: NetProgram, td: SystemTermDesc, x: Tensor, t: Tensor, cot: Sequence[Optional[Tensor]], flat_grad: Tensor) -> None:
+    """The reverse half: one component jets_backward per block, all accumulating into the same flat gradient."""
+    for c, a, nt, nx in td.launches():
+        jets_backward(prog, x, t, nt, nx, cot[3 * c + a], flat_grad, axis=a, component=c)
+
+
 def _launch_line(key) -> dict:
     """The keyword of `jets_forward` / `jets_backward` for one entry of `launches()`: an axis, or a direction tuple."""
     return {"direction": key} if isinstance(key, tuple) else {"axis": key}
@@ -633,6 +856,7 @@ def _term_residual_nd(td: AxisTermDesc, *args, **kwargs):
 
 def _axes_jets(prog: NetProgram, td: AxisTermDesc, x: Tensor, t: Tensor) -> List[Optional[Tensor]]:
     """The forward half of an `AxisTermDesc` / `MixedTermDesc` chain: one jets_forward per launch of the descriptor."""
+    _single_output(prog, "a single-field term residual")
     jets: List[Optional[Tensor]] = [None] * (_lib.PINN_TERM_MIXED_BLOCKS if isinstance(td, MixedTermDesc) else 3)
     for b, (key, nt, nx) in zip(_launch_blocks(td), td.launches()):
         jets[b] = jets_forward(prog, x, t, nt, nx, **_launch_line(key))
@@ -653,6 +877,12 @@ def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: 
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    if isinstance(pd, SystemTermDesc):  # the chain over the fields and their axes; the residual is (N, E)
+        s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
+        if N == 0:
+            return (torch.empty((0, pd.n_equations), dtype=torch.float32, device=dev) if want_residual else None), s
+        r, _ = term_residual_system(pd, _system_jets(prog, pd, x, t), x, t, want_residual=want_residual, loss_sum=s)
+        return r, s
     if isinstance(pd, AxisTermDesc) and N:  # the chain over the axes: one jet launch each, then the element-wise residual
         s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
         r, _ = _term_residual_nd(pd, _axes_jets(prog, pd, x, t), x, t, want_residual=want_residual, loss_sum=s)
@@ -661,6 +891,7 @@ def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: 
         s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
         r, _ = term_residual(pd, jets_forward(prog, x, t, pd.nt, pd.nx), x, t, want_residual=want_residual, loss_sum=s)
         return r, s
+    _single_output(prog, "a compiled residual")
     r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
     s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
     if N:
@@ -684,6 +915,16 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
     lib = _lib.load()
     dev = _require_device(x, t, flat_grad, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
+    if isinstance(pd, SystemTermDesc):
+        # the chain over the fields: one component jet launch per (field, axis), the element-wise residuals of all equations
+        # with the weighted loss sum and one block of cotangents per launch, one component reverse sweep per block
+        s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
+        if N == 0:
+            return (torch.empty((0, pd.n_equations), dtype=torch.float32, device=dev) if want_residual else None), s
+        r, cot = term_residual_system(pd, _system_jets(prog, pd, x, t), x, t, grad_scale=grad_scale, want_residual=want_residual,
+                                      loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
+        _system_backward(prog, pd, x, t, cot, flat_grad)
+        return r, s
     if isinstance(pd, AxisTermDesc) and N:
         # the chain over the axes: one jet launch per axis, the element-wise residual with its loss sum and one block of
         # cotangents per launch, one reverse sweep per axis into the same flat gradient
@@ -700,6 +941,7 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
                                want_residual=want_residual, loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
         jets_backward(prog, x, t, pd.nt, pd.nx, cot, flat_grad)
         return r, s
+    _single_output(prog, "a compiled residual")
     r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
     s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
     if N:
@@ -741,6 +983,7 @@ def residual_loss_grad_inverse(prog: NetProgram, pd, coef_values: Tensor, x: Ten
     if coef_grads is not None and (coef_grads.dtype != torch.float32 or not coef_grads.is_contiguous() or coef_grads.numel() < 2):
         raise ValueError("coef_grads: at least 2 contiguous float32 values on the device")
     x, t, N = _prep_points(prog, x, t)
+    _single_output(prog, "a compiled residual")
     r = torch.empty((N, 1), dtype=torch.float32, device=dev) if want_residual else None
     s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
     if N:
@@ -762,6 +1005,11 @@ def residual_backward(prog: NetProgram, pd, x: Tensor, t: Tensor, res_bar: Tenso
     x, t, N = _prep_points(prog, x, t)
     if N == 0:
         return
+    if isinstance(pd, SystemTermDesc):  # res_bar: (N, E), the cotangent of the (N, E) residual
+        _, cot = term_residual_system(pd, _system_jets(prog, pd, x, t), x, t, residual_cotangent=res_bar.reshape(N, pd.n_equations),
+                                      want_residual=False, want_cotangents=True)
+        _system_backward(prog, pd, x, t, cot, flat_grad)
+        return
     res_bar = _f32c(res_bar).reshape(-1)
     assert res_bar.numel() == N
     if isinstance(pd, AxisTermDesc):  # the chain over the axes with the caller's cotangent in place of grad_scale l'(r)
@@ -774,6 +1022,7 @@ def residual_backward(prog: NetProgram, pd, x: Tensor, t: Tensor, res_bar: Tenso
                                want_residual=False, want_cotangents=True)
         jets_backward(prog, x, t, pd.nt, pd.nx, cot, flat_grad)
         return
+    _single_output(prog, "a compiled residual")
     nt, nx = pde_streams(pd)
     ws, wptr, wn = _scratch(prog, dev, N, nt, nx, True)
     with torch.cuda.device(dev):
@@ -1072,7 +1321,8 @@ def _stream_set_covering(nt: int, nx: int) -> Optional[Tuple[int, int]]:
         return None
 
 
-def _pure_input_grads(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, params, direction: str):
+def _pure_input_grads(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, cot: Tensor, params, direction: str,
+                      component: int = 0):
     """Differentiable part of d<cot, jets>/dx[:, 0] (direction "x") or d<cot, jets>/dt ("t") that stays on one axis: the
     value and the streams of that axis, each raised by one order, from a JetFunction one order higher.  (N, 1), or None
     when no compiled stream set reaches that order."""
@@ -1085,7 +1335,7 @@ def _pure_input_grads(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, 
     if ss is None:
         return None
     a, b = ss
-    J = JetFunction.apply(prog, x, t, a, b, *params)
+    J = JetFunction.apply(prog, x, t, a, b, component, *params) if component else JetFunction.apply(prog, x, t, a, b, *params)
     # stream of order j + 1 along the direction in the (a, b) set
     rows = [(1 + a + j) if direction == "x" else (1 + j) for j in range(len(sel))]
     out = None
@@ -1108,25 +1358,33 @@ class JetFunction(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, *params: Tensor):
-        ctx.prog, ctx.nt, ctx.nx = prog, nt, nx
+    def forward(ctx, prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, *params):
+        # `apply` takes no keywords: a component launch passes `component` as a plain int in front of the tensors,
+        # JetFunction.apply(prog, x, t, nt, nx, k, *params); without it (component 0) the arguments are as they always were
+        component = 0
+        if params and isinstance(params[0], int):
+            component, params = int(params[0]), params[1:]
+            ctx.lead = (None,) * 6
+        else:
+            ctx.lead = (None,) * 5
+        ctx.prog, ctx.nt, ctx.nx, ctx.component = prog, nt, nx, component
         ctx.save_for_backward(x, t)
-        return jets_forward(prog, x, t, nt, nx)
+        return jets_forward(prog, x, t, nt, nx, component=component)
 
     @staticmethod
     def backward(ctx, cot: Tensor):
-        prog, nt, nx = ctx.prog, ctx.nt, ctx.nx
+        prog, nt, nx, component = ctx.prog, ctx.nt, ctx.nx, ctx.component
         x, t = ctx.saved_tensors
         params = prog.tensors  # the live tensors this node was applied to (PINNModel.jets passes exactly these)
         want_x, want_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        want_w = any(ctx.needs_input_grad[5:])
+        want_w = any(ctx.needs_input_grad[len(ctx.lead):])
         if not (want_x or want_t):
             flat = new_flat_grad(prog, cot.device)
-            jets_backward(prog, x, t, nt, nx, cot, flat)
+            jets_backward(prog, x, t, nt, nx, cot, flat, component=component)
             grads = split_flat_grad(prog, flat)
-            return (None, None, None, None, None, *grads)
+            return (*ctx.lead, *grads)
         flat = new_flat_grad(prog, cot.device) if want_w else None
-        xg, tg = jets_backward_inputs(prog, x, t, nt, nx, cot.detach(), flat, want_x, want_t)
+        xg, tg = jets_backward_inputs(prog, x, t, nt, nx, cot.detach(), flat, want_x, want_t, component=component)
         grads = split_flat_grad(prog, flat) if flat is not None else [None] * len(prog.tensors)
         if xg is not None:
             xg = xg.to(x.dtype)
@@ -1142,7 +1400,7 @@ class JetFunction(torch.autograd.Function):
                     if c > 0:
                         cols.append(_NotTwiceDifferentiable.apply(xg[:, c:c + 1], what + " (spatial column >= 1)", *anchors))
                         continue
-                    pure = _pure_input_grads(prog, x, t, nt, nx, cot, params, "x")
+                    pure = _pure_input_grads(prog, x, t, nt, nx, cot, params, "x", component)
                     mixed = nt > 0 and bool(torch.any(cot[1:1 + nt] != 0))
                     if pure is None:
                         cols.append(_NotTwiceDifferentiable.apply(xg[:, 0:1], what + f" (x order {nx + 1} is beyond the compiled sets)",
@@ -1155,7 +1413,7 @@ class JetFunction(torch.autograd.Function):
                 xg = torch.cat(cols, 1)
             if tg is not None:
                 what = "d<cot, jets>/dt"
-                pure = _pure_input_grads(prog, x, t, nt, nx, cot, params, "t")
+                pure = _pure_input_grads(prog, x, t, nt, nx, cot, params, "t", component)
                 mixed = nx > 0 and bool(torch.any(cot[1 + nt:] != 0))
                 if pure is None:
                     tg = _NotTwiceDifferentiable.apply(tg, what + f" (t order {nt + 1} is beyond the compiled sets)", *anchors)
@@ -1164,7 +1422,7 @@ class JetFunction(torch.autograd.Function):
                                                                    *anchors)
                 else:
                     tg = pure.to(tg.dtype)
-        return (None, xg if want_x else None, tg if want_t else None, None, None, *grads)
+        return (None, xg if want_x else None, tg if want_t else None, *ctx.lead[3:], *grads)
 
 
 class ResidualFunction(torch.autograd.Function):

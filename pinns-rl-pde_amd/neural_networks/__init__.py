@@ -123,18 +123,24 @@ class BaseNetwork(nn.Module):
         if self._prog_cache is not None:
             self._prog_cache[1].set_deterministic(self._deterministic)
 
-    def jets(self, x: torch.Tensor, t: torch.Tensor, time_order: int = 0, space_order: int = 0) -> torch.Tensor:
-        """(K, N) = [u, d/dt.., d/dx..] in one launch; differentiable w.r.t. the parameters and w.r.t. x / t."""
+    def jets(self, x: torch.Tensor, t: torch.Tensor, time_order: int = 0, space_order: int = 0, component: int = 0) -> torch.Tensor:
+        """(K, N) = [u, d/dt.., d/dx..] in one launch; differentiable w.r.t. the parameters and w.r.t. x / t.  `component`:
+        the output the jets are of, for a network with output_dim > 1 (one launch per component)."""
         prog = self.program()
         params = prog.tensors
         if torch.is_grad_enabled() and (x.requires_grad or t.requires_grad or any(p.requires_grad for p in params)):
+            if component:
+                return _E.JetFunction.apply(prog, x, t, time_order, space_order, int(component), *params)
             return _E.JetFunction.apply(prog, x, t, time_order, space_order, *params)
-        return _E.jets_forward(prog, x, t, time_order, space_order)
+        return _E.jets_forward(prog, x, t, time_order, space_order, component=component)
 
     def forward(self, x: InputType) -> OutputType:
         inp = self._prepare_input(x)
         if inp.dim() != 2:
             raise ValueError(f"expected a (N, input_dim) input, got {tuple(inp.shape)}")
+        n_out = self.program().n_outputs
+        if n_out > 1:  # (N, C): one component launch per output
+            return torch.stack([self.jets(inp[:, :-1], inp[:, -1:], 0, 0, component=k)[0] for k in range(n_out)], 1)
         u = self.jets(inp[:, :-1], inp[:, -1:], 0, 0)
         return u[0].unsqueeze(1)
 
@@ -456,8 +462,8 @@ class PINNModel(BaseNetwork):
         prog = self.model.program()
         return prog
 
-    def jets(self, x, t, time_order: int = 0, space_order: int = 0):
-        return self.model.jets(x, t, time_order, space_order)
+    def jets(self, x, t, time_order: int = 0, space_order: int = 0, component: int = 0):
+        return self.model.jets(x, t, time_order, space_order, component=component)
 
     def forward(self, x):
         return self.model(x)

@@ -32,6 +32,38 @@ _PAIR_AXES = ((0, 1), (0, 2), (1, 2))  # the pairs of axes a mixed factor can na
 _COORD_AXIS = {"x": 0, "y": 1, "z": 2}
 
 
+def box_points(domain, time_domain, dim: int, nb: int, ni: int, dev: torch.device) -> Dict[str, Any]:
+    """The fixed boundary and initial points of a box in `dim` space dimensions (1-D: the two ends times the time grid, and the
+    line at t0).  x (n, dim), t (n, 1): [face (axis 0, low) | face (axis 0, high) | face (axis 1, low) | ... | initial points];
+    every face is the tensor grid of the other coordinates and of time (nb points each: nb^dim per face, the two faces of an
+    axis in the same order, so point k of the low face pairs with point k of the high one); the initial points xi are the
+    tensor grid of the box (ni per axis) at time_domain[0].  n_face, n_bc = 2 dim n_face, n_ic."""
+    t0, t1 = float(time_domain[0]), float(time_domain[1])
+    lin = [torch.linspace(domain[d][0], domain[d][1], nb, device=dev) for d in range(dim)]
+    tl = torch.linspace(t0, t1, nb, device=dev)
+    xs, ts = [], []
+    for a in range(dim):
+        others = [lin[d] for d in range(dim) if d != a] + [tl]
+        mesh = [g.reshape(-1) for g in torch.meshgrid(*others, indexing="ij")]
+        for side in (0, 1):
+            cols, k = [], 0
+            for d in range(dim):
+                if d == a:
+                    cols.append(torch.full_like(mesh[0], float(domain[a][side])))
+                else:
+                    cols.append(mesh[k])
+                    k += 1
+            xs.append(torch.stack(cols, dim=1))
+            ts.append(mesh[-1].reshape(-1, 1))
+    n_face = nb ** dim
+    gi = [torch.linspace(domain[d][0], domain[d][1], ni, device=dev) for d in range(dim)]
+    xi = torch.stack([g.reshape(-1) for g in torch.meshgrid(*gi, indexing="ij")], dim=1)
+    xs.append(xi)
+    ts.append(torch.full((xi.shape[0], 1), t0, device=dev))
+    return {"x": torch.cat(xs, 0).float().contiguous(), "t": torch.cat(ts, 0).float().contiguous(), "xi": xi, "n_face": n_face,
+            "n_bc": 2 * dim * n_face, "n_ic": xi.shape[0]}
+
+
 class TermPDEnD(PDEBase):
     """`TermPDEnD(config, terms, initial_condition_fn, exact_solution_fn=None)` for `config.dimension` 2 or 3.
 
@@ -188,35 +220,13 @@ class TermPDEnD(PDEBase):
         dev = torch.device(self.device)
         if self._points is not None and self._points[0] == dev:
             return self._points[1]
-        dim, nb, ni = self.dimension, self._nb, self._ni
-        t0, t1 = float(self.time_domain[0]), float(self.time_domain[1])
-        lin = [torch.linspace(self.domain[d][0], self.domain[d][1], nb, device=dev) for d in range(dim)]
-        tl = torch.linspace(t0, t1, nb, device=dev)
-        xs, ts = [], []
-        for a in range(dim):
-            others = [lin[d] for d in range(dim) if d != a] + [tl]
-            mesh = [g.reshape(-1) for g in torch.meshgrid(*others, indexing="ij")]
-            for side in (0, 1):
-                cols, k = [], 0
-                for d in range(dim):
-                    if d == a:
-                        cols.append(torch.full_like(mesh[0], float(self.domain[a][side])))
-                    else:
-                        cols.append(mesh[k])
-                        k += 1
-                xs.append(torch.stack(cols, dim=1))
-                ts.append(mesh[-1].reshape(-1, 1))
-        n_face = nb ** dim
-        gi = [torch.linspace(self.domain[d][0], self.domain[d][1], ni, device=dev) for d in range(dim)]
-        xi = torch.stack([g.reshape(-1) for g in torch.meshgrid(*gi, indexing="ij")], dim=1)
-        xs.append(xi)
-        ts.append(torch.full((xi.shape[0], 1), t0, device=dev))
+        pts = box_points(self.domain, self.time_domain, self.dimension, self._nb, self._ni, dev)
+        xi = pts.pop("xi")
         with torch.no_grad():
             u0 = self._initial_condition_fn(xi).reshape(-1).float().contiguous()
         if u0.shape[0] != xi.shape[0]:
             raise ValueError(f"{type(self).__name__}: initial_condition_fn returned {u0.shape[0]} values for {xi.shape[0]} points")
-        pts = {"x": torch.cat(xs, 0).float().contiguous(), "t": torch.cat(ts, 0).float().contiguous(), "n_face": n_face,
-               "n_bc": 2 * dim * n_face, "n_ic": xi.shape[0], "u0": u0.to(dev)}
+        pts["u0"] = u0.to(dev)
         if self._bc[0] == "dirichlet":
             pts["ub"] = torch.full((pts["n_bc"],), self._bc[1], dtype=torch.float32, device=dev)
         self._points = (dev, pts)

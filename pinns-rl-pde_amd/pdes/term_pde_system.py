@@ -1,0 +1,343 @@
+"""`TermPDESystem`: a coupled system of PDEs given as data — several unknowns, several equations.
+
+The fields are the outputs of ONE network with `output_dim = C`.  Output k of such a network is exactly the one-output network
+whose output layer is row k of the output weight and entry k of the output bias, so the jets of field k come from a component
+launch (`engine.jets_forward(..., component=k)`): the layer-major engine with the two output-layer entries of its weight table
+(and of its gradient table) pointing at row k.  `pinn_term_residual_system` combines the streams of all fields into
+
+    r_e = sum_{m in equation e} c_m prod_f phi_{m,f},   phi a stream of ANY field, a coordinate, sin / cos of a field,
+
+and hands every (field, axis) block its cotangents for one component reverse sweep each.  Residuals, loss and gradient stay
+free of autograd, so the launch list, the captured step and the flat L-BFGS closure take such a system as they take
+`TermPDEnD`.  A component launch recomputes the trunk: a C-field system costs about C single-field chains.  Mixed derivatives
+are not available in systems.
+"""
+
+from __future__ import annotations
+
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from .. import _lib
+from .. import engine as _E
+from .pde_base import PDEBase, PDEConfig, _pick_stream_set
+from .term_pde import Coef
+from .term_pde_nd import box_points
+
+_SUFFIX = {  # factor suffix -> (the one-field factor name, time order, (axis, space order))
+    "": ("u", 0, (0, 0)), "t": ("u_t", 1, (0, 0)), "tt": ("u_tt", 2, (0, 0)),
+    "x": ("u_x", 0, (0, 1)), "xx": ("u_xx", 0, (0, 2)), "xxx": ("u_xxx", 0, (0, 3)), "xxxx": ("u_xxxx", 0, (0, 4)),
+    "y": ("u_y", 0, (1, 1)), "yy": ("u_yy", 0, (1, 2)), "z": ("u_z", 0, (2, 1)), "zz": ("u_zz", 0, (2, 2)),
+}
+_COORDS = {"x": 0, "y": 1, "z": 2, "t": -1}
+PINN_MAX_POINT_TERMS = 8  # the loss terms one pinn_jet_losses call takes
+
+
+class TermPDESystem(PDEBase):
+    """`TermPDESystem(config, fields, equations, initial_condition_fn, exact_solution_fn=None, equation_weights=None,
+    initial_condition_fields=None)` for `config.dimension` 1, 2 or 3.
+
+    fields: 1 to 4 names, each an identifier without "_" and none of x, y, z, t; field k is output k of the model, and
+        `config.output_dim` is set to their number.
+    equations: 1 to 4 term lists `[(coef, factors), ...]` in `TermPDE`'s form (coef a number or `(scale, "parameter name")`), at
+        most 32 terms of at most 4 factors over all equations.  Factor names: "<field>", "<field>_t", "<field>_tt",
+        "<field>_x" .. "<field>_xxxx", "<field>_y", "<field>_yy", "<field>_z", "<field>_zz", "sin(<field>)", "cos(<field>)", "x",
+        "y", "z", "t".  Per field the smallest compiled stream set that holds its factors is launched.
+    equation_weights: omega_e >= 0 (default 1): the residual loss is sum_e omega_e mean l(r_e).
+    initial_condition_fn(x: (n, dim)) -> (n, len(initial_condition_fields)); initial_condition_fields defaults to all fields.
+    exact_solution_fn(x, t) -> (n, C): enables `validate()`.
+
+    config.boundary_conditions is `{"periodic": {}}` (every field, opposite faces paired point by point) or
+    `{"dirichlet": {"type": "fixed", "value": v}}` with v a number or a list of C entries; an entry None means no boundary
+    term for that field (the pressure of incompressible flow).  Boundary and initial losses are sums over the fields.  The
+    fixed points are `TermPDEnD`'s: every face a tensor grid of the other coordinates and of time (in 1-D the two ends times
+    the time grid), the initial points a tensor grid of the box at `time_domain[0]`.
+
+    Gray-Scott in 1-D:
+        TermPDESystem(cfg, ("u", "v"),
+                      [[(1.0, ("u_t",)), ((-1.0, "Du"), ("u_xx",)), (1.0, ("u", "v", "v")), ((-1.0, "F"), ()), ((1.0, "F"), ("u",))],
+                       [(1.0, ("v_t",)), ((-1.0, "Dv"), ("v_xx",)), (-1.0, ("u", "v", "v")), ((1.0, "Fk"), ("v",))]],
+                      lambda x: torch.stack([1 - 0.5 * torch.exp(-50 * x[:, 0] ** 2), 0.25 * torch.exp(-50 * x[:, 0] ** 2)], 1))
+    """
+
+    KIND = "term_system"  # not a `_lib.PDE` kind: the descriptor is a `SystemTermDesc`
+
+    def __init__(self, config: PDEConfig, fields: Sequence[str], equations: Sequence[Sequence[Tuple[Coef, Sequence[str]]]],
+                 initial_condition_fn: Callable[[torch.Tensor], torch.Tensor],
+                 exact_solution_fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
+                 equation_weights: Optional[Sequence[float]] = None, initial_condition_fields: Optional[Sequence[str]] = None,
+                 boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32, **kwargs):
+        who = type(self).__name__
+        dim = int(getattr(config, "dimension", 1))
+        if dim not in (1, 2, 3):
+            raise NotImplementedError(f"{who}: dimension {dim}: one to three space dimensions")
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        if not 1 <= len(fields) <= _lib.PINN_SYSTEM_MAX_FIELDS:
+            raise ValueError(f"{who}: {len(fields)} fields; a system has 1 to {_lib.PINN_SYSTEM_MAX_FIELDS}")
+        for name in fields:
+            if not isinstance(name, str) or not name.isidentifier() or "_" in name or name in _COORDS:
+                raise ValueError(f"{who}: field name {name!r}: an identifier without '_' that is none of x, y, z, t")
+        if len(set(fields)) != len(fields):
+            raise ValueError(f"{who}: field names {fields} repeat")
+        equations = [list(eq) for eq in equations]
+        if not 1 <= len(equations) <= _lib.PINN_SYSTEM_MAX_EQUATIONS:
+            raise ValueError(f"{who}: {len(equations)} equations; a system has 1 to {_lib.PINN_SYSTEM_MAX_EQUATIONS}")
+        n_terms = sum(len(eq) for eq in equations)
+        if n_terms > _lib.PINN_SYSTEM_MAX_TERMS:
+            raise ValueError(f"{who}: {n_terms} terms over all equations; a system has at most {_lib.PINN_SYSTEM_MAX_TERMS}")
+        if not callable(initial_condition_fn):
+            raise TypeError(f"{who}: initial_condition_fn(x: (n, dim)) -> (n, number of initial fields) is required")
+        if int(boundary_points_per_axis) < 2 or int(initial_points_per_axis) < 2:
+            raise ValueError(f"{who}: at least 2 boundary and 2 initial points per axis")
+        C = len(fields)
+        index = {name: c for c, name in enumerate(fields)}
+        self.fields = fields
+        self._term_coefs: List[Coef] = []
+        self._term_factors: List[Tuple[object, ...]] = []
+        self._equation_of: List[int] = []
+        nt, nx = [0] * C, [[0, 0, 0] for _ in range(C)]
+        for e, eq in enumerate(equations):
+            for coef, factors in eq:
+                m = len(self._term_coefs)
+                factors = (factors,) if isinstance(factors, str) else tuple(factors)
+                if len(factors) > _lib.PINN_TERM_MAX_FACTORS:
+                    raise ValueError(f"{who}: equation {e}, term {m} has {len(factors)} factors; a term has at most "
+                                     f"{_lib.PINN_TERM_MAX_FACTORS}")
+                row = []
+                for f in factors:
+                    parsed = self._parse_factor(f, index)
+                    if parsed is None:
+                        raise ValueError(f"{who}: equation {e}, term {m}: unknown factor '{f}' (a coordinate x, y, z, t, or one of "
+                                         f"<field>, <field>_t, _tt, _x .. _xxxx, _y, _yy, _z, _zz, sin(<field>), cos(<field>) with "
+                                         f"<field> in {', '.join(fields)}; mixed derivatives are not available in systems)")
+                    c, name, t_order, (axis, order) = parsed
+                    need = _COORDS[name] if c is None else (axis if order else 0)
+                    if need >= dim:
+                        raise ValueError(f"{who}: equation {e}, term {m}: factor '{f}' needs dimension {need + 1}, the problem has {dim}")
+                    if c is None:
+                        row.append(name)
+                        continue
+                    nt[c] = max(nt[c], t_order)
+                    nx[c][axis] = max(nx[c][axis], order)
+                    row.append((c, name))
+                if isinstance(coef, (tuple, list)):
+                    if len(coef) != 2 or not isinstance(coef[1], str):
+                        raise ValueError(f"{who}: equation {e}, term {m}: a coefficient is a number or (scale, 'parameter name')")
+                    coef = (float(coef[0]), coef[1])
+                else:
+                    coef = float(coef)
+                self._term_coefs.append(coef)
+                self._term_factors.append(tuple(row))
+                self._equation_of.append(e)
+        for c in range(C):
+            try:
+                nt[c], nx[c][0] = _pick_stream_set(nt[c], nx[c][0])
+            except NotImplementedError:
+                raise NotImplementedError(
+                    f"{who}: the factors of field '{fields[c]}' need time order {nt[c]} together with order {nx[c][0]} along x, and no "
+                    "compiled stream set holds both (time order 2 goes with space order 0 or 2)") from None
+        self._nt, self._nx = tuple(nt), tuple(tuple(v) for v in nx)
+        E = len(equations)
+        w = [1.0] * E if equation_weights is None else [float(v) for v in equation_weights]
+        if len(w) != E or any(not (v >= 0.0 and v != float("inf")) for v in w):
+            raise ValueError(f"{who}: equation_weights: {E} finite weights >= 0 (got {equation_weights})")
+        self._eq_weights = tuple(w)
+        # ---- boundary and initial conditions
+        bcs = dict(getattr(config, "boundary_conditions", None) or {})
+        if list(bcs) == ["dirichlet"]:
+            p = bcs["dirichlet"] or {}
+            if p.get("type", "fixed") != "fixed":
+                raise NotImplementedError(f"{who}: dirichlet boundary of type '{p.get('type')}': a fixed value on all faces only")
+            v = p.get("value", 0.0)
+            vals = list(v) if isinstance(v, (list, tuple)) else [v] * C
+            if len(vals) != C:
+                raise ValueError(f"{who}: dirichlet value {v}: a number or one entry (a number or None) per field ({C})")
+            self._bc = ("dirichlet", tuple(None if x is None else float(x) for x in vals))
+            n_bc_terms = sum(x is not None for x in vals)
+        elif list(bcs) == ["periodic"]:
+            self._bc = ("periodic", None)
+            n_bc_terms = dim * C
+        else:
+            raise NotImplementedError(
+                f"{who}: boundary conditions {sorted(bcs)}: exactly one of {{'dirichlet': {{'type': 'fixed', 'value': v}}}} on all "
+                "faces or {'periodic': {}} (Neumann and Robin faces read derivative streams on the faces: not available)")
+        ic_fields = fields if initial_condition_fields is None else tuple(initial_condition_fields)
+        for name in ic_fields:
+            if name not in index:
+                raise ValueError(f"{who}: initial_condition_fields names '{name}', which is none of the fields {fields}")
+        if len(set(ic_fields)) != len(ic_fields):
+            raise ValueError(f"{who}: initial_condition_fields {ic_fields} repeat")
+        self._ic_fields = tuple(index[name] for name in ic_fields)
+        if n_bc_terms + len(self._ic_fields) > PINN_MAX_POINT_TERMS:
+            raise NotImplementedError(
+                f"{who}: the boundary / initial chain has {n_bc_terms + len(self._ic_fields)} loss terms ({n_bc_terms} boundary + "
+                f"{len(self._ic_fields)} initial); one pinn_jet_losses call takes at most {PINN_MAX_POINT_TERMS}")
+        if list(getattr(config, "trainable_parameters", []) or []):
+            raise NotImplementedError(f"{who}: trainable parameters (inverse problems) are not covered: the coefficients of a "
+                                      "term residual are read by value")
+        super().__init__(config)
+        self.config.output_dim = C
+        if self._training_mode() != "forward" or self.observation_data:
+            raise NotImplementedError(f"{who}: data modes and observation data are not covered (forward problems only)")
+        for coef in self._term_coefs:
+            if isinstance(coef, tuple) and self.get_parameter(coef[1]) is None:
+                raise ValueError(f"{who}: coefficient parameter '{coef[1]}' is not in config.parameters")
+        self._initial_condition_fn = initial_condition_fn
+        self._exact_solution_fn = exact_solution_fn
+        self._nb, self._ni = int(boundary_points_per_axis), int(initial_points_per_axis)
+        self._coef_values: Optional[torch.Tensor] = None
+        self._coef_device: Optional[torch.device] = None
+        self._descs: Dict[Any, Any] = {}
+        self._points: Optional[Tuple[torch.device, Dict[str, Any]]] = None
+
+    @staticmethod
+    def _parse_factor(f: str, index: Dict[str, int]):
+        """(field index | None, one-field factor name, time order, (axis, space order)) of a factor name, or None."""
+        if not isinstance(f, str):
+            return None
+        if f in _COORDS:
+            return None, f, 0, (0, 0)
+        for fn in ("sin", "cos"):
+            if f.startswith(fn + "(") and f.endswith(")") and f[4:-1] in index:
+                return index[f[4:-1]], f"{fn}(u)", 0, (0, 0)
+        name, _, suffix = f.partition("_")
+        if name in index and suffix in _SUFFIX and ("_" in f) == bool(suffix):
+            one, t_order, axis_order = _SUFFIX[suffix]
+            return index[name], one, t_order, axis_order
+        return None
+
+    # ---------------------------------------------------------------- coefficients and descriptors
+    @property
+    def n_fields(self) -> int:
+        return len(self.fields)
+
+    @property
+    def n_equations(self) -> int:
+        return len(self._eq_weights)
+
+    def _coefficients(self):
+        return tuple(c[0] * float(self.get_parameter(c[1], required=True)) if isinstance(c, tuple) else c for c in self._term_coefs)
+
+    def _has_trainable_coefficients(self) -> bool:
+        return False
+
+    @property
+    def coef_values(self) -> torch.Tensor:
+        """The c_m as float32 on the PDE's device, one per term, built once: what the kernel reads at launch time."""
+        dev = torch.device(self.device)  # the REQUESTED device is remembered beside the tensor (see TermPDE.coef_values)
+        if self._coef_values is None or self._coef_device != dev:
+            self._coef_values = torch.tensor([float(c) for c in self._coefficients()], dtype=torch.float32, device=dev).reshape(-1)
+            self._coef_device = dev
+            self._descs = {}
+        return self._coef_values
+
+    def _term_desc(self, loss: str, delta: float) -> "_E.SystemTermDesc":
+        cv = self.coef_values
+        key = (loss, float(delta))
+        if key not in self._descs:
+            self._descs[key] = _E.SystemTermDesc(self._term_factors, self._equation_of, cv, self.dimension, self.n_fields,
+                                                 self.n_equations, self._nt, self._nx, self._eq_weights, loss, delta)
+        return self._descs[key]
+
+    def _pde_desc(self):
+        return self._term_desc(self._loss_function_name(), self._huber_delta())
+
+    def _pde_desc_l1(self):
+        return self._term_desc("mae", 1.0)
+
+    def exact_solution(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        if self._exact_solution_fn is None:
+            raise NotImplementedError(f"{type(self).__name__}: no exact_solution_fn was given")
+        u = self._exact_solution_fn(x, t)
+        if u.dim() != 2 or u.shape[1] != self.n_fields:
+            raise ValueError(f"{type(self).__name__}: exact_solution_fn returned {tuple(u.shape)}, expected (n, {self.n_fields})")
+        return u
+
+    def validate(self, model, num_points: int = 1000) -> Dict[str, float]:
+        """`PDEBase.validate` over all fields, plus "relative_l2_error" = ||u_pred - u_exact|| / ||u_exact|| over all of them."""
+        x, t = self.generate_collocation_points(num_points)
+        with torch.no_grad():
+            u_pred = model(torch.cat([x, t], dim=1))
+        exact = self.exact_solution(x, t).to(u_pred.dtype)
+        err = torch.abs(u_pred - exact)
+        return {"l2_error": torch.mean(err**2).item(), "max_error": torch.max(err).item(), "mean_error": torch.mean(err).item(),
+                "relative_l2_error": (torch.linalg.norm(err) / torch.linalg.norm(exact)).item()}
+
+    def _check_model(self, model) -> None:
+        C = getattr(getattr(model, "model", model), "output_dim", None)
+        if C is not None and int(C) != self.n_fields:
+            raise ValueError(f"{type(self).__name__}: {self.n_fields} fields {self.fields} need a model with output_dim = {self.n_fields} "
+                             f"(this one has {C})")
+
+    def compute_residual(self, model, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """(N, E) residuals with a grad_fn towards the network parameters."""
+        self._check_model(model)
+        return super().compute_residual(model, x, t)
+
+    # ---------------------------------------------------------------- fixed evaluation points
+    def _system_points(self) -> Dict[str, Any]:
+        """`box_points` of the problem, built once per device, with u0 (n_ic, number of initial fields) the initial targets and,
+        under Dirichlet faces, ub[c] (n_bc,) the constant target of field c (None where the field has no boundary term)."""
+        dev = torch.device(self.device)
+        if self._points is not None and self._points[0] == dev:
+            return self._points[1]
+        pts = box_points(self.domain, self.time_domain, self.dimension, self._nb, self._ni, dev)
+        with torch.no_grad():
+            u0 = self._initial_condition_fn(pts["xi"])
+        u0 = (u0.reshape(-1, 1) if u0.dim() == 1 else u0).float()
+        if tuple(u0.shape) != (pts["n_ic"], len(self._ic_fields)):
+            raise ValueError(f"{type(self).__name__}: initial_condition_fn returned {tuple(u0.shape)} for {pts['n_ic']} points, expected "
+                             f"({pts['n_ic']}, {len(self._ic_fields)})")
+        pts["u0"] = u0.t().contiguous().to(dev)  # (fields, n_ic): one contiguous target per initial field
+        if self._bc[0] == "dirichlet":
+            pts["ub"] = [None if v is None else torch.full((pts["n_bc"],), v, dtype=torch.float32, device=dev) for v in self._bc[1]]
+        self._points = (dev, pts)
+        return pts
+
+    # ---------------------------------------------------------------- losses
+    def compute_loss(self, model, x: torch.Tensor, t: torch.Tensor, n_total: Optional[int] = None,
+                     aux_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+        """residual = sum_e omega_e mean l(r_e) (the chain behind `engine.residual_loss_grad`); boundary and initial: sums over
+        the fields of the means on the fixed points, from ONE (n, C) forward of the model (C component launches, differentiable
+        through `JetFunction`); then `_compose_losses`' tail."""
+        self._check_model(model)
+        dev = self.device
+        residual_loss = self._residual_loss(model, x, t, n_total)
+        P = self._system_points()
+        u = model(torch.cat([P["x"], P["t"]], dim=1))
+        nbc, nf = P["n_bc"], P["n_face"]
+        boundary_loss = torch.zeros((), device=dev)
+        for c in range(self.n_fields):
+            if self._bc[0] == "dirichlet":
+                if P["ub"][c] is not None:
+                    boundary_loss = boundary_loss + self._apply_loss_fn(u[:nbc, c] - P["ub"][c])
+            else:
+                for a in range(self.dimension):
+                    lo = 2 * a * nf
+                    boundary_loss = boundary_loss + self._apply_loss_fn(u[lo : lo + nf, c] - u[lo + nf : lo + 2 * nf, c])
+        initial_loss = torch.zeros((), device=dev)
+        for k, c in enumerate(self._ic_fields):
+            initial_loss = initial_loss + self._apply_loss_fn(u[nbc:, c] - P["u0"][k])
+        zero = torch.zeros((), device=dev)
+        return self._compose_losses(residual_loss, boundary_loss, initial_loss, zero, zero, aux_scale)
+
+    def _manual_chain(self, n_batch: int) -> Dict[str, Any]:
+        """`compute_loss`' boundary / initial part as data for the launch list.  "components" = C: the value rows of the C
+        component forwards on the fixed points are stacked as a (C, n) block, the loss terms name their field as the stream, and
+        row c of the cotangent block feeds component c's reverse launch.  Boundary terms in the order of `compute_loss`."""
+        P = self._system_points()
+        lw = self._loss_weights()
+        bw, iw = (lw.get("boundary", 10.0), lw.get("initial", 10.0)) if lw else (10.0, 10.0)
+        nbc, nf = P["n_bc"], P["n_face"]
+        terms = []
+        for c in range(self.n_fields):
+            if self._bc[0] == "dirichlet":
+                if P["ub"][c] is not None:
+                    terms.append((0, nbc, c, 0, P["ub"][c], float(bw)))
+            else:
+                terms += [(2 * a * nf, 2 * a * nf + nf, c, nf, None, float(bw)) for a in range(self.dimension)]
+        n_bc_terms = len(terms)
+        for k, c in enumerate(self._ic_fields):
+            terms.append((nbc, nbc + P["n_ic"], c, 0, P["u0"][k], float(iw)))
+        return {"x": P["x"], "t": P["t"], "nt": 0, "nx": 0, "terms": terms, "n_bc": n_bc_terms, "components": self.n_fields}

@@ -465,6 +465,7 @@ class PDETrainer:
         from ..pdes.pde_base import PDEBase
         from ..pdes.term_pde import TermPDE
         from ..pdes.term_pde_nd import TermPDEnD
+        from ..pdes.term_pde_system import TermPDESystem
 
         tc = self.config.training
         kind = getattr(tc, "optimizer", "adam")
@@ -486,6 +487,28 @@ class PDETrainer:
                 return "TermPDEnD under a process group"
             if self.rl_agent is not None:
                 return "TermPDEnD with an RL agent (the agent's grid sampler is the 1-D launch list's)"
+        system = isinstance(self.pde, TermPDESystem)
+        if system:
+            # a coupled system: the chain of `engine.residual_loss_grad` over the fields and their axes (component launches) and
+            # the class's own boundary / initial chain cover Adam with fixed loss weights and L-BFGS on one device, with the
+            # uniform and the stratified sampler
+            if self.use_adaptive_weights:
+                return "TermPDESystem with adaptive loss weights (the three components would be sums over fields and equations)"
+            if self._causal is not None:
+                return "TermPDESystem with causal weighting (pinn_causal_weights takes one residual field)"
+            if self.process_group is not None:
+                return "TermPDESystem under a process group"
+            if self.rl_agent is not None:
+                return "TermPDESystem with an RL agent (the agent's reward is one residual field)"
+            if getattr(tc, "collocation_distribution", "uniform") == "residual_based":
+                return "TermPDESystem with the residual-based sampler (its weights come from one residual field)"
+            if len(getattr(self.pde, "_trainable_params", {})):
+                return "TermPDESystem with trainable parameters (the coefficients of a term residual are read by value)"
+            if self.pde._training_mode() != "forward" or getattr(self.pde, "observation_data", None):
+                return "TermPDESystem in a data mode (the launch list of a system covers forward problems)"
+            n_out = getattr(getattr(self.model, "model", self.model), "output_dim", None)
+            if n_out != self.pde.n_fields:
+                return f"TermPDESystem with {self.pde.n_fields} fields on a model whose output_dim is {n_out}"
         if self.rl_agent is not None and not hasattr(self.rl_agent, "action_probabilities"):
             return "RL agent without a device-side action selection"
         if getattr(tc, "collocation_distribution", "uniform") not in ("uniform", "stratified", "residual_based"):
@@ -519,7 +542,7 @@ class PDETrainer:
                 return "smoothness term"
             if self.process_group is not None:
                 return "smoothness term under a process group"
-        if self.pde.dimension != 1 and not nd:
+        if self.pde.dimension != 1 and not nd and not system:
             return "multi-dimensional problem"
         mode = self.pde._training_mode()
         if mode == "data_only":
@@ -722,7 +745,8 @@ class PDETrainer:
                 ch["t"] = torch.cat([ch["t"], to], 0).contiguous()
                 ch["terms"] = list(ch["terms"]) + [(lo, lo + xo.shape[0], 0, 0, obs["u"].to(dev).float().reshape(-1).contiguous(), float(dw))]
                 ch["has_data"] = True
-            K, npts = 1 + ch["nt"] + ch["nx"], ch["x"].shape[0]
+            # a system's chain ("components" = C): the value rows of its C component forwards, stacked, are the (C, n) block
+            K, npts = ch.get("components") or (1 + ch["nt"] + ch["nx"]), ch["x"].shape[0]
             ch["term_losses"] = torch.zeros(len(ch["terms"]), dtype=torch.float32, device=dev)
             ch["cot"] = torch.zeros(K, npts, dtype=torch.float32, device=dev)
             ch["terms_dp"] = [(lo, hi, st, pr, tg, w / world) for lo, hi, st, pr, tg, w in ch["terms"]]
@@ -810,12 +834,21 @@ class PDETrainer:
             else:
                 _E.residual_loss_grad(prog, pd, x, t, F["rw"] / float(N), F["grad"][:n], loss_sum=F["grad"][n : n + 1])
 
+        C = ch.get("components", 0)  # a system: one component launch per field, its value row the stream of that field
+
         def boundary_chain(grad, summary):
-            u = _E.jets_forward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"])
+            if C:
+                u = torch.cat([_E.jets_forward(prog, ch["x"], ch["t"], 0, 0, component=c) for c in range(C)], 0)
+            else:
+                u = _E.jets_forward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"])
             _E.jet_losses(u, ch["terms"], loss_name, delta, ch["term_losses"], ch["cot"],
                           residual_sum=F["grad"][n : n + 1] if summary else None, residual_scale=1.0 / float(N),
                           residual_weight=F["rw"], n_boundary_terms=ch["n_bc"], summary4=F["summary"] if summary else None)
-            _E.jets_backward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"], ch["cot"], grad)
+            if C:
+                for c in range(C):
+                    _E.jets_backward(prog, ch["x"], ch["t"], 0, 0, ch["cot"][c : c + 1], grad, component=c)
+            else:
+                _E.jets_backward(prog, ch["x"], ch["t"], ch["nt"], ch["nx"], ch["cot"], grad)
             return u
 
         F["grad"].zero_()

@@ -3,6 +3,7 @@
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
                                [--term-pde] [--term-nd] [--term-mixed] [--causal M,EPS]
+                               [--system {gray_scott,navier_stokes}]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -34,6 +35,13 @@ sweep around `pinn_term_residual_axes` (the launch along y on the layer-major en
 along e_x + e_y on the set (0, 2)), M3 the 2-D Cahn-Hilliard equation written out as ten terms (four launch pairs: x on (1, 4),
 y, e_x + e_y and e_x - e_y on (0, 4)).  After the step table it times every launch of each chain on its own (device time
 between two events, the step's batch).
+
+`--system gray_scott` runs N1 and S1, `--system navier_stokes` N2 and S2: a coupled system as a `TermPDESystem` on fourier
+4x128 (output_dim = the number of fields) with 49 729 points beside the single-field step with the same stream sets — S1
+Gray-Scott in 1-D (two fields on the set (1, 2); N1 is one such field), S2 incompressible Navier-Stokes in 2-D ((u, v, p): two
+fields on (1, 2) + (0, 2) along y, the pressure on (1, 1) + (0, 1); N2 is one field on (1, 2) + (0, 2)).  Every field is a
+component launch on the layer-major engine, which recomputes the trunk.  After the step table it times every launch of the
+system's chain on its own, `pinn_term_residual_system` among them.
 
 `--causal M,EPS` turns on the causal (time-weighted) residual loss (`training.causal_weighting`: M time bins, sharpness
 EPS): the autograd mode builds the weighted loss with torch ops on the residual tensor, the other two run the residual part
@@ -106,8 +114,35 @@ def _mixed_2d(which):
     return f"{label} as TermPDEMixed, fourier 4x128", net, P.TermPDEMixed(pc, terms, ic), 49729
 
 
+GRAY_SCOTT = [[(1.0, ("u_t",)), ((-1.0, "Du"), ("u_xx",)), (1.0, ("u", "v", "v")), ((-1.0, "F"), ()), ((1.0, "F"), ("u",))],
+              [(1.0, ("v_t",)), ((-1.0, "Dv"), ("v_xx",)), (-1.0, ("u", "v", "v")), ((1.0, "Fk"), ("v",))]]
+NAVIER_STOKES = [
+    [(1.0, ("u_t",)), (1.0, ("u", "u_x")), (1.0, ("v", "u_y")), (1.0, ("p_x",)), ((-1.0, "nu"), ("u_xx",)), ((-1.0, "nu"), ("u_yy",))],
+    [(1.0, ("v_t",)), (1.0, ("u", "v_x")), (1.0, ("v", "v_y")), (1.0, ("p_y",)), ((-1.0, "nu"), ("v_xx",)), ((-1.0, "nu"), ("v_yy",))],
+    [(1.0, ("u_x",)), (1.0, ("v_y",))]]
+
+
+def _system(which):
+    """Coupled systems as `TermPDESystem` on fourier 4x128 with one output per field, 49 729 points."""
+    if which == "gray_scott":
+        fields, eqs, dim, label = ("u", "v"), GRAY_SCOTT, 1, "Gray-Scott 1D (u, v)"
+        bcs, ic, icf = {"periodic": {}}, (lambda x: torch.stack([1 - 0.5 * torch.exp(-50 * (x[:, 0] - 0.5) ** 2),
+                                                                   0.25 * torch.exp(-50 * (x[:, 0] - 0.5) ** 2)], 1)), None
+    else:
+        fields, eqs, dim, label = ("u", "v", "p"), NAVIER_STOKES, 2, "Navier-Stokes 2D (u, v, p)"
+        bcs = {"dirichlet": {"type": "fixed", "value": [0.0, 0.0, None]}}
+        ic, icf = (lambda x: torch.stack([torch.sin(math.pi * x[:, 0]) * torch.sin(math.pi * x[:, 1]),
+                                          torch.zeros_like(x[:, 0])], 1)), ("u", "v")
+    net = B.model("fourier", 128, 4, "tanh", input_dim=dim + 1, output_dim=len(fields))
+    pc = P.PDEConfig(name=which, domain=[(0.0, 1.0)] * dim, time_domain=(0.0, 1.0),
+                     parameters={"Du": 2e-5, "Dv": 1e-5, "F": 0.04, "Fk": 0.1, "nu": 0.01}, boundary_conditions=bcs,
+                     initial_condition={}, exact_solution={}, dimension=dim, device=B.dev)
+    return f"{label} as TermPDESystem, fourier 4x128", net, P.TermPDESystem(pc, fields, eqs, ic, initial_condition_fields=icf), 49729
+
+
 ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2),
-              "M1": lambda: _heat_nd(2), "M2": lambda: _mixed_2d("aniso"), "M3": lambda: _mixed_2d("ch")}
+              "M1": lambda: _heat_nd(2), "M2": lambda: _mixed_2d("aniso"), "M3": lambda: _mixed_2d("ch"),
+              "S1": lambda: _system("gray_scott"), "S2": lambda: _system("navier_stokes")}
 
 
 def build(tag, adaptive="none", smoothness=0.0, term_pde=False, causal=None):
@@ -287,6 +322,43 @@ def time_nd_launches(tag, iters=20):
         print(f"| {label} | {a.elapsed_time(b) / iters:.4f} |", flush=True)
 
 
+def time_system_launches(tag, iters=20):
+    """Device time of every launch of a system's chain on its own: one component jet launch per (field, axis) forward, the
+    element-wise residuals of all equations, one component reverse sweep per block."""
+    torch.manual_seed(0)
+    name, net, eq, n_req = ND_CONFIGS[tag]()
+    x, t = eq._sample_uniform(n_req)
+    prog, td = net.program(), eq._pde_desc()
+    n = int(x.shape[0])
+    flat, s = E.new_flat_grad(prog, B.dev), torch.zeros(1, device=B.dev)
+    jets = E._system_jets(prog, td, x, t)
+    _, cot = E.term_residual_system(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
+    calls = []
+    for c, a, nt, nx in td.launches():
+        who = f"field {eq.fields[c]}, axis {a}, set ({nt}, {nx})"
+        calls.append((f"pinn_jet_forward, {who}", lambda c=c, a=a, nt=nt, nx=nx: E.jets_forward(prog, x, t, nt, nx, axis=a, component=c)))
+        calls.append((f"pinn_jet_backward, {who}",
+                      lambda c=c, a=a, nt=nt, nx=nx: E.jets_backward(prog, x, t, nt, nx, cot[3 * c + a], flat, axis=a, component=c)))
+    calls.append(("pinn_term_residual_system (loss sum + cotangents, two launches)",
+                  lambda: E.term_residual_system(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
+    calls.append(("pinn_term_residual_system (residuals only, one launch)", lambda: E.term_residual_system(td, jets, x, t)))
+    calls.append(("the chain through engine.residual_loss_grad", lambda: E.residual_loss_grad(prog, td, x, t, 1.0 / n, flat, loss_sum=s)))
+    print()
+    print(f"| {tag} launch ({n} points) | ms |")
+    print("|---|---|")
+    for label, fn in calls:
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        print(f"| {label} | {a.elapsed_time(b) / iters:.4f} |", flush=True)
+
+
 def time_causal_launches(tag, causal, iters=20):
     """Device time of the launches of the causal chain, each on its own, and of the one fused launch they replace."""
     torch.manual_seed(0)
@@ -341,7 +413,11 @@ def main():
     ap.add_argument("--term-nd", action="store_true", help="N1, N2: the heat Laplacian in 1-D (TermPDE) and 2-D (TermPDEnD), fourier 4x128")
     ap.add_argument("--term-mixed", action="store_true",
                     help="M1, M2, M3: 2-D heat (TermPDEnD), anisotropic diffusion and Cahn-Hilliard (TermPDEMixed), fourier 4x128")
+    ap.add_argument("--system", choices=["gray_scott", "navier_stokes"], default=None,
+                    help="N1, S1 (gray_scott) or N2, S2 (navier_stokes): a TermPDESystem beside the single-field step, fourier 4x128")
     args = ap.parse_args()
+    if args.system and args.configs == "C1,C2,C3,C4":
+        args.configs = "N1,S1" if args.system == "gray_scott" else "N2,S2"
     if args.term_nd and args.configs == "C1,C2,C3,C4":
         args.configs = "N1,N2"
     if args.term_mixed and args.configs == "C1,C2,C3,C4":
@@ -403,6 +479,10 @@ def main():
         if args.term_pde and tag == "C2":
             time_term_launches(tag)
         if args.term_mixed and tag in ND_CONFIGS:
+            time_nd_launches(tag)
+        if args.system and tag in ("S1", "S2"):
+            time_system_launches(tag)
+        if args.system and tag == "N2":
             time_nd_launches(tag)
         if causal is not None and not args.term_pde:
             time_causal_launches(tag, causal)
