@@ -527,8 +527,50 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   if constexpr (MRG && COEF) pcl[tid] = 0.0f;
 
   float xr[kMaxDin] = {0.0f, 0.0f, 0.0f, 0.0f};
+  // Merged units: one value per lane of wave 0 instead, coordinate tid >> 4 of point tid & 15 (kMaxDin kU = 64 lanes), and
+  // a fetch is one unconditional load with no wait behind it.  The address is selected arithmetically between x and t; a
+  // lane without a coordinate (past din, or a point past the end) loads t[0].  xv holds the raw word: whether it counts
+  // is decided again at its store (mput), so that nothing uses the loaded register before then.  x may be null when
+  // din == 1: no lane selects it then.  Lane indices come from an opaque copy of tid: nothing is held across the unit loop.
+  [[maybe_unused]] float xv = 0.0f;
+  static_assert(kMaxDin * kU == 64, "the merged units' coordinate lanes are wave 0");
+  auto mfetch = [&](long long p, bool ok) {  // wave 0; p, ok: the lane's point and whether it exists
+    const int cc = u16_opaque(tid) >> 4;
+    const bool live = ok && cc < din;
+    const bool space = live && cc < din - 1;
+    unsigned long long bx = reinterpret_cast<unsigned long long>(a.x), bt = reinterpret_cast<unsigned long long>(a.t);
+    // both pointers in scalar registers: left to itself the optimizer selects between the two kernel-argument slots per
+    // lane and reads the pointer with a vector load, a second round trip ahead of the coordinate's
+    asm volatile("" : "+s"(bx), "+s"(bt));
+    // index p (din - 1) + cc into x, p into t, 0 for a lane without a coordinate: one multiply-add, no branch
+    const long long idx = p * (space ? din - 1 : live ? 1 : 0) + (space ? cc : 0);
+    // (a global pointer: formed from an integer it would otherwise be a flat one, whose load also counts in lgkmcnt)
+    using gfloat = const float __attribute__((address_space(1)));
+    xv = *(gfloat*)(bt + (space ? bx - bt : 0ull) + 4ull * static_cast<unsigned long long>(idx));
+  };
+  auto mput = [&](float* dst, bool ok) {  // dst[cc kU + point]
+    const int to = u16_opaque(tid);
+    dst[to] = ok && (to >> 4) < din ? xv : 0.0f;
+  };
+  auto unit_point = [&](long long u, bool& ok) -> long long {
+    const long long p = u * kU + (u16_opaque(tid) & 15);
+    ok = u < nunits && p < NL;
+    return p;
+  };
+  auto at_point = [&](long long p0, int npts, bool& ok) -> long long {
+    const int n = u16_opaque(tid) & 15;
+    ok = n < npts && p0 + n < a.N;
+    return p0 + n;
+  };
+  // u: the unit whose coordinates are requested; merged units store those of unit us (requested earlier)
   auto fetch_coords = [&](long long u) {
-    if (tid < kU) {
+    if constexpr (MRG) {
+      if (wv == 0) {
+        bool ok;
+        const long long p = unit_point(u, ok);
+        mfetch(p, ok);
+      }
+    } else if (tid < kU) {
       const long long p = u * kU + tid;
       const bool ok = u < nunits && p < NL;
 #pragma unroll
@@ -539,7 +581,13 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     }
   };
   auto fetch_coords_at = [&](long long p0, int npts) {  // points p0 .. p0 + npts - 1 (npts <= kU)
-    if (tid < kU) {
+    if constexpr (MRG) {
+      if (wv == 0) {
+        bool ok;
+        const long long p = at_point(p0, npts, ok);
+        mfetch(p, ok);
+      }
+    } else if (tid < kU) {
       const long long p = p0 + tid;
       const bool ok = tid < npts && p < a.N;
 #pragma unroll
@@ -549,20 +597,51 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       }
     }
   };
-  auto put_coords = [&](float* dst) {
+  auto put_xr = [&](float* dst) {  // the other units: what the last fetch left in xr
     if (tid < kU) {
 #pragma unroll
       for (int cc = 0; cc < kMaxDin; ++cc) dst[cc * kU + tid] = xr[cc];
     }
   };
+  auto put_coords = [&](float* dst, [[maybe_unused]] long long us) {  // of unit us
+    if constexpr (MRG) {
+      if (wv == 0) {
+        bool ok;
+        unit_point(us, ok);
+        mput(dst, ok);
+      }
+    } else {
+      put_xr(dst);
+    }
+  };
+  auto put_coords_at = [&](float* dst, [[maybe_unused]] long long p0, [[maybe_unused]] int npts) {  // of fetch_coords_at
+    if constexpr (MRG) {
+      if (wv == 0) {
+        bool ok;
+        at_point(p0, npts, ok);
+        mput(dst, ok);
+      }
+    } else {
+      put_xr(dst);
+    }
+  };
 #if PINN_U16_PACK
   if (a.u16_tail_groups > 0) {  // the packed round's coordinates: visible long before the round's first barrier
-    fetch_coords_at(a.u16_loop_points + 4LL * a.u16_tail_groups * blockIdx.x, 4 * a.u16_tail_groups);
-    put_coords(xint);
+    const long long tp0 = a.u16_loop_points + 4LL * a.u16_tail_groups * blockIdx.x;
+    fetch_coords_at(tp0, 4 * a.u16_tail_groups);
+    put_coords_at(xint, tp0, 4 * a.u16_tail_groups);
   }
 #endif
   fetch_coords(blockIdx.x);
-  put_coords(xin2);
+  put_coords(xin2, blockIdx.x);
+  // Merged units: xv holds the coordinates of the workgroup's next unit from here on.  Unit u stores them behind its
+  // first GEMM (as every unit does) and requests those of the unit after next behind its LAST forward GEMM.  vmcnt counts
+  // in order, so the first vmcnt wait behind a request waits for the cold load as well, whatever it was written for.
+  // Behind the last forward GEMM no weight request follows in the forward sweep; in the compiled kernel the first such
+  // wait is one the compiler places behind the output layer's barrier (it guards registers of earlier weight requests),
+  // so the load has the last layer's jets, the output layer and that barrier to land.  That is not quite enough: about
+  // 350 cycles per unit stay exposed on wave 0, against 2 000 at the unit top (profiles/r10_wave0_chains.md).
+  if constexpr (MRG) fetch_coords(blockIdx.x + gridDim.x);
   int xpar = 0;
 
   for (long long u = blockIdx.x; u < nunits; u += gridDim.x) {
@@ -573,7 +652,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     const float* xin = xin2 + xpar * (kMaxDin * kU);
     float* xin_next = xin2 + (xpar ^ 1) * (kMaxDin * kU);
     xpar ^= 1;
-    fetch_coords(u + gridDim.x);
+    if constexpr (!MRG) fetch_coords(u + gridDim.x);
     f32x4 w0, w1;  // first two weight blocks of the next GEMM, requested a phase ahead
     {
       const LayerDev L0 = uniform_layer(net.layer[0]);
@@ -604,7 +683,13 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         u16_gemm<K, false>(acc, Ly.W, Ly.ld, u16_rows_off(16 * wv, Ly.ld, c, g), w0, w1, Ly.in_dim >> 4, src + c * kUP + 4 * g);
         acc[0] += *reinterpret_cast<const f32x4*>(wb + (1 + l) * kUH + frow);
       }
-      if (l == 0) put_coords(xin_next);  // the loads had the encoding and a GEMM to land; last read two barriers ago
+      if (l == 0) {
+        // the loads had the encoding and a GEMM to land (merged units: a whole unit); last read two barriers ago
+        put_coords(xin_next, u + gridDim.x);
+      }
+      if constexpr (MRG) {
+        if (last) fetch_coords(u + 2 * gridDim.x);  // behind the store above: xv is free
+      }
       PINN_STAMP(ST_FWD_GEMM);
       if (!last) {
         {
