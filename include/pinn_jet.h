@@ -63,6 +63,10 @@ extern "C" {
 #define PINN_FLAG_PLAIN_STREAMS 16 /* engine hint: every call of the descriptor keeps one stream per derivative where the
                                       16-point kernel would run 1-D Burgers on the merged set u, u_t - nu u_xx, u_x (A/B
                                       runs and tests; same results to rounding) */
+#define PINN_FLAG_GENERIC_UNITS 32 /* engine hint: every call of the descriptor keeps the merged units that read the network's
+                                      shape from the descriptor where the 16-point kernel would run the units with the
+                                      default shape compiled in (Fourier features 2 -> 64, three layers of 128; A/B runs and
+                                      tests; the same bits) */
 /* Space axis of a jet launch: with axis a (1 or 2) the space streams of pinn_jet_forward, pinn_jet_backward and
    pinn_jet_backward_inputs are d^k/dx_a^k, seeded from column a of x instead of column 0; the stream order stays
    [u, d/dt.., d/dx_a..].  The weight gradient and the input cotangents (every column, mixed terms included) stay exact.
@@ -339,6 +343,13 @@ int pinn_residual_loss_grad_inverse(const PinnNetDesc* net, const float* const* 
 size_t pinn_inverse_workspace_bytes(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N);
 /* "jet_kernel_u16" | "jet_kernel_wide" | "layer_major": the kernel such a call takes (as pinn_kernel_name). */
 int pinn_inverse_kernel_name(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N, char* buf, size_t len);
+/* The translation unit family of the kernel that the residual-mode calls of (net, pde) take on N points; forward-only,
+ * fused, residual-adjoint and inverse calls of a descriptor are routed together, so one answer holds for all of them:
+ * "jet_u16mf_<family>" (merged stream set, the default network's shape compiled in; the inverse call takes its
+ * jet_u16mfc_ sibling), "jet_u16m_<family>" (merged stream set, shape read from the descriptor; jet_u16mc_),
+ * "jet_u16_<nt>_<nx>_<family>" (one stream per derivative; jet_u16c_), or "jet_kernel_wide" / "layer_major" as
+ * pinn_kernel_name answers for the reverse launch.  A query: nothing is launched and no device is needed. */
+int pinn_residual_unit_name(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N, char* buf, size_t len);
 
 /* weight_grads += d(sum_n residual_cotangent[n] * r_n)/d(weights): the backward of pinn_residual_forward for an
  * arbitrary downstream graph (loss.backward() through `residual`, trainer.py:689; LRW's per-component

@@ -19,6 +19,7 @@ PINN_FLAG_DETERMINISTIC = 2
 PINN_FLAG_LAYER_MAJOR = 4
 PINN_FLAG_WIDE_TILE32 = 8
 PINN_FLAG_PLAIN_STREAMS = 16
+PINN_FLAG_GENERIC_UNITS = 32
 PINN_FLAG_SPACE_AXIS_MASK = 0x300
 
 
@@ -89,7 +90,7 @@ EXPORTS = (
     "pinn_inverse_workspace_bytes", "pinn_inverse_kernel_name", "pinn_adaptive_adam_step", "pinn_lbfgs_state_bytes",
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
-    "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system",
+    "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system", "pinn_residual_unit_name",
 )
 
 
@@ -249,6 +250,8 @@ def load():
         lib.pinn_inverse_workspace_bytes.argtypes = [P(PinnNetDesc), P(PinnPdeDesc), i64]
         lib.pinn_inverse_kernel_name.restype = ctypes.c_int
         lib.pinn_inverse_kernel_name.argtypes = [P(PinnNetDesc), P(PinnPdeDesc), i64, ctypes.c_char_p, sz]
+        lib.pinn_residual_unit_name.restype = ctypes.c_int
+        lib.pinn_residual_unit_name.argtypes = [P(PinnNetDesc), P(PinnPdeDesc), i64, ctypes.c_char_p, sz]
         lib.pinn_point_losses.restype = ctypes.c_int
         lib.pinn_point_losses.argtypes = [vp, i32, i32, P(i32), P(i32), P(vp), P(f32), i32, f32, vp, vp, vp, f32, f32, i32, vp, vp]
         lib.pinn_jet_losses.restype = ctypes.c_int
@@ -326,6 +329,15 @@ def kernel_name(prog, N: int, nt: int, nx: int, backward: int) -> str:
     reverse launches), "jet_kernel_wide" (fused tile-major, 32-point tiles) or "layer_major"."""
     buf = ctypes.create_string_buffer(64)
     check(load().pinn_kernel_name(ctypes.byref(prog.desc), int(N), int(nt), int(nx), int(backward), buf, len(buf)))
+    return buf.value.decode("ascii")
+
+
+def residual_unit_name(prog, pd, N: int) -> str:
+    """Translation unit family of the kernel that the residual-mode calls of (prog, PinnPdeDesc pd) take on N points
+    (pinn_residual_unit_name): "jet_u16mf_<family>", "jet_u16m_<family>", "jet_u16_<nt>_<nx>_<family>", "jet_kernel_wide" or
+    "layer_major"."""
+    buf = ctypes.create_string_buffer(64)
+    check(load().pinn_residual_unit_name(ctypes.byref(prog.desc), ctypes.byref(pd), int(N), buf, len(buf)))
     return buf.value.decode("ascii")
 
 

@@ -56,6 +56,13 @@ constexpr int kUWaves = 8;
 constexpr int kUH = 128;        // image height (features)
 constexpr int kUImgS = kU * kUP;  // floats per stream of an image
 
+// The shape the fixed-shape units (FIXED in the kernel) are compiled for: the default network of the package, fixed for a
+// whole training run.  jet_u16_fixed_shape() compares a NetDev with it.
+struct U16FixedShape {
+  int din, enc_out, layers, in0, width;
+};
+constexpr U16FixedShape kUFixed = {2, 64, 3, 64, 128};
+
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -87,14 +94,15 @@ __device__ __forceinline__ void u16_enc_preact(const float* ep, int din, const f
 
 // encoding into an image dst[s][n][f]; thread -> (point tid & 15, feature tid >> 4 + 32 i)
 // MRG: the merged stream set [value, w, d/dx] (jet_device.h), cc its coefficient c; NT = NX = 1 then
-template <int ACT, int NT, int NX, bool MRG = false>
+// FIXED: the fixed-shape units (kUFixed): Fourier features, 64 of them, of two coordinates
+template <int ACT, int NT, int NX, bool MRG = false, bool FIXED = false>
 __device__ __forceinline__ void u16_encode(const NetDev& net, const float* ep, const float* xin, float* dst, int tid, float cc = 0.0f) {
   constexpr int K = 1 + NT + NX;
   const int n = tid & 15;
-  const int din = net.din;
+  const int din = FIXED ? kUFixed.din : net.din;
   float* row = dst + n * kUP;
-  if (net.enc == ENC_FOURIER) {
-    const int M = net.enc_out >> 1;
+  if (FIXED || net.enc == ENC_FOURIER) {
+    const int M = FIXED ? kUFixed.enc_out >> 1 : net.enc_out >> 1;
 #pragma unroll 1
     for (int m = tid >> 4; m < M; m += kUThreads / kU) {
       float z[K], ys[K], yc[K];
@@ -424,6 +432,42 @@ __device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
   return v;
 }
 
+// Layer l of the fixed shape: compile-time sizes, W and act_param from the kernel's resident copies (fixed-shape units
+// only; the gradient pointers are read from the descriptor where the flush uses them).  scalar_sizes: the packed round's
+// form, where l is a run-time value and the sizes are scalar registers, so that the round is compiled in the shape it has
+// in the generic units (its element-wise code must contract its multiply-adds as theirs does, see the round) and only
+// the descriptor reads are gone.
+struct U16FixedLayers {  // by value, member by member: an array indexed with the packed round's run-time l would live in scratch
+  const float *W0, *W1, *W2;
+  float ap0, ap1, ap2;
+};
+__device__ __forceinline__ LayerDev u16_fixed_layer(const U16FixedLayers f, int l, bool scalar_sizes = false) {
+  LayerDev u = {};
+  u.W = l == 0 ? f.W0 : l == 1 ? f.W1 : f.W2;
+  int in_dim = l == 0 ? kUFixed.in0 : kUFixed.width, out_dim = kUFixed.width;
+  if (scalar_sizes) asm("" : "+s"(in_dim), "+s"(out_dim));
+  u.in_dim = in_dim;
+  u.out_dim = out_dim;
+  // The row stride goes through an empty asm: as a constant it is folded into per-lane 64-bit addresses of the column
+  // form's loads (u16_wload), which are hoisted out of the unit loop and spilled; as a scalar it stays in the loads'
+  // scalar base, as in the generic units.
+  int ld = u.in_dim;
+  asm("" : "+s"(ld));
+  u.ld = ld;
+  u.act_param = l == 0 ? f.ap0 : l == 1 ? f.ap1 : f.ap2;
+  return u;
+}
+// The macros below are for the body of jet_kernel_u16 alone (undefined again behind it).  They capture its names net, fix,
+// fnull and FIXED.
+// the layer descriptor as the kernel body uses it (FIXED is a constant: one arm is compiled)
+#define U16_LAYER(l) (FIXED ? u16_fixed_layer(fix, (l)) : uniform_layer(net.layer[(l)]))
+#define U16_LAYER_P(l) (FIXED ? u16_fixed_layer(fix, (l), true) : uniform_layer(net.layer[(l)]))  // the packed round's
+// whether layer l forms a weight / a bias gradient: the fixed-shape units ask the resident word fnull
+#define U16_HAS_DW(l, Ly) (FIXED ? ((fnull >> (l)) & 1u) == 0u : (Ly).dW != nullptr)
+#define U16_HAS_DB(l, Ly) (FIXED ? ((fnull >> (4 + (l))) & 1u) == 0u : (Ly).db != nullptr)
+// trip count of a layer loop: the fixed-shape units unroll it, the others keep the loop
+#define U16_LAYER_UNROLL FIXED ? kPersist : 1
+
 // NA0: 16-feature k-tiles of the first MFMA layer's weight-gradient accumulators (4: at most 64 input features)
 // BWD = false: the forward-only launch of the same networks.  It runs the forward code of the reverse launch unchanged,
 // so a forward-only call and a fused call give bit-identical per-point results.
@@ -440,9 +484,19 @@ __device__ __forceinline__ f32x4 row16_sum4(f32x4 v) {
 // the Burgers residual, K = 3.  Its coefficient c = -c_0 is read from the row pad where it is used.  The merged COEF
 // form sums dL/dc per lane in pcl (every activation element's partial, and at layer 0 the Fourier features' through one
 // more single-stream abar GEMM) and stores -sum as the cotangent of c_0 in the slab row's slot.
-template <int ACT, int NT, int NX, bool BWD, int NA0, bool COEF = false, bool MRG = false>
+//
+// FIXED = true (jet_u16mf_* / jet_u16mfc_* units, merged set only): the shape of the network is compiled in (kUFixed:
+// 64 Fourier features of two coordinates, three MFMA layers 64 -> 128 -> 128 -> 128 with ld == in_dim, head 128 -> 1).
+// The layer loops of the unit loop are unrolled with a compile-time layer, so widths, image roles, GEMM depths and tile
+// offsets are constants and no layer descriptor is read inside the unit loop: the three W pointers, the activation
+// parameters and one word that says which gradient pointers are null are read once and stay in scalar registers (the row
+// stride too: u16_fixed_layer says why it is not a literal).  The packed round keeps its loops and takes the same
+// resident values.  The arithmetic and its order are those of the generic merged unit, which the same descriptor takes
+// with PINN_FLAG_GENERIC_UNITS.
+template <int ACT, int NT, int NX, bool BWD, int NA0, bool COEF = false, bool MRG = false, bool FIXED = false>
 __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs a) {
   static_assert(!MRG || (NT == 1 && NX == 1), "the merged set is laid out as the (1,1) set");
+  static_assert(!FIXED || (MRG && NA0 == kUFixed.in0 / 16), "the fixed shape is a merged unit's");
   constexpr int K = 1 + NT + NX;
   constexpr int NKT = kUH / 16;
   constexpr int NPT = NA0 + (kPersist - 1) * NKT;
@@ -483,8 +537,8 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
   const int g = lane >> 4, c = lane & 15;
-  const int din = net.din;
-  const int nl = net.n_layers;
+  const int din = FIXED ? kUFixed.din : net.din;
+  const int nl = FIXED ? kUFixed.layers : net.n_layers;
   // The unit loop's points: a.N, or the whole rounds only when a packed round follows (every unit of the loop is then
   // full).  The loop knows no other point count: one more scalar held across it costs the reverse kernel scratch.
 #if PINN_U16_PACK
@@ -642,6 +696,27 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   // so the load has the last layer's jets, the output layer and that barrier to land.  That is not quite enough: about
   // 350 cycles per unit stay exposed on wave 0, against 2 000 at the unit top (profiles/r10_wave0_chains.md).
   if constexpr (MRG) fetch_coords(blockIdx.x + gridDim.x);
+  // Fixed-shape units: what the unit loop and the packed round need of the layer table, read here once.  The values go
+  // through an empty asm so that they are kept in scalar registers instead of being read again at every use.
+  [[maybe_unused]] U16FixedLayers fix = {};
+  [[maybe_unused]] unsigned fnull = 0u;  // bit l: layer l has no dW, bit 4 + l: no db
+  if constexpr (FIXED) {
+    auto resident_w = [&](int l) -> const float* {
+      unsigned long long wp = reinterpret_cast<unsigned long long>(net.layer[l].W);
+      asm("" : "+s"(wp));
+      using gfloat = const float __attribute__((address_space(1)));
+      return (const float*)(gfloat*)wp;
+    };
+    auto resident_ap = [&](int l) -> float {
+      unsigned ap = __float_as_uint(net.layer[l].act_param);
+      asm("" : "+s"(ap));
+      return __uint_as_float(ap);
+    };
+    fix = {resident_w(0), resident_w(1), resident_w(2), resident_ap(0), resident_ap(1), resident_ap(2)};
+#pragma unroll
+    for (int l = 0; l < kPersist; ++l) fnull |= (net.layer[l].dW ? 0u : 1u << l) | (net.layer[l].db ? 0u : 16u << l);
+    asm("" : "+s"(fnull));
+  }
   int xpar = 0;
 
   for (long long u = blockIdx.x; u < nunits; u += gridDim.x) {
@@ -655,7 +730,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     if constexpr (!MRG) fetch_coords(u + gridDim.x);
     f32x4 w0, w1;  // first two weight blocks of the next GEMM, requested a phase ahead
     {
-      const LayerDev L0 = uniform_layer(net.layer[0]);
+      const LayerDev L0 = U16_LAYER(0);
       const unsigned off = u16_rows_off(16 * wv < L0.out_dim ? 16 * wv : 0, L0.ld, c, g);
       w0 = u16_wload<false>(L0.W, L0.ld, off, 0);
       w1 = u16_wload<false>(L0.W, L0.ld, off, L0.in_dim > 16 ? 1 : 0);
@@ -668,14 +743,15 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     // layer's record in S; their reverse sweep reads the activations where the forward sweep left them.
     float* src = (MRG || (nl & 1)) ? X : A2;
     float* dst = (MRG || (nl & 1)) ? A2 : X;
-    u16_encode<ACT, NT, NX, MRG>(net, ep, xin, src, u16_opaque(tid), mcoef());  // opaque: addresses formed here, not held over the loop
+    u16_encode<ACT, NT, NX, MRG, FIXED>(net, ep, xin, src, u16_opaque(tid), mcoef());  // opaque: addresses formed here, not held over the loop
     U16_BARRIER(ST_ENCODE);
 
     // ---- hidden layers ----
     f32x4 acc[K];
+#pragma unroll U16_LAYER_UNROLL
     for (int l = 0; l < nl; ++l) {
-      const LayerDev Ly = uniform_layer(net.layer[l]);
-      const bool on = 16 * wv < Ly.out_dim;
+      const LayerDev Ly = U16_LAYER(l);
+      const bool on = FIXED || 16 * wv < Ly.out_dim;
       const bool last = l + 1 == nl;
 #pragma unroll
       for (int s = 0; s < K; ++s) acc[s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -693,7 +769,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       PINN_STAMP(ST_FWD_GEMM);
       if (!last) {
         {
-          const LayerDev Ln = uniform_layer(net.layer[l + 1]);
+          const LayerDev Ln = U16_LAYER(l + 1);
           const unsigned off = u16_rows_off(16 * wv < Ln.out_dim ? 16 * wv : 0, Ln.ld, c, g);
           w0 = u16_wload<false>(Ln.W, Ln.ld, off, 0);  // latency hides under the jets
           w1 = u16_wload<false>(Ln.W, Ln.ld, off, Ln.in_dim > 16 ? 1 : 0);
@@ -748,7 +824,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         for (int w = 0; w < kUWaves; ++w) v += UP[(w * K + s) * kU + c];
         j[s] = v;
       }
-      if (a.mode == MODE_JETS) {
+      if (!FIXED && a.mode == MODE_JETS) {
 #pragma unroll
         for (int s = 0; s < K; ++s) {
           if (writer && ok && a.jets_out[s]) a.jets_out[s][p] = j[s];
@@ -792,7 +868,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     if (tid < kU) psl[kU + c] += ub[0];
     f32x4 ab[K];
     {
-      const LayerDev Lz = uniform_layer(net.layer[nl - 1]);
+      const LayerDev Lz = U16_LAYER(nl - 1);
       const f32x4 w4 = *reinterpret_cast<const f32x4*>(wb + frow);
 #pragma unroll
       for (int s = 0; s < K; ++s) ab[s] = w4 * ub[s];
@@ -825,10 +901,11 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     }
     PINN_STAMP(ST_B0);
 
+#pragma unroll U16_LAYER_UNROLL
     for (int l = nl - 1; l >= 0; --l) {
-      const LayerDev Ly = uniform_layer(net.layer[l]);
-      const bool on = 16 * wv < Ly.out_dim;
-      const bool need_abar = l > 0 || net.enc == ENC_LINEAR;
+      const LayerDev Ly = U16_LAYER(l);
+      const bool on = FIXED || 16 * wv < Ly.out_dim;
+      const bool need_abar = l > 0 || (!FIXED && net.enc == ENC_LINEAR);
       const bool kon = 16 * wv < Ly.in_dim;  // this wave owns input-feature rows of the layer
       // the GEMMs of layer l+1 have finished reading X (zbar) and A2; with a single MFMA layer the barrier keeps
       // u16_encode (all columns of A2, below) from overwriting another wave's parked record before its B0 has read it
@@ -843,9 +920,9 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       const float* const AP = !KEEP || (l & 1) ? A2 : X;
       float pw = 0.0f;  // act_param of layer l-1
       if constexpr (KEEP) {
-        if (l > 0) pw = uniform_layer(net.layer[l - 1]).act_param;
+        if (l > 0) pw = U16_LAYER(l - 1).act_param;
       } else if (l > 0) {
-        const LayerDev P = uniform_layer(net.layer[l - 1]);
+        const LayerDev P = U16_LAYER(l - 1);
         pw = P.act_param;
         if (kon) {  // replay a_{l-1} from its record into this wave's columns of A2
           f32x4 rec[K], y[K];
@@ -862,7 +939,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           u16_put<K>(A2 + ioff, y);
         }
       } else {
-        u16_encode<ACT, NT, NX, MRG>(net, ep, xin, A2, u16_opaque(tid), mcoef());
+        u16_encode<ACT, NT, NX, MRG, FIXED>(net, ep, xin, A2, u16_opaque(tid), mcoef());
       }
       const unsigned coff = u16_cols_off(kon ? 16 * wv : 0, Ly.ld, c, g);
       if (need_abar) {  // requests hide under the barrier
@@ -870,7 +947,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         w1 = u16_wload<true>(Ly.W, Ly.ld, coff, 1);
       }
       U16_BARRIER(ST_BWD_PUT);
-      if (Ly.db && tid < Ly.out_dim) {
+      if (U16_HAS_DB(l, Ly) && tid < Ly.out_dim) {
         float gsum = 0.0f;
 #pragma unroll
         for (int n = 0; n < kU; ++n) gsum += ZB[n * kUP + tid];
@@ -886,7 +963,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         // dW (persistent tiles): first for waves 4-7, last for waves 0-3
-        if ((half == 0) == dw_first && on && Ly.dW) {
+        if ((half == 0) == dw_first && on && U16_HAS_DW(l, Ly)) {
           const float* zl = ZB + 4 * g * kUP + 16 * wv + c;
           const float* al = AP + 4 * g * kUP + c;
           const int na = Ly.in_dim >> 4;
@@ -916,14 +993,14 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         // Three MFMA layers: a_1 has taken the encoding's place in X.  dW_2 was X's last reader (a barrier ago), dW_0
         // reads the encoding behind the next barrier: it is formed again here, beside the partner wave's GEMMs.
         if (l == 1 && nl > 2) {
-          u16_encode<ACT, NT, NX, MRG>(net, ep, xin, X, u16_opaque(tid), mcoef());
+          u16_encode<ACT, NT, NX, MRG, FIXED>(net, ep, xin, X, u16_opaque(tid), mcoef());
           PINN_STAMP(ST_ENCODE);
         }
       }
       if constexpr (MRG && COEF) {
         // Fourier features depend on c through their w stream: dL/dc += sum_j abar_w,j e_j with e_j = -b_x^2 (value
         // feature j).  abar_w = W0^T zbar_w is one single-stream GEMM; the value features are stream 0 of the encoding.
-        if (l == 0 && net.enc == ENC_FOURIER && kon) {
+        if (l == 0 && (FIXED || net.enc == ENC_FOURIER) && kon) {
           f32x4 aw[1] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
           {  // a rolled loop: the unrolled, prefetching form of u16_gemm_n costs this unit scratch
             const float* xl = ZB + kUImgS + c * kUP + 4 * g;
@@ -936,7 +1013,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
               for (int m = 0; m < 4; ++m) aw[0] = mfma16(w[m], xv[m], aw[0]);
             }
           }
-          const int M = net.enc_out >> 1;
+          const int M = FIXED ? kUFixed.enc_out >> 1 : net.enc_out >> 1;
           const f32x4 val = *reinterpret_cast<const f32x4*>(AP + ioff);
           float part = 0.0f;
 #pragma unroll
@@ -950,7 +1027,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     }
 
     // ---- encoding backward (first Linear of feedforward / SIREN) ----
-    if (net.enc == ENC_LINEAR && (net.d_encW || (MRG && COEF))) {
+    if (!FIXED && net.enc == ENC_LINEAR && (net.d_encW || (MRG && COEF))) {
       const int H = net.enc_out;
       // merged COEF units run the adjoint for its coefficient partials even without a first-Linear gradient to form
       const bool enc_sums = !(MRG && COEF) || net.d_encW != nullptr;
@@ -1000,6 +1077,9 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   // 4j + (c & 3), all streams.  The four lanes c >> 2 = 0 .. 3 of a point then run the unit's element-wise code on
   // the same values and store the same words.  Nothing here is live across the unit loop besides pt[] and the
   // running sums in LDS: addresses come from an opaque copy of the thread index.
+  // The fixed-shape units keep the round's layer loops rolled, with the sizes in scalar registers (U16_LAYER_P): unrolled
+  // with compile-time sizes the compiler contracted the round's jets differently, and some of its points rounded to
+  // other bits than in the generic units (the unit loop's did not).  The round is a quarter unit once per launch.
   if (a.u16_tail_groups > 0) {
     const int G = a.u16_tail_groups;
     const int tp = u16_opaque(tid);
@@ -1024,7 +1104,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     const float* xin = xint;
     f32x4 w0, w1;
     {
-      const LayerDev L0 = uniform_layer(net.layer[0]);
+      const LayerDev L0 = U16_LAYER_P(0);
       const unsigned off = u16_rows_off(16 * wv < L0.out_dim ? 16 * wv : 0, L0.ld, cp, gp);
       w0 = u16_wload<false>(L0.W, L0.ld, off, 0);
       w1 = u16_wload<false>(L0.W, L0.ld, off, L0.in_dim > 16 ? 1 : 0);
@@ -1032,12 +1112,13 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     PINN_STAMP(ST_STAGE);
     float* src = (nl & 1) ? X : A2;
     float* dst = (nl & 1) ? A2 : X;
-    u16_encode<ACT, NT, NX, MRG>(net, ep, xin, src, tp, mcoef());
+    u16_encode<ACT, NT, NX, MRG, FIXED>(net, ep, xin, src, tp, mcoef());
     U16_BARRIER(ST_ENCODE);
 
     // ---- hidden layers; the last one leaves its output-layer partials in UP ----
+#pragma unroll 1
     for (int l = 0; l < nl; ++l) {
-      const LayerDev Ly = uniform_layer(net.layer[l]);
+      const LayerDev Ly = U16_LAYER_P(l);
       const bool on = 16 * wv < Ly.out_dim;
       const bool last = l + 1 == nl;
       f32x4 pa[kUPackMax];
@@ -1046,7 +1127,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       if (on) u16p_gemm<false>(pa, G, Ly.W, Ly.ld, u16_rows_off(16 * wv, Ly.ld, cp, gp), w0, w1, Ly.in_dim >> 4, src + boff);
       PINN_STAMP(ST_FWD_GEMM);
       if (!last) {
-        const LayerDev Ln = uniform_layer(net.layer[l + 1]);
+        const LayerDev Ln = U16_LAYER_P(l + 1);
         const unsigned off = u16_rows_off(16 * wv < Ln.out_dim ? 16 * wv : 0, Ln.ld, cp, gp);
         w0 = u16_wload<false>(Ln.W, Ln.ld, off, 0);
         w1 = u16_wload<false>(Ln.W, Ln.ld, off, Ln.in_dim > 16 ? 1 : 0);
@@ -1124,7 +1205,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           for (int w = 0; w < kUWaves; ++w) v += UP[(w * K + s) * kU + pp];
           j[s] = v;
         }
-        if (a.mode == MODE_JETS) {
+        if (!FIXED && a.mode == MODE_JETS) {
 #pragma unroll
           for (int s = 0; s < K; ++s) {
             if (writer && ok && a.jets_out[s]) a.jets_out[s][p] = j[s];
@@ -1167,7 +1248,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       if (writer) psl[kU + pp] += ub[0];
       f32x4 ab[K];
       {
-        const LayerDev Lz = uniform_layer(net.layer[nl - 1]);
+        const LayerDev Lz = U16_LAYER_P(nl - 1);
         const f32x4 w4 = *reinterpret_cast<const f32x4*>(wb + frowp);
 #pragma unroll
         for (int s = 0; s < K; ++s) ab[s] = w4 * ub[s];
@@ -1199,10 +1280,11 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     }
 
     if constexpr (BWD) {
+#pragma unroll 1
       for (int l = nl - 1; l >= 0; --l) {
-        const LayerDev Ly = uniform_layer(net.layer[l]);
+        const LayerDev Ly = U16_LAYER_P(l);
         const bool on = 16 * wv < Ly.out_dim;
-        const bool need_abar = l > 0 || net.enc == ENC_LINEAR;
+        const bool need_abar = l > 0 || (!FIXED && net.enc == ENC_LINEAR);
         const bool kon = 16 * wv < Ly.in_dim;
         // zbar_l goes from where it was parked into this wave's columns of X.  The last layer's (the first here) was
         // parked in A2 and X's columns have been free since the output layer's barrier, so it moves BEFORE the barrier
@@ -1226,7 +1308,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         float pw = 0.0f;
         u16_wave_sync();  // this wave's parked words are read before its replay below overwrites them (top layer: A2)
         if (l > 0) {
-          const LayerDev P = uniform_layer(net.layer[l - 1]);
+          const LayerDev P = U16_LAYER_P(l - 1);
           pw = P.act_param;
           if (kon) {  // replay a_{l-1} into this wave's columns of A2
 #pragma unroll
@@ -1248,7 +1330,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
             }
           }
         } else {
-          u16_encode<ACT, NT, NX, MRG>(net, ep, xin, A2, tp, mcoef());
+          u16_encode<ACT, NT, NX, MRG, FIXED>(net, ep, xin, A2, tp, mcoef());
         }
         const unsigned coff = u16_cols_off(kon ? 16 * wv : 0, Ly.ld, cp, gp);
         if (need_abar) {
@@ -1256,7 +1338,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           w1 = u16_wload<true>(Ly.W, Ly.ld, coff, 1);
         }
         U16_BARRIER(ST_BWD_PUT);
-        if (Ly.db && tp < Ly.out_dim) {
+        if (U16_HAS_DB(l, Ly) && tp < Ly.out_dim) {
           float gsum = 0.0f;
           for (int n = 0; n < 4 * G; ++n) gsum += X[n * kUP + tp];
           pl[l * kUH + tp] += gsum;
@@ -1297,7 +1379,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
           park = xch;
           PINN_STAMP(ST_BWD_EW);
         }
-        if (on && Ly.dW) {
+        if (on && U16_HAS_DW(l, Ly)) {
           const float* zl = X + gp * kUP + 16 * wv + cp;
           const float* al = A2 + gp * kUP + cp;
           const int na = Ly.in_dim >> 4;
@@ -1307,13 +1389,13 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
         }
         PINN_STAMP(ST_BWD_STREAM);
         if constexpr (MRG && COEF) {  // the Fourier features' coefficient partial, as in a unit: the lanes of the w columns
-          if (l == 0 && net.enc == ENC_FOURIER && kon) {
+          if (l == 0 && (FIXED || net.enc == ENC_FOURIER) && kon) {
             f32x4 pa[kUPackMax];
 #pragma unroll
             for (int j = 0; j < kUPackMax; ++j) pa[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             u16p_gemm<true>(pa, G, Ly.W, Ly.ld, coff, u16_wload<true>(Ly.W, Ly.ld, coff, 0), u16_wload<true>(Ly.W, Ly.ld, coff, 1),
                             Ly.out_dim >> 4, X + boff);
-            const int M = net.enc_out >> 1;
+            const int M = FIXED ? kUFixed.enc_out >> 1 : net.enc_out >> 1;
             float part = 0.0f;
 #pragma unroll
             for (int j = 0; j < kUPackMax; ++j) {
@@ -1332,7 +1414,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
       }
 
       // ---- encoding backward (first Linear of feedforward / SIREN) ----
-      if (net.enc == ENC_LINEAR && (net.d_encW || (MRG && COEF))) {
+      if (!FIXED && net.enc == ENC_LINEAR && (net.d_encW || (MRG && COEF))) {
         const int H = net.enc_out;
         const bool enc_sums = !(MRG && COEF) || net.d_encW != nullptr;
         U16_BARRIER(ST_ENC_BWD);
@@ -1437,7 +1519,7 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
     for (int o = 8; o > 0; o >>= 1) gsum += __shfl_xor(gsum, o);
     if (tf == 0) net.db_out[doff] = gsum;
   }
-  if (net.enc == ENC_LINEAR && net.d_encW && tf < net.enc_out) {
+  if (!FIXED && net.enc == ENC_LINEAR && net.d_encW && tf < net.enc_out) {
 #pragma unroll
     for (int cc = 0; cc < kMaxDin; ++cc)
       if (cc < din) net.d_encW[doff + tf * din + cc] = pl[(kPersist + cc) * kUH + tf];
@@ -1448,7 +1530,11 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
 #pragma unroll
   for (int p = 0; p < kPersist; ++p) {
     if (p < nl) {
-      const LayerDev Lp = uniform_layer(net.layer[p]);
+      LayerDev Lp = U16_LAYER(p);
+      if constexpr (FIXED) {  // the gradient pointers are read here, where they are used
+        Lp.dW = uniform_ptr(net.layer[p].dW);
+        Lp.db = uniform_ptr(net.layer[p].db);
+      }
       if (Lp.db && tf < Lp.out_dim) Lp.db[doff + tf] = pl[p * kUH + tf];
       if (16 * wv >= Lp.out_dim) continue;
       if (Lp.dW) {
@@ -1470,6 +1556,12 @@ __global__ __launch_bounds__(kUThreads, 1) void jet_kernel_u16(const KernelArgs 
   write_stamps();
 #endif
 }
+
+#undef U16_LAYER
+#undef U16_LAYER_P
+#undef U16_HAS_DW
+#undef U16_HAS_DB
+#undef U16_LAYER_UNROLL
 
 // The launch plan (host).  With grid workgroups, R = N / (16 grid) full rounds of 16-point units and M = N - 16 grid R
 // points left, G = ceil(M / (4 grid)) <= 4 four-point groups per workgroup hold them.  G = 1..3 (and a unit compiled with
@@ -1547,18 +1639,31 @@ hipError_t launch_jet_u16_coef(const KernelArgs& a, int grid, hipStream_t stream
   return hipGetLastError();
 }
 
-// the merged units (MRG = true): forward-only / reverse, and the COEF reverse launch
-template <int ACT>
+// The network has the shape the fixed-shape units are compiled for (kUFixed); every other network that fits the 16-point
+// kernel keeps the generic units: other widths, two or one MFMA layers, another feature count, a first-Linear encoding,
+// a layer that is a column-chunk view (ld != in_dim).
+inline bool jet_u16_fixed_shape(const NetDev& n) {
+  if (n.enc != ENC_FOURIER || n.din != kUFixed.din || n.enc_out != kUFixed.enc_out || n.n_layers != kUFixed.layers) return false;
+  if (n.h_last != kUFixed.width) return false;
+  for (int l = 0; l < kUFixed.layers; ++l) {
+    const int in = l == 0 ? kUFixed.in0 : kUFixed.width;
+    if (n.layer[l].in_dim != in || n.layer[l].out_dim != kUFixed.width || n.layer[l].ld != in) return false;
+  }
+  return true;
+}
+
+// the merged units (MRG = true): forward-only / reverse, and the COEF reverse launch; FIXED: the fixed-shape units
+template <int ACT, bool FIXED = false>
 hipError_t launch_jet_u16m_act(const KernelArgs& a, bool bwd, int grid, hipStream_t stream) {
-  auto kern = bwd ? jet_kernel_u16<ACT, 1, 1, true, 4, false, true> : jet_kernel_u16<ACT, 1, 1, false, 4, false, true>;
+  auto kern = bwd ? jet_kernel_u16<ACT, 1, 1, true, 4, false, true, FIXED> : jet_kernel_u16<ACT, 1, 1, false, 4, false, true, FIXED>;
   hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(false, bwd), stream, a);
   return hipGetLastError();
 }
-template <int ACT>
+template <int ACT, bool FIXED = false>
 hipError_t launch_jet_u16m_coef(const KernelArgs& a, int grid, hipStream_t stream) {
-  auto kern = jet_kernel_u16<ACT, 1, 1, true, 4, true, true>;
+  auto kern = jet_kernel_u16<ACT, 1, 1, true, 4, true, true, FIXED>;
   hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kUThreads), jet_u16m_lds_bytes(true, true), stream, a);

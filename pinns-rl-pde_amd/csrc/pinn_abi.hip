@@ -57,13 +57,18 @@ PINN_DECLC(uc, 2, 0)
 #undef PINN_DECLC1
 #endif
 
-/* merged stream set (Burgers on three streams): jet_u16m_<family>, jet_u16mc_<family> */
+/* merged stream set (Burgers on three streams): jet_u16m_<family>, jet_u16mc_<family>; with the network's shape compiled
+   in: jet_u16mf_<family>, jet_u16mfc_<family> */
 #if !defined(PINN_DEV)
 #define PINN_DECLM(a) hipError_t launch_jetum_a##a(const KernelArgs&, bool, int, hipStream_t); hipError_t launch_jetumc_a##a(const KernelArgs&, int, hipStream_t);
+#define PINN_DECLF(a) hipError_t launch_jetumf_a##a(const KernelArgs&, bool, int, hipStream_t); hipError_t launch_jetumfc_a##a(const KernelArgs&, int, hipStream_t);
 PINN_DECLM(0) PINN_DECLM(1) PINN_DECLM(2) PINN_DECLM(3) PINN_DECLM(4)
+PINN_DECLF(0) PINN_DECLF(2) PINN_DECLF(4) /* csrc/Makefile: FACTS */
 #undef PINN_DECLM
+#undef PINN_DECLF
 #elif defined(PINN_DEV_MERGED)
 hipError_t launch_jetum_a0(const KernelArgs&, bool, int, hipStream_t);
+hipError_t launch_jetumf_a0(const KernelArgs&, bool, int, hipStream_t);
 #endif
 
 #ifdef PINN_STAMPS
@@ -469,15 +474,44 @@ static bool u16m_unit_packed(const NetDev& n, bool coef) {
   return strstr(pinn_build_info(), unit) == nullptr;
 }
 
-static hipError_t dispatch_u16m(bool coef, const KernelArgs& a, bool bwd, int grid, hipStream_t st) {
+// The fixed-shape merged units (jet_kernel_u16.h, FIXED) take a descriptor that takes the merged units and has the shape
+// they are compiled for (jet_u16_fixed_shape).  They give the generic merged units' bits, and like use_merged the answer is
+// the same for forward-only, fused, res_bar and inverse calls: both fixed units of the family must be routable, and each
+// must carry the packed round exactly if its generic sibling does (the round sums in another order than ordinary units).
+// PINN_FLAG_GENERIC_UNITS keeps the generic merged units.  `merged` is use_merged's answer for the same call.
+static bool use_fixed_shape(const PinnNetDesc* d, const NetDev& n, bool merged) {
+  if (!merged || (d->flags & PINN_FLAG_GENERIC_UNITS) || !jet_u16_fixed_shape(n)) return false;
+  const int fam = jet_wide_act_family(n);
+  if (fam == PINN_ACT_SIN || fam == PINN_ACT_SIGMOID) return false;  // no fixed units are built for these (csrc/Makefile: FACTS)
+  const char* info = pinn_build_info();
+  char unit[64];
+#if defined(PINN_DEV)
+  const int forms = 1;  // the dev build has no COEF units
+#else
+  const int forms = 2;
+#endif
+  for (int coef = 0; coef < forms; ++coef) {
+    snprintf(unit, sizeof(unit), coef ? "jet_u16mfc_%d:" : "jet_u16mf_%d:", fam);
+    if (strstr(info, unit)) return false;
+    snprintf(unit, sizeof(unit), coef ? "nopack jet_u16mfc_%d " : "nopack jet_u16mf_%d ", fam);
+    if ((strstr(info, unit) == nullptr) != u16m_unit_packed(n, coef != 0)) return false;
+  }
+  return true;
+}
+
+static hipError_t dispatch_u16m(bool coef, bool fixed, const KernelArgs& a, bool bwd, int grid, hipStream_t st) {
   [[maybe_unused]] const int fam = jet_wide_act_family(a);
 #if !defined(PINN_DEV)
+#define PINN_FCASE(A_) \
+  if (fam == A_ && fixed) return coef ? launch_jetumfc_a##A_(a, grid, st) : launch_jetumf_a##A_(a, bwd, grid, st);
 #define PINN_MCASE(A_) \
   if (fam == A_) return coef ? launch_jetumc_a##A_(a, grid, st) : launch_jetum_a##A_(a, bwd, grid, st);
+  PINN_FCASE(0) PINN_FCASE(2) PINN_FCASE(4)
   PINN_MCASE(0) PINN_MCASE(1) PINN_MCASE(2) PINN_MCASE(3) PINN_MCASE(4)
 #undef PINN_MCASE
+#undef PINN_FCASE
 #elif defined(PINN_DEV_MERGED)
-  if (!coef && fam == 0) return launch_jetum_a0(a, bwd, grid, st);
+  if (!coef && fam == 0) return fixed ? launch_jetumf_a0(a, bwd, grid, st) : launch_jetum_a0(a, bwd, grid, st);
 #endif
   return hipErrorInvalidValue;
 }
@@ -656,7 +690,8 @@ static int run(const PinnNetDesc* net, const float* const* weights, float* const
     }
     const bool merged = u16 && use_merged(net, a.net, pde, nt, nx, mode);
     if (u16) jet_u16_set_plan(a, grid, merged ? u16m_unit_packed(a.net, inverse) : u16_unit_packed(a.net, nt, nx, inverse));
-    hipError_t e = merged  ? dispatch_u16m(inverse, a, bwd, grid, static_cast<hipStream_t>(stream))
+    const bool fixed = use_fixed_shape(net, a.net, merged);  // same plan, LDS size and results as the generic merged unit
+    hipError_t e = merged  ? dispatch_u16m(inverse, fixed, a, bwd, grid, static_cast<hipStream_t>(stream))
                    : inverse ? dispatch_coef(u16, nt, nx, a, grid, static_cast<hipStream_t>(stream))
                    : u16   ? dispatch_u16(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream))
                            : dispatch_wide(nt, nx, a, bwd, grid, static_cast<hipStream_t>(stream));
@@ -830,6 +865,22 @@ int pinn_kernel_name(const PinnNetDesc* net, int64_t N, int32_t time_order, int3
     name = use_u16(net, n, time_order, space_order, backward == 1) ? "jet_kernel_u16" : "jet_kernel_wide";
   }
   snprintf(buf, len, "%s", name);
+  return PINN_OK;
+}
+
+int pinn_residual_unit_name(const PinnNetDesc* net, const PinnPdeDesc* pde, int64_t N, char* buf, size_t len) {
+  int32_t nt, nx;
+  int rc = pinn_pde_streams(pde, &nt, &nx);
+  if (rc) return rc;
+  rc = pinn_kernel_name(net, N, nt, nx, 1, buf, len);
+  if (rc || strcmp(buf, "jet_kernel_u16") != 0) return rc;
+  NetDev n;
+  build_wide(net, nullptr, nullptr, &n);
+  const int fam = jet_wide_act_family(n);
+  const bool merged = use_merged(net, n, pde, nt, nx, MODE_PDE);  // the decisions run() makes, in the same helpers
+  if (use_fixed_shape(net, n, merged)) snprintf(buf, len, "jet_u16mf_%d", fam);
+  else if (merged) snprintf(buf, len, "jet_u16m_%d", fam);
+  else snprintf(buf, len, "jet_u16_%d_%d_%d", (int)nt, (int)nx, fam);
   return PINN_OK;
 }
 
