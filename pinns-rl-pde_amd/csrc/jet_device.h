@@ -70,7 +70,11 @@ __device__ __forceinline__ void act_derivs(float z, float w, float (&f)[6]) {
   if constexpr (ACT == PINN_ACT_TANH) {
     const float y = fast_tanhf(z);
     const float y2 = y * y;
-    const float f1 = 1.0f - y2;
+    // First order only (the sets (1,0), (1,1)): one rounding, spelled out.  Left to the compiler, 1 - y * y became an fma in
+    // the forward-only (1,0) 16-point unit and stayed a multiply and a subtract in its reverse unit, so the jets of the
+    // two calls differed by ulps (tests/test_pde_epilogue_gpu.py).  The higher orders keep the expression as it was: their
+    // units contract it alike, and spelled out it cost jet_wide_1_4_0 / jet_widec_1_4_0 their VGPR-form MFMA build.
+    const float f1 = ORD == 1 ? fmaf(-y, y, 1.0f) : 1.0f - y2;
     f[0] = y;
     f[1] = f1;
     if constexpr (ORD >= 2) f[2] = -2.0f * y * f1;

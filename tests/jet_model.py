@@ -247,7 +247,7 @@ def pde_streams(name: str, dimension: int = 1) -> Tuple[int, int]:
     if dimension > 1:
         return {"wave": (2, 0), "pendulum": (2, 0)}.get(name, (1, 0))
     return {"heat": (1, 1), "burgers": (1, 2), "allen_cahn": (1, 2), "kdv": (1, 3), "cahn_hilliard": (1, 4),
-            "wave": (2, 2), "convection": (1, 1), "black_scholes": (1, 2), "pendulum": (2, 0)}[name]
+            "wave": (2, 2), "convection": (1, 1), "black_scholes": (1, 2), "pendulum": (2, 0), "heat_laplacian": (1, 2)}[name]
 
 
 def pde_residual(name: str, p: Mapping, j: List[Tensor], x0: Tensor, NT: int, NX: int, dimension: int = 1):
@@ -274,7 +274,7 @@ def pde_residual(name: str, p: Mapping, j: List[Tensor], x0: Tensor, NT: int, NX
             d[0], d[1] = -rr * one, one
             return T(1) - rr * u, d
         d[1] = one  # every other >=2-D residual keeps only its u_t term (+ nothing that survives)
-        if name == "burgers" or name == "kdv" or name == "heat" or name == "cahn_hilliard" or name == "convection":
+        if name in ("burgers", "kdv", "heat", "cahn_hilliard", "convection", "heat_laplacian"):
             return T(1), d
         raise ValueError(name)
     if name == "burgers":
@@ -285,6 +285,10 @@ def pde_residual(name: str, p: Mapping, j: List[Tensor], x0: Tensor, NT: int, NX
         al = p["alpha"]
         d[1], d[NT + 1] = one, -al * one
         return T(1) - al * X(1), d
+    if name == "heat_laplacian":  # the intended heat equation, u_t - alpha u_xx (PINN_PDE_HEAT_LAPLACIAN)
+        al = p["alpha"]
+        d[1], d[NT + 2] = one, -al * one
+        return T(1) - al * X(2), d
     if name == "allen_cahn":
         e2 = p.get("epsilon", 0.1) ** 2
         d[0], d[1], d[NT + 2] = 3 * u * u - 1, one, -e2 * one
@@ -320,6 +324,35 @@ def pde_residual(name: str, p: Mapping, j: List[Tensor], x0: Tensor, NT: int, NX
         gl = p.get("g", 9.81) / p.get("L", 1.0)
         d[0], d[2] = gl * torch.cos(u), one
         return T(2) + gl * torch.sin(u), d
+    raise ValueError(name)
+
+
+def pde_coef_grads(name: str, p: Mapping, j: List[Tensor], x0: Tensor, NT: int, NX: int, dimension: int = 1):
+    """(dr/dc_0, dr/dc_1) per point: jet_device.h::pde_coef_grads.  c_0 / c_1 are nu | alpha | epsilon | c | velocity |
+    sigma, r | g / L in the order of include/pinn_jet.h; a kind without the coefficient gives zeros."""
+    u = j[0]
+    X = lambda k: j[NT + k]  # noqa: E731
+    zero = torch.zeros_like(u)
+    if dimension > 1:  # only terms that survive the reference's >= 2-D behaviour carry a coefficient
+        return (torch.sin(u) if name == "pendulum" else zero), (-u if name == "black_scholes" else zero)
+    if name in ("burgers", "heat_laplacian"):
+        return -X(2), zero
+    if name == "heat":
+        return -X(1), zero
+    if name == "allen_cahn":
+        return -2 * p.get("epsilon", 0.1) * X(2), zero
+    if name == "wave":
+        return -2 * p.get("c", 1.0) * X(2), zero
+    if name == "cahn_hilliard":
+        return 2 * p.get("epsilon", 0.1) * X(4), zero
+    if name == "convection":
+        return X(1), zero
+    if name == "pendulum":
+        return torch.sin(u), zero
+    if name == "black_scholes":
+        return p.get("sigma", 0.2) * x0 * x0 * X(2), x0 * X(1) - u
+    if name == "kdv":
+        return zero, zero
     raise ValueError(name)
 
 
