@@ -457,6 +457,52 @@ int pinn_causal_weights(const float* residual, const float* t, int64_t N, int32_
                         float* loss_sum_out, float* plain_sum_out, float* bin_losses, float* bin_weights, double* scratch,
                         void* stream);
 
+/* ---- face loss terms: Dirichlet, Neumann, Robin and periodic conditions per face (no counterpart in pinnrl) ----------
+ * A superset of pinn_jet_losses for up to PINN_FACE_MAX_TERMS terms, on a grid instead of one workgroup.  The jets of ALL
+ * launches of a boundary / initial chain lie in ONE buffer of n_floats floats (pinn_jet_forward writes its rows straight
+ * into it), the cotangents in a second buffer of the same layout (row s of a launch is the jet_cotangents[s] of its
+ * pinn_jet_backward).  Term k names up to four segments of n floats by their offsets in floats, -1 meaning absent:
+ *   value, value_pair   A, A'   a value row segment and its optional partner (periodic pairs),
+ *   deriv, deriv_pair   B, B'   a derivative row segment and its optional partner,
+ * and  d_i = alpha (A[i] - A'[i]) + beta (B[i] - B'[i]) - T_i  for i < n,  T_i = target[i], or target_const when target is
+ * null.  A missing segment contributes nothing.  fp32 evaluation order, every operation rounded once, none contracted:
+ *   d = -T_i;   a = A[i], then a = a - A'[i] with a partner;   d = fma(alpha, a, d)   (with a value segment);
+ *   b = B[i], then b = b - B'[i] with a partner;   d = fma(beta, b, d)   (with a derivative segment).
+ * Outputs:
+ *   term_losses[k] = (1/n) sum_i l(d_i): l in double from the fp32 d_i (l as pinn_causal_weights has it), double sums, the
+ *                    mean rounded once;
+ *   cotangent       with s = weight / (float)n, sa = s * alpha, sb = s * beta (fp32, in this order) and l' exact in fp32:
+ *                    sa l'(d_i) on A, its negation on A', sb l'(d_i) on B, its negation on B'.  Every float a term names is
+ *                    written exactly once; every other float of the buffer is left untouched (the caller zeroes it once:
+ *                    the rows no term names, such as u_t of a (1, 1) launch, then stay zero without a fill per step);
+ *   summary4        nullable: {residual, boundary, initial, total} as pinn_jet_losses defines them (residual = residual_sum[0]
+ *                    * residual_scale in fp32; the three sums over the rounded term losses in double, term order, rounded
+ *                    once).  n_terms == 0 with a summary still writes it.
+ * terms is a HOST array, read before the call returns and handed to the kernels by value (no upload, no copy of jets);
+ * jets, cotangent, target, term_losses, residual_sum, summary4, scratch: device.  scratch: PINN_FACE_SCRATCH_DOUBLES
+ * doubles, 8-byte aligned.
+ * Two launches on `stream`, no synchronisation, no allocation, no atomics: a fixed grid of min(64, ceil(max n / 256))
+ * blocks x 256 threads (the term loop is wave-uniform; block b takes the points b * 256 + tid, + grid * 256, ... of every
+ * term; 4-byte accesses, so which thread takes which point does not depend on alignment; per-block, per-term partial sums
+ * in double: a fixed butterfly inside a wave, the four waves in order); one workgroup adds the partials in block order.
+ * Two calls on the same inputs are bit-identical, and so are the term losses of the same data at other offsets.
+ * Checked on the host before any launch, PINN_ERR_BAD_DESC: n_terms outside [0, PINN_FACE_MAX_TERMS]; an unknown loss;
+ * n < 1; an offset other than -1 whose segment leaves [0, n_floats); alpha != 0 without a value segment or a value segment
+ * with alpha == 0, and the same for beta and the derivative segment; a partner without its primary; any two segments that
+ * overlap, of different terms or of one; with n_terms > 0 a null jets / cotangent / terms / term_losses / scratch.
+ * Misaligned scratch: PINN_ERR_MISALIGNED. */
+#define PINN_FACE_MAX_TERMS 32
+#define PINN_FACE_SCRATCH_DOUBLES (64 * PINN_FACE_MAX_TERMS) /* 64 blocks x 32 terms */
+typedef struct PinnFaceTerm {
+  int32_t value, value_pair, deriv, deriv_pair; /* offsets in floats into jets / cotangent, -1: absent */
+  int32_t n;                                    /* points of the term */
+  float alpha, beta, target_const, weight;
+  const float* target; /* n device floats, or null: target_const */
+} PinnFaceTerm;
+int pinn_face_losses(const float* jets, float* cotangent, int64_t n_floats, int32_t n_terms, const PinnFaceTerm* terms,
+                     int32_t loss, float huber_delta, float* term_losses, const float* residual_sum, float residual_scale,
+                     float residual_weight, int32_t n_boundary_terms, float* summary4, double* scratch, void* stream);
+
 /* ---- residuals given as data (pinnrl: a user's PDEBase subclass, pinnrl/pdes/pde_base.py:574-588) ---------------------
  * A residual outside the nine compiled PDEs, as a sum of products of streams, coordinates and sin / cos of the value:
  *   r = sum_{m < n_terms} c_m prod_{f < n_factors[m]} phi_{m,f}

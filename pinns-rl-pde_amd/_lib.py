@@ -72,6 +72,9 @@ PINN_SYSTEM_MAX_FIELDS = 4
 PINN_SYSTEM_MAX_EQUATIONS = 4
 PINN_SYSTEM_MAX_TERMS = 32
 PINN_SYSTEM_SCRATCH_DOUBLES = 64 * (4 + 32)
+# pinn_face_losses: the loss terms of per-face boundary conditions
+PINN_FACE_MAX_TERMS = 32
+PINN_FACE_SCRATCH_DOUBLES = 64 * PINN_FACE_MAX_TERMS
 
 
 def PINN_SYSTEM_FACTOR(field: int, code: int) -> int:
@@ -91,6 +94,7 @@ EXPORTS = (
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
     "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system", "pinn_residual_unit_name",
+    "pinn_face_losses",
 )
 
 
@@ -144,6 +148,14 @@ class PinnTermPdeSystem(ctypes.Structure):
         ("n_terms", ctypes.c_int32), ("equation_of", ctypes.c_int32 * PINN_SYSTEM_MAX_TERMS),
         ("eq_weight", ctypes.c_float * PINN_SYSTEM_MAX_EQUATIONS), ("loss", ctypes.c_int32), ("huber_delta", ctypes.c_float),
         ("terms", PinnTermPdeTerm * PINN_SYSTEM_MAX_TERMS),
+    ]
+
+
+class PinnFaceTerm(ctypes.Structure):
+    _fields_ = [
+        ("value", ctypes.c_int32), ("value_pair", ctypes.c_int32), ("deriv", ctypes.c_int32), ("deriv_pair", ctypes.c_int32),
+        ("n", ctypes.c_int32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("target_const", ctypes.c_float),
+        ("weight", ctypes.c_float), ("target", ctypes.c_void_p),
     ]
 
 
@@ -287,6 +299,8 @@ def load():
         lib.pinn_term_residual_system.argtypes = [P(PinnTermPdeSystem), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, vp, P(vp), vp, vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
+        lib.pinn_face_losses.restype = ctypes.c_int
+        lib.pinn_face_losses.argtypes = [vp, vp, i64, i32, P(PinnFaceTerm), i32, f32, vp, vp, f32, f32, i32, vp, vp, vp]
         if lib.pinn_abi_version() != PINN_ABI_VERSION:
             raise JetLibraryError(f"libpinnjet.so ABI {lib.pinn_abi_version()} != expected {PINN_ABI_VERSION}: rebuild")
         _lib = lib

@@ -543,17 +543,22 @@ def pde_streams(pd) -> Tuple[int, int]:
 # raw launches
 # ---------------------------------------------------------------------------------------------
 def jets_forward(prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, axis: int = 0,
-                 direction: Optional[Sequence[int]] = None, component: int = 0) -> Tensor:
+                 direction: Optional[Sequence[int]] = None, component: int = 0, out: Optional[Tensor] = None) -> Tensor:
     """(K, N) tensor of [u, d/dt.., d/dx_axis..] — one launch, no graph.  `axis`: the column of x the space streams
     differentiate along (non-zero: the layer-major engine; also the sets (0, 1) .. (0, 4)).  `direction`: a tuple of
     -1 / 0 / +1 per space axis instead — the space streams are (sum_c d_c d/dx_c)^k u, sets (0, 1) .. (0, 4) only.
-    `component`: the output of a multi-output network the jets are of (`NetProgram`); composes with both."""
+    `component`: the output of a multi-output network the jets are of (`NetProgram`); composes with both.
+    `out`: a contiguous float32 (K, N) tensor of the caller's to write into (a view of a larger buffer, say) instead of a
+    new one."""
     desc = _launch_desc(prog, axis, direction, component)
     lib = _lib.load()
     dev = _require_device(x, t, *prog.tensors)
     x, t, N = _prep_points(prog, x, t)
     K = 1 + nt + nx
-    out = torch.empty((K, N), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((K, N), dtype=torch.float32, device=dev)
+    elif out.shape != (K, N) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out: a contiguous float32 ({K}, {N}) tensor on {dev}; got {tuple(out.shape)}, {out.dtype}, {out.device}")
     if N == 0:
         return out
     optr = (ctypes.c_void_p * K)(*[out[s].data_ptr() for s in range(K)])
@@ -1078,6 +1083,58 @@ def jet_losses(jets: Tensor, terms: Sequence[Tuple[int, int, int, int, Optional[
                                        summary4.data_ptr() if summary4 is not None else None, _stream(dev)))
 
 
+class FaceTerms:
+    """The host table of `pinn_face_losses`, built once.  terms: dicts with the keys "n", "weight" and, all optional, "value",
+    "value_pair", "deriv", "deriv_pair" (offsets in floats into the jets buffer, absent or None: no such segment), "alpha",
+    "beta" (default 0), "target" (a float32 device tensor of n entries, or a number: the constant target; default 0).  The
+    table keeps the target tensors alive."""
+
+    def __init__(self, terms: Sequence[Dict[str, object]]):
+        n = len(terms)
+        self.n_terms = n
+        self.targets = []
+        self.array = (_lib.PinnFaceTerm * max(n, 1))()
+        for k, tm in enumerate(terms):
+            e = self.array[k]
+            for name in ("value", "value_pair", "deriv", "deriv_pair"):
+                v = tm.get(name)
+                setattr(e, name, -1 if v is None else int(v))
+            e.n = int(tm["n"])
+            e.alpha, e.beta, e.weight = float(tm.get("alpha", 0.0)), float(tm.get("beta", 0.0)), float(tm["weight"])
+            tg = tm.get("target", 0.0)
+            if isinstance(tg, Tensor):
+                if tg.dtype != torch.float32 or not tg.is_contiguous() or tg.numel() != e.n:
+                    raise ValueError(f"face term {k}: target is a contiguous float32 tensor of n = {e.n} entries")
+                self.targets.append(tg)
+                e.target, e.target_const = tg.data_ptr(), 0.0
+            else:
+                e.target, e.target_const = None, float(tg)
+
+
+def face_losses(jets: Tensor, terms, loss: str, huber_delta: float, term_losses: Tensor, cot: Tensor, scratch: Tensor,
+                residual_sum: Optional[Tensor] = None, residual_scale: float = 0.0, residual_weight: float = 0.0,
+                n_boundary_terms: int = 0, summary4: Optional[Tensor] = None) -> None:
+    """`pinn_face_losses`: term k reads up to four segments of the flat float32 buffer `jets` (the rows of several jet launches,
+    written in place through `jets_forward(out=)`), d = alpha (A - A') + beta (B - B') - T, term_losses[k] = mean l(d), and
+    writes the cotangents of exactly those segments into `cot` (same layout; zero it once).  terms: a `FaceTerms` or the list
+    of dicts one is built from.  scratch: PINN_FACE_SCRATCH_DOUBLES float64.  Two launches; the summary as `jet_losses`."""
+    lib = _lib.load()
+    if not isinstance(terms, FaceTerms):
+        terms = FaceTerms(terms)
+    dev = _require_device(jets, term_losses, cot, scratch, *terms.targets)
+    if loss not in _lib.LOSS:
+        raise ValueError(f"unknown loss '{loss}' (one of {', '.join(_lib.LOSS)})")
+    assert jets.dtype == torch.float32 and cot.dtype == torch.float32 and jets.is_contiguous() and cot.is_contiguous()
+    assert cot.numel() == jets.numel() and term_losses.dtype == torch.float32 and term_losses.numel() >= terms.n_terms
+    assert scratch.dtype == torch.float64 and scratch.numel() >= _lib.PINN_FACE_SCRATCH_DOUBLES
+    with torch.cuda.device(dev):
+        _lib.check(lib.pinn_face_losses(jets.data_ptr(), cot.data_ptr(), jets.numel(), terms.n_terms, terms.array,
+                                        _lib.LOSS[loss], float(huber_delta), term_losses.data_ptr(),
+                                        residual_sum.data_ptr() if residual_sum is not None else None, float(residual_scale),
+                                        float(residual_weight), int(n_boundary_terms),
+                                        summary4.data_ptr() if summary4 is not None else None, scratch.data_ptr(), _stream(dev)))
+
+
 def fd_stencil_points(x: Tensor, t: Tensor, eps: float, lo: float, hi: float, x3: Tensor, t3: Tensor) -> None:
     """x3 = [x | clamp(x + eps, lo, hi) | clamp(x - eps, lo, hi)], t3 = [t | t | t] (`pinn_fd_stencil_points`, 1-D): the 3N
     evaluation points of the finite-difference smoothness term, bit-equal to torch's fp32 arithmetic.  x, t: N contiguous
@@ -1360,29 +1417,51 @@ class JetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prog: NetProgram, x: Tensor, t: Tensor, nt: int, nx: int, *params):
         # `apply` takes no keywords: a component launch passes `component` as a plain int in front of the tensors,
-        # JetFunction.apply(prog, x, t, nt, nx, k, *params); without it (component 0) the arguments are as they always were
-        component = 0
-        if params and isinstance(params[0], int):
+        # JetFunction.apply(prog, x, t, nt, nx, k, *params), a launch along a space axis a >= 1 the pair (component, axis),
+        # JetFunction.apply(prog, x, t, nt, nx, (k, a), *params); without either (component 0, axis 0) the arguments are as
+        # they always were
+        component, axis = 0, 0
+        if params and isinstance(params[0], tuple):
+            (component, axis), params = (int(v) for v in params[0]), params[1:]
+            ctx.lead = (None,) * 6
+        elif params and isinstance(params[0], int):
             component, params = int(params[0]), params[1:]
             ctx.lead = (None,) * 6
         else:
             ctx.lead = (None,) * 5
-        ctx.prog, ctx.nt, ctx.nx, ctx.component = prog, nt, nx, component
+        ctx.prog, ctx.nt, ctx.nx, ctx.component, ctx.axis = prog, nt, nx, component, axis
         ctx.save_for_backward(x, t)
-        return jets_forward(prog, x, t, nt, nx, component=component)
+        return jets_forward(prog, x, t, nt, nx, axis=axis, component=component)
 
     @staticmethod
     def backward(ctx, cot: Tensor):
-        prog, nt, nx, component = ctx.prog, ctx.nt, ctx.nx, ctx.component
+        prog, nt, nx, component, axis = ctx.prog, ctx.nt, ctx.nx, ctx.component, ctx.axis
         x, t = ctx.saved_tensors
         params = prog.tensors  # the live tensors this node was applied to (PINNModel.jets passes exactly these)
         want_x, want_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         want_w = any(ctx.needs_input_grad[len(ctx.lead):])
         if not (want_x or want_t):
             flat = new_flat_grad(prog, cot.device)
-            jets_backward(prog, x, t, nt, nx, cot, flat, component=component)
+            jets_backward(prog, x, t, nt, nx, cot, flat, axis=axis, component=component)
             grads = split_flat_grad(prog, flat)
             return (*ctx.lead, *grads)
+        if axis:
+            # a launch along a further space axis: exact first-order cotangents of the parameters and the coordinates; none of
+            # them is differentiable again (the streams of axis a raised by one order along another column are mixed)
+            flat = new_flat_grad(prog, cot.device) if want_w else None
+            xg, tg = jets_backward_inputs(prog, x, t, nt, nx, cot.detach(), flat, want_x, want_t, axis=axis, component=component)
+            grads = split_flat_grad(prog, flat) if flat is not None else [None] * len(prog.tensors)
+            xg = xg.to(x.dtype) if xg is not None else None
+            tg = tg.to(t.dtype) if tg is not None else None
+            if torch.is_grad_enabled():
+                anchors = (x, t, *params)
+                what = f" of jets along space axis {axis}"
+                grads = [None if g is None else _NotTwiceDifferentiable.apply(g, "a weight gradient" + what, *anchors) for g in grads]
+                if xg is not None:
+                    xg = _NotTwiceDifferentiable.apply(xg, "d<cot, jets>/dx" + what, *anchors)
+                if tg is not None:
+                    tg = _NotTwiceDifferentiable.apply(tg, "d<cot, jets>/dt" + what, *anchors)
+            return (None, xg if want_x else None, tg if want_t else None, *ctx.lead[3:], *grads)
         flat = new_flat_grad(prog, cot.device) if want_w else None
         xg, tg = jets_backward_inputs(prog, x, t, nt, nx, cot.detach(), flat, want_x, want_t, component=component)
         grads = split_flat_grad(prog, flat) if flat is not None else [None] * len(prog.tensors)

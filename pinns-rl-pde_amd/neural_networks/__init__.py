@@ -123,16 +123,21 @@ class BaseNetwork(nn.Module):
         if self._prog_cache is not None:
             self._prog_cache[1].set_deterministic(self._deterministic)
 
-    def jets(self, x: torch.Tensor, t: torch.Tensor, time_order: int = 0, space_order: int = 0, component: int = 0) -> torch.Tensor:
+    def jets(self, x: torch.Tensor, t: torch.Tensor, time_order: int = 0, space_order: int = 0, component: int = 0,
+             axis: int = 0) -> torch.Tensor:
         """(K, N) = [u, d/dt.., d/dx..] in one launch; differentiable w.r.t. the parameters and w.r.t. x / t.  `component`:
-        the output the jets are of, for a network with output_dim > 1 (one launch per component)."""
+        the output the jets are of, for a network with output_dim > 1 (one launch per component).  `axis`: the column of x the
+        space streams differentiate along; a non-zero axis takes the stream sets (0, 1) .. (0, 4) and the time-carrying sets
+        of the layer-major engine, its gradients are exact and not differentiable again."""
         prog = self.program()
         params = prog.tensors
         if torch.is_grad_enabled() and (x.requires_grad or t.requires_grad or any(p.requires_grad for p in params)):
+            if axis:
+                return _E.JetFunction.apply(prog, x, t, time_order, space_order, (int(component), int(axis)), *params)
             if component:
                 return _E.JetFunction.apply(prog, x, t, time_order, space_order, int(component), *params)
             return _E.JetFunction.apply(prog, x, t, time_order, space_order, *params)
-        return _E.jets_forward(prog, x, t, time_order, space_order, component=component)
+        return _E.jets_forward(prog, x, t, time_order, space_order, axis=axis, component=component)
 
     def forward(self, x: InputType) -> OutputType:
         inp = self._prepare_input(x)
@@ -462,8 +467,8 @@ class PINNModel(BaseNetwork):
         prog = self.model.program()
         return prog
 
-    def jets(self, x, t, time_order: int = 0, space_order: int = 0, component: int = 0):
-        return self.model.jets(x, t, time_order, space_order, component=component)
+    def jets(self, x, t, time_order: int = 0, space_order: int = 0, component: int = 0, axis: int = 0):
+        return self.model.jets(x, t, time_order, space_order, component=component, axis=axis)
 
     def forward(self, x):
         return self.model(x)

@@ -24,6 +24,7 @@ import torch
 
 from .. import _lib
 from .. import engine as _E
+from .face_conditions import FaceConditions, check_face_arguments, check_term_count
 from .pde_base import PDEBase, PDEConfig, _pick_stream_set
 from .term_pde import _T_ORDER, _X_ORDER, Coef
 
@@ -76,6 +77,14 @@ class TermPDEnD(PDEBase):
     (u on opposite faces paired point by point).  The boundary loss is the mean of l(u - v) over all face points, or the sum
     over the axes of the mean of l(u_low - u_high).
 
+    face_conditions (with an empty config.boundary_conditions) gives every face its own condition instead: Dirichlet, Neumann or
+    Robin with a number or a callable as the value, periodic axes with or without the derivative, None for no condition; the
+    boundary loss is then the SUM of one mean per face, so {"default": {"type": "dirichlet", "value": v}} is 2 dim times the
+    config form's loss (face_conditions.py has the keys and the specs).  An insulated plate, heated through x_lo, cooled by
+    convection at x_hi:  face_conditions={"y": {"type": "neumann", "value": 0.0},
+                                          "x_lo": {"type": "dirichlet", "value": lambda x, t: torch.sin(torch.pi * x[:, 1])},
+                                          "x_hi": {"type": "robin", "alpha": 1.0, "beta": 0.5, "value": 0.2}}
+
     2-D heat:  TermPDEnD(cfg, [(1.0, ("u_t",)), ((-1.0, "alpha"), ("u_xx",)), ((-1.0, "alpha"), ("u_yy",))],
                          lambda x: torch.sin(torch.pi * x[:, 0]) * torch.sin(torch.pi * x[:, 1]))
     """
@@ -91,7 +100,8 @@ class TermPDEnD(PDEBase):
     def __init__(self, config: PDEConfig, terms: Sequence[Tuple[Coef, Sequence[str]]],
                  initial_condition_fn: Callable[[torch.Tensor], torch.Tensor],
                  exact_solution_fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
-                 boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32, **kwargs):
+                 boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32,
+                 face_conditions: Optional[Dict[str, Any]] = None, **kwargs):
         dim = int(getattr(config, "dimension", 1))
         if dim not in (2, 3):
             raise NotImplementedError(f"{type(self).__name__}: dimension {dim}: two or three space dimensions (TermPDE runs 1-D problems)")
@@ -146,7 +156,13 @@ class TermPDEnD(PDEBase):
         self._nx = tuple(nx)
         self._pair = tuple(pair)
         bcs = dict(getattr(config, "boundary_conditions", None) or {})
-        if list(bcs) == ["dirichlet"]:
+        self._faces: Optional[FaceConditions] = None
+        if face_conditions is not None:
+            check_face_arguments(type(self).__name__, face_conditions, config)
+            self._faces = FaceConditions(type(self).__name__, face_conditions, dim)
+            check_term_count(type(self).__name__, len(self._faces), 1)
+            self._bc = ("faces", 0.0)
+        elif list(bcs) == ["dirichlet"]:
             p = bcs["dirichlet"] or {}
             if p.get("type", "fixed") != "fixed":
                 raise NotImplementedError(f"{type(self).__name__}: dirichlet boundary of type '{p.get('type')}': a fixed value on all faces only")
@@ -229,6 +245,8 @@ class TermPDEnD(PDEBase):
         pts["u0"] = u0.to(dev)
         if self._bc[0] == "dirichlet":
             pts["ub"] = torch.full((pts["n_bc"],), self._bc[1], dtype=torch.float32, device=dev)
+        if self._faces is not None:
+            pts["face_targets"] = self._faces.targets(type(self).__name__, pts)
         self._points = (dev, pts)
         return pts
 
@@ -242,7 +260,9 @@ class TermPDEnD(PDEBase):
         P = self._nd_points()
         u = model(torch.cat([P["x"], P["t"]], dim=1)).reshape(-1)
         nbc, nf = P["n_bc"], P["n_face"]
-        if self._bc[0] == "dirichlet":
+        if self._faces is not None:
+            boundary_loss = self._faces.boundary_loss(self, model, P, P["face_targets"], u.reshape(-1, 1))
+        elif self._bc[0] == "dirichlet":
             boundary_loss = self._apply_loss_fn(u[:nbc] - P["ub"])
         else:
             boundary_loss = torch.zeros((), device=dev)
@@ -256,11 +276,15 @@ class TermPDEnD(PDEBase):
     def _manual_chain(self, n_batch: int) -> Dict[str, Any]:
         """`compute_loss`' boundary / initial part as data for the launch list (see PDEBase._manual_chain): the value stream
         on the fixed points; one target term over all faces (dirichlet) or one paired term per axis (periodic), then the
-        initial term."""
+        initial term.  With face_conditions: no "terms"; "face" holds the jet launches and the `pinn_face_losses` table
+        (`FaceConditions.chain`), the boundary terms first, then the initial term."""
         P = self._nd_points()
         lw = self._loss_weights()
         bw, iw = (lw.get("boundary", 10.0), lw.get("initial", 10.0)) if lw else (10.0, 10.0)
         nbc, nf = P["n_bc"], P["n_face"]
+        if self._faces is not None:
+            return {"x": P["x"], "t": P["t"], "nt": 0, "nx": 0, "terms": [], "n_bc": len(self._faces),
+                    "face": self._faces.chain(P, P["face_targets"], float(bw), [(0, P["u0"], float(iw))])}
         if self._bc[0] == "dirichlet":
             terms = [(0, nbc, 0, 0, P["ub"], float(bw))]
         else:

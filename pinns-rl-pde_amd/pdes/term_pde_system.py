@@ -21,6 +21,7 @@ import torch
 
 from .. import _lib
 from .. import engine as _E
+from .face_conditions import FaceConditions, check_face_arguments, check_term_count
 from .pde_base import PDEBase, PDEConfig, _pick_stream_set
 from .term_pde import Coef
 from .term_pde_nd import box_points
@@ -54,6 +55,12 @@ class TermPDESystem(PDEBase):
     fixed points are `TermPDEnD`'s: every face a tensor grid of the other coordinates and of time (in 1-D the two ends times
     the time grid), the initial points a tensor grid of the box at `time_domain[0]`.
 
+    face_conditions (with an empty config.boundary_conditions) gives every face of every field its own condition instead
+    (face_conditions.py: Dirichlet, Neumann, Robin, periodic, None; a spec for all fields or a mapping {field: spec | None} per
+    key); every (face, field) with a condition is one loss term of the boundary sum, and the boundary and initial terms
+    together number at most 32.  A lid-driven cavity, with wall = {"type": "dirichlet", "value": 0.0}:
+        face_conditions={"default": {"u": wall, "v": wall, "p": None}, "y_hi": {"u": {"type": "dirichlet", "value": 1.0}}}
+
     Gray-Scott in 1-D:
         TermPDESystem(cfg, ("u", "v"),
                       [[(1.0, ("u_t",)), ((-1.0, "Du"), ("u_xx",)), (1.0, ("u", "v", "v")), ((-1.0, "F"), ()), ((1.0, "F"), ("u",))],
@@ -67,7 +74,8 @@ class TermPDESystem(PDEBase):
                  initial_condition_fn: Callable[[torch.Tensor], torch.Tensor],
                  exact_solution_fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
                  equation_weights: Optional[Sequence[float]] = None, initial_condition_fields: Optional[Sequence[str]] = None,
-                 boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32, **kwargs):
+                 boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32,
+                 face_conditions: Optional[Dict[str, Any]] = None, **kwargs):
         who = type(self).__name__
         dim = int(getattr(config, "dimension", 1))
         if dim not in (1, 2, 3):
@@ -145,7 +153,13 @@ class TermPDESystem(PDEBase):
         self._eq_weights = tuple(w)
         # ---- boundary and initial conditions
         bcs = dict(getattr(config, "boundary_conditions", None) or {})
-        if list(bcs) == ["dirichlet"]:
+        self._faces: Optional[FaceConditions] = None
+        if face_conditions is not None:
+            check_face_arguments(who, face_conditions, config)
+            self._faces = FaceConditions(who, face_conditions, dim, fields)
+            self._bc = ("faces", None)
+            n_bc_terms = len(self._faces)
+        elif list(bcs) == ["dirichlet"]:
             p = bcs["dirichlet"] or {}
             if p.get("type", "fixed") != "fixed":
                 raise NotImplementedError(f"{who}: dirichlet boundary of type '{p.get('type')}': a fixed value on all faces only")
@@ -169,7 +183,9 @@ class TermPDESystem(PDEBase):
         if len(set(ic_fields)) != len(ic_fields):
             raise ValueError(f"{who}: initial_condition_fields {ic_fields} repeat")
         self._ic_fields = tuple(index[name] for name in ic_fields)
-        if n_bc_terms + len(self._ic_fields) > PINN_MAX_POINT_TERMS:
+        if self._faces is not None:
+            check_term_count(who, n_bc_terms, len(self._ic_fields))
+        elif n_bc_terms + len(self._ic_fields) > PINN_MAX_POINT_TERMS:
             raise NotImplementedError(
                 f"{who}: the boundary / initial chain has {n_bc_terms + len(self._ic_fields)} loss terms ({n_bc_terms} boundary + "
                 f"{len(self._ic_fields)} initial); one pinn_jet_losses call takes at most {PINN_MAX_POINT_TERMS}")
@@ -292,6 +308,8 @@ class TermPDESystem(PDEBase):
         pts["u0"] = u0.t().contiguous().to(dev)  # (fields, n_ic): one contiguous target per initial field
         if self._bc[0] == "dirichlet":
             pts["ub"] = [None if v is None else torch.full((pts["n_bc"],), v, dtype=torch.float32, device=dev) for v in self._bc[1]]
+        if self._faces is not None:
+            pts["face_targets"] = self._faces.targets(type(self).__name__, pts)
         self._points = (dev, pts)
         return pts
 
@@ -308,7 +326,11 @@ class TermPDESystem(PDEBase):
         u = model(torch.cat([P["x"], P["t"]], dim=1))
         nbc, nf = P["n_bc"], P["n_face"]
         boundary_loss = torch.zeros((), device=dev)
+        if self._faces is not None:
+            boundary_loss = self._faces.boundary_loss(self, model, P, P["face_targets"], u)
         for c in range(self.n_fields):
+            if self._faces is not None:
+                break
             if self._bc[0] == "dirichlet":
                 if P["ub"][c] is not None:
                     boundary_loss = boundary_loss + self._apply_loss_fn(u[:nbc, c] - P["ub"][c])
@@ -330,6 +352,10 @@ class TermPDESystem(PDEBase):
         lw = self._loss_weights()
         bw, iw = (lw.get("boundary", 10.0), lw.get("initial", 10.0)) if lw else (10.0, 10.0)
         nbc, nf = P["n_bc"], P["n_face"]
+        if self._faces is not None:  # no "terms": "face" holds the jet launches and the pinn_face_losses table
+            initial = [(c, P["u0"][k], float(iw)) for k, c in enumerate(self._ic_fields)]
+            return {"x": P["x"], "t": P["t"], "nt": 0, "nx": 0, "terms": [], "n_bc": len(self._faces), "components": self.n_fields,
+                    "face": self._faces.chain(P, P["face_targets"], float(bw), initial)}
         terms = []
         for c in range(self.n_fields):
             if self._bc[0] == "dirichlet":

@@ -27,7 +27,7 @@ import torch.optim as optim
 
 from .. import distributed as _D
 from .. import engine as _E
-from .._lib import LBFGS_REC, PINN_ADAPTIVE_SCRATCH_FLOATS, PINN_CAUSAL_SCRATCH_DOUBLES, PINN_FD_SCRATCH_DOUBLES, PINN_LBFGS_MAX_HISTORY, PINN_LBFGS_RECORD_DOUBLES
+from .._lib import LBFGS_REC, PINN_ADAPTIVE_SCRATCH_FLOATS, PINN_CAUSAL_SCRATCH_DOUBLES, PINN_FACE_SCRATCH_DOUBLES, PINN_FD_SCRATCH_DOUBLES, PINN_LBFGS_MAX_HISTORY, PINN_LBFGS_RECORD_DOUBLES
 from ..config import validate_causal_eps
 from .lbfgs import LBFGSDriver
 
@@ -749,6 +749,8 @@ class PDETrainer:
             K, npts = ch.get("components") or (1 + ch["nt"] + ch["nx"]), ch["x"].shape[0]
             ch["term_losses"] = torch.zeros(len(ch["terms"]), dtype=torch.float32, device=dev)
             ch["cot"] = torch.zeros(K, npts, dtype=torch.float32, device=dev)
+            if "face" in ch:
+                self._face_buffers(ch)
             ch["terms_dp"] = [(lo, hi, st, pr, tg, w / world) for lo, hi, st, pr, tg, w in ch["terms"]]
             if self.use_adaptive_weights:
                 # the boundary and the initial component separately, unweighted (the weights are the adaptive ones):
@@ -772,6 +774,34 @@ class PDETrainer:
                                     scratch=torch.zeros(PINN_FD_SCRATCH_DOUBLES, dtype=torch.float64, device=dev))
             F["chains"][key] = ch
         return ch
+
+    def _face_buffers(self, ch):
+        """The buffers of a chain with per-face conditions (`FaceConditions.chain`): ONE jets buffer that every launch of the
+        chain writes its rows into, launch after launch, a cotangent buffer of the same layout (zeroed here, once: pinn_face_losses
+        writes exactly the floats its terms name, so a row no term reads — u_t of a (1, 1) launch — stays zero), the table with
+        its segments as offsets in floats, the term losses and the scratch of pinn_face_losses."""
+        dev, face = self.device, ch["face"]
+        base, views = 0, []
+        for lo, hi, nt, nx, axis, comp in face["launches"]:
+            views.append((base, 1 + nt + nx, hi - lo))
+            base += (1 + nt + nx) * (hi - lo)
+        jets = torch.zeros(base, dtype=torch.float32, device=dev)
+        cot = torch.zeros(base, dtype=torch.float32, device=dev)
+        table = []
+        for tm in face["terms"]:
+            e = dict(tm)
+            for name in ("value", "value_pair", "deriv", "deriv_pair"):
+                if tm.get(name) is not None:
+                    launch, row, first = tm[name]
+                    b, _, npts = views[launch]
+                    e[name] = b + row * npts + first
+            table.append(e)
+        ch["face_jets"], ch["face_cot"] = jets, cot
+        ch["face_views"] = [(ch["x"][lo:hi], ch["t"][lo:hi], jets[b : b + K * n].view(K, n), cot[b : b + K * n].view(K, n))
+                            for (lo, hi, *_), (b, K, n) in zip(face["launches"], views)]
+        ch["face_table"] = _E.FaceTerms(table)
+        ch["term_losses"] = torch.zeros(len(table), dtype=torch.float32, device=dev)
+        ch["face_scratch"] = torch.zeros(PINN_FACE_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)
 
     def _manual_launches(self, x, t, side=None):
         """One optimiser step as a fixed launch sequence, no autograd (pinnrl/training/trainer.py:686-698 with
@@ -835,8 +865,21 @@ class PDETrainer:
                 _E.residual_loss_grad(prog, pd, x, t, F["rw"] / float(N), F["grad"][:n], loss_sum=F["grad"][n : n + 1])
 
         C = ch.get("components", 0)  # a system: one component launch per field, its value row the stream of that field
+        face = ch.get("face")  # per-face conditions: value and derivative launches into one buffer, pinn_face_losses
+
+        def face_losses(summary):
+            _E.face_losses(ch["face_jets"], ch["face_table"], loss_name, delta, ch["term_losses"], ch["face_cot"], ch["face_scratch"],
+                           residual_sum=F["grad"][n : n + 1] if summary else None, residual_scale=1.0 / float(N),
+                           residual_weight=F["rw"], n_boundary_terms=ch["n_bc"], summary4=F["summary"] if summary else None)
 
         def boundary_chain(grad, summary):
+            if face is not None:
+                for (lo, hi, nt, nx, axis, comp), (xv, tv, jv, cv) in zip(face["launches"], ch["face_views"]):
+                    _E.jets_forward(prog, xv, tv, nt, nx, axis=axis, component=comp, out=jv)
+                face_losses(summary)
+                for (lo, hi, nt, nx, axis, comp), (xv, tv, jv, cv) in zip(face["launches"], ch["face_views"]):
+                    _E.jets_backward(prog, xv, tv, nt, nx, cv, grad, axis=axis, component=comp)
+                return ch["face_jets"]
             if C:
                 u = torch.cat([_E.jets_forward(prog, ch["x"], ch["t"], 0, 0, component=c) for c in range(C)], 0)
             else:
@@ -868,8 +911,12 @@ class PDETrainer:
             F["grad"][:n].add_(F["grad_side"])
             # the {residual, boundary, initial, total} summary needs the residual launch's loss sum: the (3 us) loss-term
             # kernel runs once more here; it rewrites the same cotangents
-            _E.jet_losses(u, ch["terms"], loss_name, delta, ch["term_losses"], ch["cot"], residual_sum=F["grad"][n : n + 1],
-                          residual_scale=1.0 / float(N), residual_weight=F["rw"], n_boundary_terms=ch["n_bc"], summary4=F["summary"])
+            if face is not None:
+                face_losses(True)
+            else:
+                _E.jet_losses(u, ch["terms"], loss_name, delta, ch["term_losses"], ch["cot"], residual_sum=F["grad"][n : n + 1],
+                              residual_scale=1.0 / float(N), residual_weight=F["rw"], n_boundary_terms=ch["n_bc"],
+                              summary4=F["summary"])
         sm = ch.get("smooth")
         if sm is not None:
             # the smoothness term (HeatEquation._compute_smoothness_loss), after the summary is written and every other
