@@ -668,7 +668,8 @@ int pinn_term_residual_mixed(const PinnTermPdeMixed* pde, const float* coef_valu
  *   r_e = sum_{m: equation_of[m] = e} c_m prod_{f < n_factors[m]} phi_{m,f},   e < n_equations,
  * with one term list of at most PINN_SYSTEM_MAX_TERMS terms shared by all equations.  A factor is ONE BYTE,
  * PINN_SYSTEM_FACTOR(field, code) = field * 32 + code: `code` is a PinnTermFactor 0 .. 10 or PINN_TERM_UY .. PINN_TERM_Z
- * (11 .. 16) with its meaning for that field; coordinates ignore the field bits; no mixed derivatives.  Dimension 1 to 3.
+ * (11 .. 16) with its meaning for that field; coordinates ignore the field bits; no mixed derivatives
+ * (pinn_term_residual_system_mixed below has u_xy, u_xz, u_yz of every field).  Dimension 1 to 3.
  * Per field c, (time_order[c], space_order[c][0]) is a compiled axis-0 set and the axes 1 and 2 take the orders 0 .. 2
  * (0 beyond `dimension`).  The chain is one pinn_jet_forward per (field, axis with streams) -> pinn_term_residual_system ->
  * one pinn_jet_backward per block, all accumulating into the same weight gradients.
@@ -729,6 +730,56 @@ int pinn_term_residual_system(const PinnTermPdeSystem* pde, const float* coef_va
                               const float* t, int64_t N, float grad_scale, const float* residual_cotangent, float* residual_out,
                               float* loss_sum_out, float* eq_loss_sums, float* const* jet_cotangents, float* coef_grads,
                               double* scratch, void* stream);
+
+/* ---- term residuals of coupled systems with mixed derivatives (u_xy of any field) ------------------------------------------
+ * pinn_term_residual_system plus the factors u_ab of every field: the grad-div term of linear elasticity,
+ * mu Lap(u) + (lambda + mu) grad(div u), names v_xy in the u-equation and u_xy in the v-equation.  The factor byte stays
+ * PINN_SYSTEM_FACTOR(field, code); the codes 0 .. 16 keep their meaning, PINN_TERM_UXY, PINN_TERM_UXZ and PINN_TERM_UYZ
+ * (21 .. 23) are the mixed derivative of THAT field along the pair k = code - 21 of (x,y), (x,z), (y,z).  The codes 17 .. 20
+ * (order > 2 along y / z) and 24 .. 26 (u_aabb) are refused by name.  pair_order[c][k] is 0 or 2 (0 for a pair that touches an
+ * axis >= dimension); u_ab of field c needs pair_order[c][k] == 2 and order >= 2 of that field on both axes.
+ *   jets, jet_cotangents   HOST tables of 6 C device pointers (PINN_SYSTEM_MIXED_BLOCKS(C)).  Entry 3 c + a is the axis block
+ *                      (c, a) exactly as for pinn_term_residual_system.  Entry 3 C + 3 c + k is the 3 x N block of field c's
+ *                      launch along e_a + e_b for pair k on the set (0, 2) — a component launch with
+ *                      PINN_FLAG_SPACE_DIRECTION; only its row 2 (P_2) is read; NULL where pair_order[c][k] == 0.
+ *   value              u_ab = 0.5f * ((P_2 - A_2) - B_2), evaluated in fp32 in exactly this order (pinn_term_residual_mixed's);
+ *                      A_2, B_2 are the order-2 rows of the field's two axis blocks (axis 0: row time_order + 2).
+ *   cotangents         u_ab of a field is a (field, stream) target of its own under the sweep-2 rule of
+ *                      pinn_term_residual_system: the summands of one term that hit it are summed first, the sum is multiplied
+ *                      by rbar_{equation_of[m]} and the product is added to the accumulator g_k.  At write-out, per field and
+ *                      in ascending pair index k: p_k = 0.5f * g_k goes to row 2 of the P block, and the accumulator of the
+ *                      order-2 row of axis a, then that of axis b, has p_k subtracted from it (an x row that two pairs touch
+ *                      receives (acc - p_0) - p_1, the order of pinn_term_residual_mixed).  Rows 0 and 1 of every P cotangent
+ *                      block are written as zeros, as is every row the program never reads, so each block goes straight into
+ *                      pinn_jet_backward.
+ * Everything else — residual_out (E x N), residual_cotangent, loss_sum_out, eq_loss_sums, coef_grads, grad_scale * eq_weight[e]
+ * rounded once on the host, the loss kinds, sgn(0) = 0, scratch (PINN_SYSTEM_SCRATCH_DOUBLES), the rounding order of the pure
+ * factors, per-block double partials added in block order by the finish launch, no atomics, one launch when no sum is wanted,
+ * N == 0 a no-op — as pinn_term_residual_system: with every pair_order 0 the residuals and cotangent blocks are the same.
+ * Checked on the host before any HIP call: every check of pinn_term_residual_system; a pair_order outside {0, 2} or non-zero
+ * on a pair beyond the dimension (dimension 1 among them); a u_ab factor without pair_order[field][k] == 2 and order >= 2 on both
+ * axes of that field; a null required P block in either table: PINN_ERR_BAD_DESC, the message naming the field and the pair. */
+#define PINN_SYSTEM_MIXED_BLOCKS(C) (6 * (C))
+
+typedef struct PinnTermPdeSystemMixed {
+  int32_t dimension;                                   /* 1 .. 3 (a mixed factor needs 2 or 3) */
+  int32_t n_fields;
+  int32_t n_equations;
+  int32_t time_order[PINN_SYSTEM_MAX_FIELDS];
+  int32_t space_order[PINN_SYSTEM_MAX_FIELDS][3];
+  int32_t n_terms;
+  int32_t equation_of[PINN_SYSTEM_MAX_TERMS];
+  float eq_weight[PINN_SYSTEM_MAX_EQUATIONS];
+  int32_t loss;
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_SYSTEM_MAX_TERMS];        /* factor[f] = PINN_SYSTEM_FACTOR(field, code), code 0 .. 16 or 21 .. 23 */
+  int32_t pair_order[PINN_SYSTEM_MAX_FIELDS][3];       /* per field, pairs (x,y), (x,z), (y,z): 0 or 2 */
+} PinnTermPdeSystemMixed;
+
+int pinn_term_residual_system_mixed(const PinnTermPdeSystemMixed* pde, const float* coef_values, const float* const* jets,
+                                    const float* x, const float* t, int64_t N, float grad_scale, const float* residual_cotangent,
+                                    float* residual_out, float* loss_sum_out, float* eq_loss_sums, float* const* jet_cotangents,
+                                    float* coef_grads, double* scratch, void* stream);
 
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.

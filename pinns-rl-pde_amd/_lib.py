@@ -72,6 +72,8 @@ PINN_SYSTEM_MAX_FIELDS = 4
 PINN_SYSTEM_MAX_EQUATIONS = 4
 PINN_SYSTEM_MAX_TERMS = 32
 PINN_SYSTEM_SCRATCH_DOUBLES = 64 * (4 + 32)
+# pinn_term_residual_system_mixed: the factor codes of a system whose fields may name u_xy, u_xz, u_yz (codes 21 .. 23)
+TERM_FACTOR_SYSTEM_MIXED = dict(TERM_FACTOR_ND, **{"u_xy": 21, "u_xz": 22, "u_yz": 23})
 # pinn_face_losses: the loss terms of per-face boundary conditions
 PINN_FACE_MAX_TERMS = 32
 PINN_FACE_SCRATCH_DOUBLES = 64 * PINN_FACE_MAX_TERMS
@@ -80,6 +82,12 @@ PINN_FACE_SCRATCH_DOUBLES = 64 * PINN_FACE_MAX_TERMS
 def PINN_SYSTEM_FACTOR(field: int, code: int) -> int:
     """One byte per factor of a system term: field * 32 + code (a `TERM_FACTOR_ND` code; coordinates ignore the field)."""
     return int(field) * 32 + int(code)
+
+
+def PINN_SYSTEM_MIXED_BLOCKS(C: int) -> int:
+    """Entries of the block tables of pinn_term_residual_system_mixed: 3 C axis blocks (3 c + a), then 3 C P blocks
+    (3 C + 3 c + k, pair k of (x,y), (x,z), (y,z))."""
+    return 6 * int(C)
 
 
 # the record of pinn_lbfgs_direction / pinn_lbfgs_eval_stats (doubles); from "dmax" on: 64 per-block partials of max|d|
@@ -94,7 +102,7 @@ EXPORTS = (
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
     "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system", "pinn_residual_unit_name",
-    "pinn_face_losses",
+    "pinn_face_losses", "pinn_term_residual_system_mixed",
 )
 
 
@@ -149,6 +157,10 @@ class PinnTermPdeSystem(ctypes.Structure):
         ("eq_weight", ctypes.c_float * PINN_SYSTEM_MAX_EQUATIONS), ("loss", ctypes.c_int32), ("huber_delta", ctypes.c_float),
         ("terms", PinnTermPdeTerm * PINN_SYSTEM_MAX_TERMS),
     ]
+
+
+class PinnTermPdeSystemMixed(ctypes.Structure):
+    _fields_ = PinnTermPdeSystem._fields_ + [("pair_order", (ctypes.c_int32 * 3) * PINN_SYSTEM_MAX_FIELDS)]
 
 
 class PinnFaceTerm(ctypes.Structure):
@@ -297,6 +309,9 @@ def load():
         lib.pinn_term_residual_mixed.argtypes = [P(PinnTermPdeMixed), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, P(vp), vp, vp, vp]
         lib.pinn_term_residual_system.restype = ctypes.c_int
         lib.pinn_term_residual_system.argtypes = [P(PinnTermPdeSystem), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, vp, P(vp), vp, vp, vp]
+        lib.pinn_term_residual_system_mixed.restype = ctypes.c_int
+        lib.pinn_term_residual_system_mixed.argtypes = [P(PinnTermPdeSystemMixed), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, vp, P(vp), vp,
+                                                        vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         lib.pinn_face_losses.restype = ctypes.c_int

@@ -447,7 +447,11 @@ class SystemTermDesc:
     eq_weights: omega_e (default 1).  No mixed derivatives.  Wherever the engine takes an `AxisTermDesc` it takes a
     `SystemTermDesc` too and runs the chain: one component jets_forward per (field, axis with streams),
     term_residual_system, one component jets_backward per block.  Its residual tensor is (N, E) and its loss sum is
-    sum_e omega_e sum_n l(r_e,n)."""
+    sum_e omega_e sum_n l(r_e,n).  `MixedSystemTermDesc` below has the mixed derivatives."""
+
+    _STRUCT = _lib.PinnTermPdeSystem
+    _FACTORS = _lib.TERM_FACTOR_ND
+    _FACTOR_NOTE = "; mixed derivatives are not available in systems"
 
     def __init__(self, terms: Sequence[Sequence[object]], equation_of: Sequence[int], coef_values: Tensor, dimension: int,
                  n_fields: int, n_equations: int, nt: Sequence[int], nx: Sequence[Sequence[int]],
@@ -472,7 +476,7 @@ class SystemTermDesc:
         w = [1.0] * E if eq_weights is None else [float(v) for v in eq_weights]
         if len(w) != E or any(not (v >= 0.0 and v != float("inf")) for v in w):
             raise ValueError(f"eq_weights: {E} finite weights >= 0 (got {eq_weights})")
-        d = _lib.PinnTermPdeSystem()
+        d = self._STRUCT()
         d.dimension, d.n_fields, d.n_equations, d.n_terms = dim, C, E, len(terms)
         for c in range(C):
             d.time_order[c] = nt[c]
@@ -492,15 +496,14 @@ class SystemTermDesc:
             row = []
             for f, fac in enumerate(factors):
                 field, name = (0, fac) if isinstance(fac, str) else (int(fac[0]), fac[1])
-                if name not in _lib.TERM_FACTOR_ND:
-                    raise ValueError(f"term {m}: unknown factor '{name}' (one of {', '.join(_lib.TERM_FACTOR_ND)}; mixed derivatives "
-                                     "are not available in systems)")
+                if name not in self._FACTORS:
+                    raise ValueError(f"term {m}: unknown factor '{name}' (one of {', '.join(self._FACTORS)}{self._FACTOR_NOTE})")
                 coord = name in ("x", "y", "z", "t")
                 if isinstance(fac, str) and not coord:
                     raise ValueError(f"term {m}: factor '{name}' needs its field: (field index, '{name}')")
                 if not 0 <= field < C:
                     raise ValueError(f"term {m}: factor '{name}' names field {field} of {C}")
-                d.terms[m].factor[f] = _lib.PINN_SYSTEM_FACTOR(0 if coord else field, _lib.TERM_FACTOR_ND[name])
+                d.terms[m].factor[f] = _lib.PINN_SYSTEM_FACTOR(0 if coord else field, self._FACTORS[name])
                 row.append(name if coord else (field, name))
             norm.append(tuple(row))
         if coef_values.dtype != torch.float32 or not coef_values.is_contiguous() or coef_values.numel() < len(terms):
@@ -525,6 +528,70 @@ class SystemTermDesc:
             out.append((c, 0, self.nt[c], self.nx[c][0]))
             out += [(c, a, 0, self.nx[c][a]) for a in range(1, self.dimension) if self.nx[c][a] > 0]
         return out
+
+    def blocks(self) -> List[int]:
+        """Index in the block tables of the residual call of every launch of `launches()`, in its order: 3 field + axis."""
+        return [3 * c + a for c, a, _, _ in SystemTermDesc.launches(self)]
+
+
+class MixedSystemTermDesc(SystemTermDesc):
+    """A `SystemTermDesc` whose fields may name mixed derivatives (`pinn_term_residual_system_mixed`): its factor names plus
+    (field, "u_xy"), (field, "u_xz"), (field, "u_yz") (`_lib.TERM_FACTOR_SYSTEM_MIXED`).
+
+    The same arguments plus pair: per field the order 0 or 2 of the pairs (x, y), (x, z), (y, z), 0 for a pair beyond the
+    dimension.  A pair of order 2 of field c adds one component jet launch of the set (0, 2) along e_a + e_b (the P block,
+    entry 3 C + 3 c + k of the 6 C tables): u_ab = (P_2 - A_2 - B_2) / 2, so "u_ab" of a field needs its pair order 2 and its
+    order >= 2 on both axes.  "u_xt", third-order mixed factors, "u_aabb" and orders above 2 along y and z are not available."""
+
+    _STRUCT = _lib.PinnTermPdeSystemMixed
+    _FACTORS = _lib.TERM_FACTOR_SYSTEM_MIXED
+    _FACTOR_NOTE = "; u_xt, u_xxy, u_aabb and orders above 2 along y and z are not available in systems"
+
+    def __init__(self, terms: Sequence[Sequence[object]], equation_of: Sequence[int], coef_values: Tensor, dimension: int,
+                 n_fields: int, n_equations: int, nt: Sequence[int], nx: Sequence[Sequence[int]],
+                 pair: Optional[Sequence[Sequence[int]]] = None, eq_weights: Optional[Sequence[float]] = None, loss: str = "mse",
+                 huber_delta: float = 1.0):
+        super().__init__(terms, equation_of, coef_values, dimension, n_fields, n_equations, nt, nx, eq_weights, loss, huber_delta)
+        C, dim = self.n_fields, self.dimension
+        pair = ((0, 0, 0),) * C if pair is None else tuple(tuple(int(v) for v in row) + (0,) * (3 - len(row)) for row in pair)
+        if len(pair) != C:
+            raise ValueError(f"pair: one row of three pair orders per field ({C})")
+        for c in range(C):
+            if len(pair[c]) != 3 or any(v not in (0, 2) for v in pair[c]) or any(v and _PAIRS[k][1] >= dim for k, v in enumerate(pair[c])):
+                raise ValueError(f"field {c}: pair orders {pair[c]}: 0 or 2 for the pairs (x, y), (x, z), (y, z), 0 for a pair beyond "
+                                 f"the dimension ({dim})")
+            for k in range(3):
+                self.desc.pair_order[c][k] = pair[c][k]
+        for m, factors in enumerate(self.terms):
+            for fac in factors:
+                if not isinstance(fac, str) and fac[1] in _MIXED_2:
+                    c, k = fac[0], _MIXED_2[fac[1]]
+                    a, b = _PAIRS[k]
+                    if pair[c][k] != 2 or self.nx[c][a] < 2 or self.nx[c][b] < 2:
+                        raise ValueError(f"term {m}: '{fac[1]}' of field {c} needs pair order 2 and space order >= 2 on both axes of that "
+                                         f"field (pair orders {pair[c]}, space orders {self.nx[c]})")
+        self.pair = pair
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "MixedSystemTermDesc":
+        """The same program and the same coefficient tensor under another loss kind."""
+        return MixedSystemTermDesc(self.terms, self.equation_of, self.coef_values, self.dimension, self.n_fields, self.n_equations,
+                                   self.nt, self.nx, self.pair, self.eq_weights, loss, huber_delta)
+
+    def _direction(self, k: int) -> Tuple[int, ...]:
+        a, b = _PAIRS[k]
+        return tuple(1 if c in (a, b) else 0 for c in range(self.dimension))
+
+    def launches(self) -> List[Tuple[int, object, int, int]]:
+        """`SystemTermDesc.launches()`, then per field and pair of order 2 the entry (field, direction tuple e_a + e_b, 0, 2)."""
+        out: List[Tuple[int, object, int, int]] = list(SystemTermDesc.launches(self))
+        for c in range(self.n_fields):
+            out += [(c, self._direction(k), 0, 2) for k in range(3) if self.pair[c][k] == 2]
+        return out
+
+    def blocks(self) -> List[int]:
+        """Index in the 6 C tables of `pinn_term_residual_system_mixed` of every launch of `launches()`, in its order."""
+        C = self.n_fields
+        return SystemTermDesc.blocks(self) + [3 * C + 3 * c + k for c in range(C) for k in range(3) if self.pair[c][k] == 2]
 
 
 def pde_streams(pd) -> Tuple[int, int]:
@@ -787,28 +854,51 @@ def term_residual_system(td: SystemTermDesc, jets: Sequence[Optional[Tensor]], x
     have the shapes of the jets; every row the program never reads is zero, so each goes straight into `jets_backward`.
     loss_sum[0] += sum_e omega_e sum_n l(r_e,n), eq_loss_sums[e] += sum_n l(r_e,n), coef_grads[m] += sum_n rbar prod_f phi
     where given.  One launch, two with a sum; the residual is a transposed view of the (E, N) buffer the kernel writes."""
+    return _term_residual_system("term_residual_system", False, td, jets, x, t, grad_scale, residual_cotangent, want_residual, loss_sum,
+                                 want_cotangents, coef_grads, eq_loss_sums)
+
+
+def term_residual_system_mixed(td: MixedSystemTermDesc, jets: Sequence[Optional[Tensor]], x: Tensor, t: Tensor, grad_scale: float = 0.0,
+                               residual_cotangent: Optional[Tensor] = None, want_residual: bool = True,
+                               loss_sum: Optional[Tensor] = None, want_cotangents: bool = False,
+                               coef_grads: Optional[Tensor] = None,
+                               eq_loss_sums: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[List[Optional[Tensor]]]]:
+    """`pinn_term_residual_system_mixed`: `term_residual_system` on 6 C blocks — entry 3 c + a the axis block (c, a) as there,
+    entry 3 C + 3 c + k the (3, N) block of field c's launch along e_a + e_b for pair k, None where that pair order is 0.  The
+    cotangent blocks have the shapes of the jets (rows 0 and 1 of a P block are zero)."""
+    return _term_residual_system("term_residual_system_mixed", True, td, jets, x, t, grad_scale, residual_cotangent, want_residual,
+                                 loss_sum, want_cotangents, coef_grads, eq_loss_sums)
+
+
+def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t, grad_scale, residual_cotangent, want_residual,
+                          loss_sum, want_cotangents, coef_grads, eq_loss_sums):
+    """The body of `term_residual_system` / `term_residual_system_mixed`: the checks, the buffers and the one call."""
     lib = _lib.load()
     dim, C, E = td.dimension, td.n_fields, td.n_equations
-    jets = list(jets) + [None] * (3 * C - len(jets))
+    nb = _lib.PINN_SYSTEM_MIXED_BLOCKS(C) if mixed else 3 * C
+    jets = list(jets) + [None] * (nb - len(jets))
     dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums)
     rows = []
     for c in range(C):
         rows += [1 + td.nt[c] + td.nx[c][0]] + [(1 + td.nx[c][a]) if (a < dim and td.nx[c][a] > 0) else 0 for a in (1, 2)]
-    if len(jets) != 3 * C or jets[0] is None or jets[0].dim() != 2:
-        raise ValueError(f"term_residual_system: {3 * C} blocks, jets[0] the (1 + nt + nx[0], N) block of field 0's axis-0 launch")
+    if mixed:
+        rows += [3 if td.pair[c][k] == 2 else 0 for c in range(C) for k in range(3)]
+    if len(jets) != nb or jets[0] is None or jets[0].dim() != 2:
+        raise ValueError(f"{who}: {nb} blocks, jets[0] the (1 + nt + nx[0], N) block of field 0's axis-0 launch")
     N = jets[0].shape[1]
-    for b in range(3 * C):
+    for b in range(nb):
         j = jets[b]
         if (j is None) != (rows[b] == 0) or (j is not None and (tuple(j.shape) != (rows[b], N) or j.dtype != torch.float32
                                                                or not j.is_contiguous())):
-            raise ValueError(f"term_residual_system: block {b} (field {b // 3}, axis {b % 3}) must be "
+            where = f"field {b // 3}, axis {b % 3}" if b < 3 * C else f"field {(b - 3 * C) // 3}, pair {(b - 3 * C) % 3}"
+            raise ValueError(f"{who}: block {b} ({where}) must be "
                              f"{'None' if rows[b] == 0 else f'a contiguous float32 ({rows[b]}, {N}) tensor'}")
     x, t = _f32c(x.detach()), _f32c(t.detach())
     if x.numel() != N * dim or t.numel() != N:
-        raise ValueError(f"term_residual_system: x is (N, {dim}) and t holds N values (N = {N}; got {tuple(x.shape)}, {tuple(t.shape)})")
+        raise ValueError(f"{who}: x is (N, {dim}) and t holds N values (N = {N}; got {tuple(x.shape)}, {tuple(t.shape)})")
     if residual_cotangent is not None:
         if tuple(residual_cotangent.shape) != (N, E):
-            raise ValueError(f"term_residual_system: residual_cotangent is (N, E) = ({N}, {E}); got {tuple(residual_cotangent.shape)}")
+            raise ValueError(f"{who}: residual_cotangent is (N, E) = ({N}, {E}); got {tuple(residual_cotangent.shape)}")
         residual_cotangent = _f32c(residual_cotangent.t())  # (E, N), equation e at e N
     for tns in (loss_sum, coef_grads, eq_loss_sums):
         assert tns is None or (tns.dtype == torch.float32 and tns.is_contiguous())
@@ -821,34 +911,41 @@ def term_residual_system(td: SystemTermDesc, jets: Sequence[Optional[Tensor]], x
     reduce = loss_sum is not None or coef_grads is not None or eq_loss_sums is not None
     scratch = torch.empty(_lib.PINN_SYSTEM_SCRATCH_DOUBLES, dtype=torch.float64, device=dev) if reduce else None
     opt = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
-    jptr = (ctypes.c_void_p * (3 * C))(*[opt(j) for j in jets])
-    cptr = (ctypes.c_void_p * (3 * C))(*[opt(c) for c in cot]) if cot is not None else None
+    jptr = (ctypes.c_void_p * nb)(*[opt(j) for j in jets])
+    cptr = (ctypes.c_void_p * nb)(*[opt(c) for c in cot]) if cot is not None else None
+    entry = lib.pinn_term_residual_system_mixed if mixed else lib.pinn_term_residual_system
     with torch.cuda.device(dev):
-        _lib.check(lib.pinn_term_residual_system(ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(),
-                                                 N, float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum),
-                                                 opt(eq_loss_sums), cptr, opt(coef_grads), opt(scratch), _stream(dev)))
+        _lib.check(entry(ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), N, float(grad_scale),
+                         opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr, opt(coef_grads), opt(scratch),
+                         _stream(dev)))
     return (r.t() if r is not None else None), cot
-
-
-def _system_jets(prog: NetProgram, td: SystemTermDesc, x: Tensor, t: Tensor) -> List[Optional[Tensor]]:
-    """The forward half of a `SystemTermDesc` chain: one component jets_forward per (field, axis with streams)."""
-    if prog.n_outputs != td.n_fields:
-        raise ValueError(f"a system of {td.n_fields} fields needs a network with {td.n_fields} outputs (this one has {prog.n_outputs})")
-    jets: List[Optional[Tensor]] = [None] * (3 * td.n_fields)
-    for c, a, nt, nx in td.launches():
-        jets[3 * c + a] = jets_forward(prog, x, t, nt, nx, axis=a, component=c)
-    return jets
-
-
-def _system_backward(prog: NetProgram, td: SystemTermDesc, x: Tensor, t: Tensor, cot: Sequence[Optional[Tensor]], flat_grad: Tensor) -> None:
-    """The reverse half: one component jets_backward per block, all accumulating into the same flat gradient."""
-    for c, a, nt, nx in td.launches():
-        jets_backward(prog, x, t, nt, nx, cot[3 * c + a], flat_grad, axis=a, component=c)
 
 
 def _launch_line(key) -> dict:
     """The keyword of `jets_forward` / `jets_backward` for one entry of `launches()`: an axis, or a direction tuple."""
     return {"direction": key} if isinstance(key, tuple) else {"axis": key}
+
+
+def _term_residual_sys(td: SystemTermDesc, *args, **kwargs):
+    return (term_residual_system_mixed if isinstance(td, MixedSystemTermDesc) else term_residual_system)(td, *args, **kwargs)
+
+
+def _system_jets(prog: NetProgram, td: SystemTermDesc, x: Tensor, t: Tensor) -> List[Optional[Tensor]]:
+    """The forward half of a `SystemTermDesc` chain: one component jets_forward per (field, axis with streams) and, for a
+    `MixedSystemTermDesc`, per (field, pair of order 2) along the pair's direction."""
+    if prog.n_outputs != td.n_fields:
+        raise ValueError(f"a system of {td.n_fields} fields needs a network with {td.n_fields} outputs (this one has {prog.n_outputs})")
+    mixed = isinstance(td, MixedSystemTermDesc)
+    jets: List[Optional[Tensor]] = [None] * (_lib.PINN_SYSTEM_MIXED_BLOCKS(td.n_fields) if mixed else 3 * td.n_fields)
+    for b, (c, key, nt, nx) in zip(td.blocks(), td.launches()):
+        jets[b] = jets_forward(prog, x, t, nt, nx, component=c, **_launch_line(key))
+    return jets
+
+
+def _system_backward(prog: NetProgram, td: SystemTermDesc, x: Tensor, t: Tensor, cot: Sequence[Optional[Tensor]], flat_grad: Tensor) -> None:
+    """The reverse half: one component jets_backward per block, all accumulating into the same flat gradient."""
+    for b, (c, key, nt, nx) in zip(td.blocks(), td.launches()):
+        jets_backward(prog, x, t, nt, nx, cot[b], flat_grad, component=c, **_launch_line(key))
 
 
 def _launch_blocks(td: AxisTermDesc) -> List[int]:
@@ -886,7 +983,7 @@ def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: 
         s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
         if N == 0:
             return (torch.empty((0, pd.n_equations), dtype=torch.float32, device=dev) if want_residual else None), s
-        r, _ = term_residual_system(pd, _system_jets(prog, pd, x, t), x, t, want_residual=want_residual, loss_sum=s)
+        r, _ = _term_residual_sys(pd, _system_jets(prog, pd, x, t), x, t, want_residual=want_residual, loss_sum=s)
         return r, s
     if isinstance(pd, AxisTermDesc) and N:  # the chain over the axes: one jet launch each, then the element-wise residual
         s = torch.zeros(1, dtype=torch.float32, device=dev) if want_loss_sum else None
@@ -926,8 +1023,8 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
         s = loss_sum if loss_sum is not None else torch.zeros(1, dtype=torch.float32, device=dev)
         if N == 0:
             return (torch.empty((0, pd.n_equations), dtype=torch.float32, device=dev) if want_residual else None), s
-        r, cot = term_residual_system(pd, _system_jets(prog, pd, x, t), x, t, grad_scale=grad_scale, want_residual=want_residual,
-                                      loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
+        r, cot = _term_residual_sys(pd, _system_jets(prog, pd, x, t), x, t, grad_scale=grad_scale, want_residual=want_residual,
+                                    loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
         _system_backward(prog, pd, x, t, cot, flat_grad)
         return r, s
     if isinstance(pd, AxisTermDesc) and N:
@@ -1011,8 +1108,8 @@ def residual_backward(prog: NetProgram, pd, x: Tensor, t: Tensor, res_bar: Tenso
     if N == 0:
         return
     if isinstance(pd, SystemTermDesc):  # res_bar: (N, E), the cotangent of the (N, E) residual
-        _, cot = term_residual_system(pd, _system_jets(prog, pd, x, t), x, t, residual_cotangent=res_bar.reshape(N, pd.n_equations),
-                                      want_residual=False, want_cotangents=True)
+        _, cot = _term_residual_sys(pd, _system_jets(prog, pd, x, t), x, t, residual_cotangent=res_bar.reshape(N, pd.n_equations),
+                                    want_residual=False, want_cotangents=True)
         _system_backward(prog, pd, x, t, cot, flat_grad)
         return
     res_bar = _f32c(res_bar).reshape(-1)

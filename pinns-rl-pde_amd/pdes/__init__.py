@@ -9,6 +9,7 @@ from .term_pde import TermPDE  # noqa: F401
 from .term_pde_mixed import TermPDEMixed  # noqa: F401
 from .term_pde_nd import TermPDEnD  # noqa: F401
 from .term_pde_system import TermPDESystem  # noqa: F401
+from .term_pde_system_mixed import TermPDESystemMixed  # noqa: F401
 
 _BY_TYPE = {
     "heat": HeatEquation, "wave": WaveEquation, "burgers": BurgersEquation, "kdv": KdVEquation,

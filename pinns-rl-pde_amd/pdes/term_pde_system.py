@@ -10,7 +10,7 @@ launch (`engine.jets_forward(..., component=k)`): the layer-major engine with th
 and hands every (field, axis) block its cotangents for one component reverse sweep each.  Residuals, loss and gradient stay
 free of autograd, so the launch list, the captured step and the flat L-BFGS closure take such a system as they take
 `TermPDEnD`.  A component launch recomputes the trunk: a C-field system costs about C single-field chains.  Mixed derivatives
-are not available in systems.
+(`<field>_xy`) are not available here: `TermPDESystemMixed` (term_pde_system_mixed.py) has them.
 """
 
 from __future__ import annotations
@@ -37,7 +37,7 @@ PINN_MAX_POINT_TERMS = 8  # the loss terms one pinn_jet_losses call takes
 
 class TermPDESystem(PDEBase):
     """`TermPDESystem(config, fields, equations, initial_condition_fn, exact_solution_fn=None, equation_weights=None,
-    initial_condition_fields=None)` for `config.dimension` 1, 2 or 3.
+    initial_condition_fields=None)` for `config.dimension` 1, 2 or 3.  Mixed derivatives: `TermPDESystemMixed`.
 
     fields: 1 to 4 names, each an identifier without "_" and none of x, y, z, t; field k is output k of the model, and
         `config.output_dim` is set to their number.
@@ -69,6 +69,9 @@ class TermPDESystem(PDEBase):
     """
 
     KIND = "term_system"  # not a `_lib.PDE` kind: the descriptor is a `SystemTermDesc`
+    # the unknown-factor message: the names a field takes, and what is not available (a subclass with more names has its own)
+    _FACTOR_NAMES = "<field>, <field>_t, _tt, _x .. _xxxx, _y, _yy, _z, _zz, sin(<field>), cos(<field>)"
+    _FACTOR_NOTE = "mixed derivatives are not available in systems"
 
     def __init__(self, config: PDEConfig, fields: Sequence[str], equations: Sequence[Sequence[Tuple[Coef, Sequence[str]]]],
                  initial_condition_fn: Callable[[torch.Tensor], torch.Tensor],
@@ -117,8 +120,8 @@ class TermPDESystem(PDEBase):
                     parsed = self._parse_factor(f, index)
                     if parsed is None:
                         raise ValueError(f"{who}: equation {e}, term {m}: unknown factor '{f}' (a coordinate x, y, z, t, or one of "
-                                         f"<field>, <field>_t, _tt, _x .. _xxxx, _y, _yy, _z, _zz, sin(<field>), cos(<field>) with "
-                                         f"<field> in {', '.join(fields)}; mixed derivatives are not available in systems)")
+                                         f"{self._FACTOR_NAMES} with "
+                                         f"<field> in {', '.join(fields)}; {self._FACTOR_NOTE})")
                     c, name, t_order, (axis, order) = parsed
                     need = _COORDS[name] if c is None else (axis if order else 0)
                     if need >= dim:
@@ -128,6 +131,7 @@ class TermPDESystem(PDEBase):
                         continue
                     nt[c] = max(nt[c], t_order)
                     nx[c][axis] = max(nx[c][axis], order)
+                    self._factor_parsed(c, name, nx)
                     row.append((c, name))
                 if isinstance(coef, (tuple, list)):
                     if len(coef) != 2 or not isinstance(coef[1], str):
@@ -206,6 +210,10 @@ class TermPDESystem(PDEBase):
         self._coef_device: Optional[torch.device] = None
         self._descs: Dict[Any, Any] = {}
         self._points: Optional[Tuple[torch.device, Dict[str, Any]]] = None
+
+    def _factor_parsed(self, c: int, name: str, nx: List[List[int]]) -> None:
+        """Hook of the constructor's term loop, called for every field factor after its orders went into nx (the space orders per
+        field and axis, a list to be changed in place).  Nothing to do here."""
 
     @staticmethod
     def _parse_factor(f: str, index: Dict[str, int]):

@@ -3,7 +3,7 @@
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
                                [--term-pde] [--term-nd] [--term-mixed] [--causal M,EPS]
-                               [--system {gray_scott,navier_stokes}]
+                               [--system {gray_scott,navier_stokes,elasticity,elasticity_nomixed}]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -42,6 +42,13 @@ Gray-Scott in 1-D (two fields on the set (1, 2); N1 is one such field), S2 incom
 fields on (1, 2) + (0, 2) along y, the pressure on (1, 1) + (0, 1); N2 is one field on (1, 2) + (0, 2)).  Every field is a
 component launch on the layer-major engine, which recomputes the trunk.  After the step table it times every launch of the
 system's chain on its own, `pinn_term_residual_system` among them.
+
+`--system elasticity` runs S3: 2-D linear elasticity, fields (u, v), u_t = mu Lap u + (lambda + mu) (u_xx + v_xy), v_t = mu Lap v +
+(lambda + mu) (u_xy + v_yy), as a `TermPDESystemMixed` on fourier 4x128, Dirichlet faces — per field the launches along x, y and
+e_x + e_y.  `--system elasticity_nomixed` runs S4, the yardstick: the same system on `TermPDESystem` with the two mixed terms
+dropped (four launches per sweep against six).  After the step table every launch of the chain is timed on its own; for S4 also
+`pinn_term_residual_system_mixed` on the same blocks with all pair orders 0, beside `pinn_term_residual_system`: the cost of
+the larger LDS footprint.
 
 `--causal M,EPS` turns on the causal (time-weighted) residual loss (`training.causal_weighting`: M time bins, sharpness
 EPS): the autograd mode builds the weighted loss with torch ops on the residual tensor, the other two run the residual part
@@ -140,9 +147,37 @@ def _system(which):
     return f"{label} as TermPDESystem, fourier 4x128", net, P.TermPDESystem(pc, fields, eqs, ic, initial_condition_fields=icf), 49729
 
 
+def _elasticity_equations(mixed):
+    eqs = [[(1.0, ("u_t",)), ((-1.0, "mu"), ("u_xx",)), ((-1.0, "mu"), ("u_yy",)), ((-1.0, "a"), ("u_xx",)), ((-1.0, "a"), ("v_xy",))],
+           [(1.0, ("v_t",)), ((-1.0, "mu"), ("v_xx",)), ((-1.0, "mu"), ("v_yy",)), ((-1.0, "a"), ("u_xy",)), ((-1.0, "a"), ("v_yy",))]]
+    return eqs if mixed else [[tm for tm in eq if not tm[1][0].endswith("_xy")] for eq in eqs]
+
+
+def _elasticity(mixed):
+    """2-D linear elasticity (u, v) on fourier 4x128, 49 729 points, Dirichlet faces: as a `TermPDESystemMixed`, or — the two mixed
+    terms dropped — as a `TermPDESystem`."""
+    mu, lam = 0.05, 0.08
+    kappa = 2 * math.pi**2 * (lam + 2 * mu)
+
+    def exact(x, t):  # (u, v) = grad phi, phi = exp(-kappa t) sin(pi x) sin(pi y): curl-free, so grad div = Laplacian
+        e = math.pi * torch.exp(-kappa * t[:, 0])
+        return torch.stack([e * torch.cos(math.pi * x[:, 0]) * torch.sin(math.pi * x[:, 1]),
+                            e * torch.sin(math.pi * x[:, 0]) * torch.cos(math.pi * x[:, 1])], 1)
+
+    net = B.model("fourier", 128, 4, "tanh", input_dim=3, output_dim=2)
+    pc = P.PDEConfig(name="elasticity", domain=[(0.0, 1.0)] * 2, time_domain=(0.0, 1.0), parameters={"mu": mu, "a": lam + mu},
+                     boundary_conditions={"dirichlet": {"type": "fixed", "value": 0.0}}, initial_condition={}, exact_solution={},
+                     dimension=2, device=B.dev)
+    cls = P.TermPDESystemMixed if mixed else P.TermPDESystem
+    ic = lambda x: exact(x, torch.zeros(x.shape[0], 1, device=x.device))  # noqa: E731
+    label = "Elasticity 2D (u, v) as TermPDESystemMixed" if mixed else "Elasticity 2D without v_xy, u_xy as TermPDESystem"
+    return f"{label}, fourier 4x128", net, cls(pc, ("u", "v"), _elasticity_equations(mixed), ic, exact_solution_fn=exact), 49729
+
+
 ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2),
               "M1": lambda: _heat_nd(2), "M2": lambda: _mixed_2d("aniso"), "M3": lambda: _mixed_2d("ch"),
-              "S1": lambda: _system("gray_scott"), "S2": lambda: _system("navier_stokes")}
+              "S1": lambda: _system("gray_scott"), "S2": lambda: _system("navier_stokes"),
+              "S3": lambda: _elasticity(True), "S4": lambda: _elasticity(False)}
 
 
 def build(tag, adaptive="none", smoothness=0.0, term_pde=False, causal=None):
@@ -323,8 +358,9 @@ def time_nd_launches(tag, iters=20):
 
 
 def time_system_launches(tag, iters=20):
-    """Device time of every launch of a system's chain on its own: one component jet launch per (field, axis) forward, the
-    element-wise residuals of all equations, one component reverse sweep per block."""
+    """Device time of every launch of a system's chain on its own: one component jet launch per (field, axis) — and, with mixed
+    derivatives, per (field, direction) — forward, the element-wise residuals of all equations, one component reverse sweep per
+    block."""
     torch.manual_seed(0)
     name, net, eq, n_req = ND_CONFIGS[tag]()
     x, t = eq._sample_uniform(n_req)
@@ -332,16 +368,25 @@ def time_system_launches(tag, iters=20):
     n = int(x.shape[0])
     flat, s = E.new_flat_grad(prog, B.dev), torch.zeros(1, device=B.dev)
     jets = E._system_jets(prog, td, x, t)
-    _, cot = E.term_residual_system(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
+    entry = "pinn_term_residual_system_mixed" if isinstance(td, E.MixedSystemTermDesc) else "pinn_term_residual_system"
+    _, cot = E._term_residual_sys(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
     calls = []
-    for c, a, nt, nx in td.launches():
-        who = f"field {eq.fields[c]}, axis {a}, set ({nt}, {nx})"
-        calls.append((f"pinn_jet_forward, {who}", lambda c=c, a=a, nt=nt, nx=nx: E.jets_forward(prog, x, t, nt, nx, axis=a, component=c)))
+    for b, (c, key, nt, nx) in zip(td.blocks(), td.launches()):
+        line = E._launch_line(key)
+        who = f"field {eq.fields[c]}, {'direction' if isinstance(key, tuple) else 'axis'} {key}, set ({nt}, {nx})"
+        calls.append((f"pinn_jet_forward, {who}", lambda c=c, nt=nt, nx=nx, line=line: E.jets_forward(prog, x, t, nt, nx, component=c, **line)))
         calls.append((f"pinn_jet_backward, {who}",
-                      lambda c=c, a=a, nt=nt, nx=nx: E.jets_backward(prog, x, t, nt, nx, cot[3 * c + a], flat, axis=a, component=c)))
-    calls.append(("pinn_term_residual_system (loss sum + cotangents, two launches)",
-                  lambda: E.term_residual_system(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
-    calls.append(("pinn_term_residual_system (residuals only, one launch)", lambda: E.term_residual_system(td, jets, x, t)))
+                      lambda c=c, b=b, nt=nt, nx=nx, line=line: E.jets_backward(prog, x, t, nt, nx, cot[b], flat, component=c, **line)))
+    calls.append((f"{entry} (loss sum + cotangents, two launches)",
+                  lambda: E._term_residual_sys(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
+    calls.append((f"{entry} (residuals only, one launch)", lambda: E._term_residual_sys(td, jets, x, t)))
+    if tag == "S4":  # the same program and blocks through the mixed entry point with all pair orders 0: the larger LDS footprint
+        tm = E.MixedSystemTermDesc(td.terms, td.equation_of, td.coef_values, td.dimension, td.n_fields, td.n_equations, td.nt, td.nx, None,
+                                   td.eq_weights)
+        calls.append(("pinn_term_residual_system_mixed, all pair orders 0 (loss sum + cotangents, two launches)",
+                      lambda: E.term_residual_system_mixed(tm, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
+        calls.append(("pinn_term_residual_system_mixed, all pair orders 0 (residuals only, one launch)",
+                      lambda: E.term_residual_system_mixed(tm, jets, x, t)))
     calls.append(("the chain through engine.residual_loss_grad", lambda: E.residual_loss_grad(prog, td, x, t, 1.0 / n, flat, loss_sum=s)))
     print()
     print(f"| {tag} launch ({n} points) | ms |")
@@ -413,11 +458,12 @@ def main():
     ap.add_argument("--term-nd", action="store_true", help="N1, N2: the heat Laplacian in 1-D (TermPDE) and 2-D (TermPDEnD), fourier 4x128")
     ap.add_argument("--term-mixed", action="store_true",
                     help="M1, M2, M3: 2-D heat (TermPDEnD), anisotropic diffusion and Cahn-Hilliard (TermPDEMixed), fourier 4x128")
-    ap.add_argument("--system", choices=["gray_scott", "navier_stokes"], default=None,
-                    help="N1, S1 (gray_scott) or N2, S2 (navier_stokes): a TermPDESystem beside the single-field step, fourier 4x128")
+    ap.add_argument("--system", choices=["gray_scott", "navier_stokes", "elasticity", "elasticity_nomixed"], default=None,
+                    help="N1, S1 (gray_scott) or N2, S2 (navier_stokes): a TermPDESystem beside the single-field step; S3 (elasticity): 2-D "
+                         "elasticity as a TermPDESystemMixed; S4 (elasticity_nomixed): the same without its mixed terms; fourier 4x128")
     args = ap.parse_args()
     if args.system and args.configs == "C1,C2,C3,C4":
-        args.configs = "N1,S1" if args.system == "gray_scott" else "N2,S2"
+        args.configs = {"gray_scott": "N1,S1", "navier_stokes": "N2,S2", "elasticity": "S3", "elasticity_nomixed": "S4"}[args.system]
     if args.term_nd and args.configs == "C1,C2,C3,C4":
         args.configs = "N1,N2"
     if args.term_mixed and args.configs == "C1,C2,C3,C4":
@@ -480,7 +526,7 @@ def main():
             time_term_launches(tag)
         if args.term_mixed and tag in ND_CONFIGS:
             time_nd_launches(tag)
-        if args.system and tag in ("S1", "S2"):
+        if args.system and tag in ("S1", "S2", "S3", "S4"):
             time_system_launches(tag)
         if args.system and tag == "N2":
             time_nd_launches(tag)
