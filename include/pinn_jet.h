@@ -781,6 +781,53 @@ int pinn_term_residual_system_mixed(const PinnTermPdeSystemMixed* pde, const flo
                                     float* residual_out, float* loss_sum_out, float* eq_loss_sums, float* const* jet_cotangents,
                                     float* coef_grads, double* scratch, void* stream);
 
+/* ---- term residuals of coupled systems with known functions of (x, t) as factors -------------------------------------------
+ * pinn_term_residual_system_mixed plus up to PINN_SYSTEM_MAX_FUNCTIONS factors g_k(x, t) that the caller has evaluated at the
+ * points: a source term f(x, t), a coefficient that varies in space (kappa(x, y) u_xx), a given velocity field (a(x, y) c_x), a
+ * body force.  r_e = sum_m c_m prod_f phi_{m,f} with phi a stream of a field, a coordinate, sin / cos of a field or g_k.  The
+ * factor byte stays PINN_SYSTEM_FACTOR(field, code); every code of pinn_term_residual_system_mixed keeps its meaning and
+ * PINN_TERM_FN0 .. PINN_TERM_FN3 (27 .. 30) name g_0 .. g_3; the field bits are ignored, as for coordinates.  Code 31 is unknown,
+ * and the codes 17 .. 20 and 24 .. 26 stay refused by name.
+ *   fn_values          n_functions x N device floats, function k at fn_values + k N, read at launch time.  A row that no term
+ *                      names is never read (a host-made, wave-uniform mask); may be NULL when no term names a function.
+ *   sweep 1            a function factor is a factor like PINN_TERM_X: it enters the product ((c_m phi_0) phi_1) ... at its position.
+ *   sweep 2            a function factor contributes no derivative summand and is no cotangent target; it stays in the products
+ *                      c_m prod_{g != f} phi_g of the other factors' derivatives and in coef_grads[m] = sum_n rbar prod_f phi_{m,f}.
+ * Everything else — the 6 C block tables, u_ab and its cotangents, residual_out (E x N), residual_cotangent, loss_sum_out,
+ * eq_loss_sums, coef_grads, grad_scale * eq_weight[e] rounded once on the host, the loss kinds, scratch
+ * (PINN_SYSTEM_SCRATCH_DOUBLES), per-block double partials added in block order by the finish launch, no atomics, one launch
+ * when no sum is wanted, N == 0 a no-op — as pinn_term_residual_system_mixed: with no function factor in the program the
+ * residuals and every cotangent block are bit-identical to it on the same inputs, whatever n_functions is.
+ * Checked on the host before any HIP call: every check of pinn_term_residual_system_mixed; n_functions outside [0, 4]; a code
+ * 27 + k with k >= n_functions; null fn_values under a named function with N > 0: PINN_ERR_BAD_DESC, the message naming the
+ * term. */
+#define PINN_SYSTEM_MAX_FUNCTIONS 4
+#define PINN_TERM_FN0 27
+#define PINN_TERM_FN1 28
+#define PINN_TERM_FN2 29
+#define PINN_TERM_FN3 30
+
+typedef struct PinnTermPdeSystemFn {
+  int32_t dimension;                                   /* 1 .. 3 (a mixed factor needs 2 or 3) */
+  int32_t n_fields;
+  int32_t n_equations;
+  int32_t time_order[PINN_SYSTEM_MAX_FIELDS];
+  int32_t space_order[PINN_SYSTEM_MAX_FIELDS][3];
+  int32_t n_terms;
+  int32_t equation_of[PINN_SYSTEM_MAX_TERMS];
+  float eq_weight[PINN_SYSTEM_MAX_EQUATIONS];
+  int32_t loss;
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_SYSTEM_MAX_TERMS];        /* factor[f] = PINN_SYSTEM_FACTOR(field, code), code 0 .. 16, 21 .. 23, 27 .. 30 */
+  int32_t pair_order[PINN_SYSTEM_MAX_FIELDS][3];       /* per field, pairs (x,y), (x,z), (y,z): 0 or 2 */
+  int32_t n_functions;                                 /* 0 .. PINN_SYSTEM_MAX_FUNCTIONS: rows of fn_values */
+} PinnTermPdeSystemFn;
+
+int pinn_term_residual_system_fn(const PinnTermPdeSystemFn* pde, const float* coef_values, const float* const* jets,
+                                 const float* x, const float* t, const float* fn_values, int64_t N, float grad_scale,
+                                 const float* residual_cotangent, float* residual_out, float* loss_sum_out, float* eq_loss_sums,
+                                 float* const* jet_cotangents, float* coef_grads, double* scratch, void* stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.
  * lr and step are DEVICE scalars (step = number of steps taken so far, incremented by the call) so that a captured

@@ -74,6 +74,10 @@ PINN_SYSTEM_MAX_TERMS = 32
 PINN_SYSTEM_SCRATCH_DOUBLES = 64 * (4 + 32)
 # pinn_term_residual_system_mixed: the factor codes of a system whose fields may name u_xy, u_xz, u_yz (codes 21 .. 23)
 TERM_FACTOR_SYSTEM_MIXED = dict(TERM_FACTOR_ND, **{"u_xy": 21, "u_xz": 22, "u_yz": 23})
+# pinn_term_residual_system_fn: up to four known functions g_k(x, t) as factors (codes 27 .. 30; "fn0" .. "fn3")
+PINN_SYSTEM_MAX_FUNCTIONS = 4
+PINN_TERM_FN0 = 27
+TERM_FACTOR_SYSTEM_FN = dict(TERM_FACTOR_SYSTEM_MIXED, **{f"fn{k}": PINN_TERM_FN0 + k for k in range(PINN_SYSTEM_MAX_FUNCTIONS)})
 # pinn_face_losses: the loss terms of per-face boundary conditions
 PINN_FACE_MAX_TERMS = 32
 PINN_FACE_SCRATCH_DOUBLES = 64 * PINN_FACE_MAX_TERMS
@@ -102,7 +106,7 @@ EXPORTS = (
     "pinn_lbfgs_scratch_bytes", "pinn_lbfgs_direction", "pinn_lbfgs_eval_stats", "pinn_fd_stencil_points", "pinn_fd_smoothness",
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
     "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system", "pinn_residual_unit_name",
-    "pinn_face_losses", "pinn_term_residual_system_mixed",
+    "pinn_face_losses", "pinn_term_residual_system_mixed", "pinn_term_residual_system_fn",
 )
 
 
@@ -161,6 +165,10 @@ class PinnTermPdeSystem(ctypes.Structure):
 
 class PinnTermPdeSystemMixed(ctypes.Structure):
     _fields_ = PinnTermPdeSystem._fields_ + [("pair_order", (ctypes.c_int32 * 3) * PINN_SYSTEM_MAX_FIELDS)]
+
+
+class PinnTermPdeSystemFn(ctypes.Structure):
+    _fields_ = PinnTermPdeSystemMixed._fields_ + [("n_functions", ctypes.c_int32)]
 
 
 class PinnFaceTerm(ctypes.Structure):
@@ -312,6 +320,9 @@ def load():
         lib.pinn_term_residual_system_mixed.restype = ctypes.c_int
         lib.pinn_term_residual_system_mixed.argtypes = [P(PinnTermPdeSystemMixed), vp, P(vp), vp, vp, i64, f32, vp, vp, vp, vp, P(vp), vp,
                                                         vp, vp]
+        lib.pinn_term_residual_system_fn.restype = ctypes.c_int
+        lib.pinn_term_residual_system_fn.argtypes = [P(PinnTermPdeSystemFn), vp, P(vp), vp, vp, vp, i64, f32, vp, vp, vp, vp, P(vp), vp,
+                                                     vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         lib.pinn_face_losses.restype = ctypes.c_int

@@ -14,7 +14,7 @@ back to eager PyTorch.
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -452,6 +452,7 @@ class SystemTermDesc:
     _STRUCT = _lib.PinnTermPdeSystem
     _FACTORS = _lib.TERM_FACTOR_ND
     _FACTOR_NOTE = "; mixed derivatives are not available in systems"
+    _FIELDLESS: Tuple[str, ...] = ("x", "y", "z", "t")  # the factors that are given without a field
 
     def __init__(self, terms: Sequence[Sequence[object]], equation_of: Sequence[int], coef_values: Tensor, dimension: int,
                  n_fields: int, n_equations: int, nt: Sequence[int], nx: Sequence[Sequence[int]],
@@ -498,7 +499,7 @@ class SystemTermDesc:
                 field, name = (0, fac) if isinstance(fac, str) else (int(fac[0]), fac[1])
                 if name not in self._FACTORS:
                     raise ValueError(f"term {m}: unknown factor '{name}' (one of {', '.join(self._FACTORS)}{self._FACTOR_NOTE})")
-                coord = name in ("x", "y", "z", "t")
+                coord = name in self._FIELDLESS
                 if isinstance(fac, str) and not coord:
                     raise ValueError(f"term {m}: factor '{name}' needs its field: (field index, '{name}')")
                 if not 0 <= field < C:
@@ -592,6 +593,64 @@ class MixedSystemTermDesc(SystemTermDesc):
         """Index in the 6 C tables of `pinn_term_residual_system_mixed` of every launch of `launches()`, in its order."""
         C = self.n_fields
         return SystemTermDesc.blocks(self) + [3 * C + 3 * c + k for c in range(C) for k in range(3) if self.pair[c][k] == 2]
+
+
+class FnSystemTermDesc(MixedSystemTermDesc):
+    """A `MixedSystemTermDesc` whose terms may name known functions of (x, t) (`pinn_term_residual_system_fn`): its factor
+    names plus "fn0" .. "fn3" (`_lib.TERM_FACTOR_SYSTEM_FN`), given like a coordinate, without a field.
+
+    The same arguments plus functions: at most four callables g_k(x: (N, dimension), t: (N, 1)) -> (N,), the convention of the
+    value callables of `face_conditions`; "fn<k>" needs k < len(functions).  A function is a factor like "x": it takes part in
+    the products and has no cotangent.  `launches()` and `blocks()` are the parent's: a function adds no network launch.  The
+    engine evaluates `fn_values(x, t)` once per call of the element-wise kernel, so under a captured step a function must be
+    pure device torch ops without a host read.  A function that no term names is evaluated all the same (and never read by the
+    kernel)."""
+
+    _STRUCT = _lib.PinnTermPdeSystemFn
+    _FACTORS = _lib.TERM_FACTOR_SYSTEM_FN
+    _FIELDLESS = SystemTermDesc._FIELDLESS + tuple(f"fn{k}" for k in range(_lib.PINN_SYSTEM_MAX_FUNCTIONS))
+
+    def __init__(self, terms: Sequence[Sequence[object]], equation_of: Sequence[int], coef_values: Tensor, dimension: int,
+                 n_fields: int, n_equations: int, nt: Sequence[int], nx: Sequence[Sequence[int]],
+                 pair: Optional[Sequence[Sequence[int]]] = None, functions: Sequence[Callable] = (),
+                 eq_weights: Optional[Sequence[float]] = None, loss: str = "mse", huber_delta: float = 1.0,
+                 function_names: Optional[Sequence[str]] = None):
+        functions = tuple(functions)
+        if len(functions) > _lib.PINN_SYSTEM_MAX_FUNCTIONS:
+            raise ValueError(f"functions: at most {_lib.PINN_SYSTEM_MAX_FUNCTIONS} known functions (got {len(functions)})")
+        for k, g in enumerate(functions):
+            if not callable(g):
+                raise ValueError(f"functions[{k}] is not callable: g(x: (N, dim), t: (N, 1)) -> (N,)")
+        names = tuple(f"fn{k}" for k in range(len(functions))) if function_names is None else tuple(str(v) for v in function_names)
+        if len(names) != len(functions):
+            raise ValueError(f"function_names: one name per function ({len(functions)})")
+        super().__init__(terms, equation_of, coef_values, dimension, n_fields, n_equations, nt, nx, pair, eq_weights, loss, huber_delta)
+        for m, factors in enumerate(self.terms):
+            for fac in factors:
+                if isinstance(fac, str) and fac.startswith("fn") and int(fac[2:]) >= len(functions):
+                    raise ValueError(f"term {m}: factor '{fac}' names function {int(fac[2:])} of {len(functions)}")
+        self.desc.n_functions = len(functions)
+        self.functions, self.function_names = functions, names
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "FnSystemTermDesc":
+        """The same program, the same coefficient tensor and the same functions under another loss kind."""
+        return FnSystemTermDesc(self.terms, self.equation_of, self.coef_values, self.dimension, self.n_fields, self.n_equations,
+                                self.nt, self.nx, self.pair, self.functions, self.eq_weights, loss, huber_delta, self.function_names)
+
+    def fn_values(self, x: Tensor, t: Tensor) -> Tensor:
+        """Every function at the points, under `torch.no_grad()`: one contiguous float32 (K, N) tensor on the points' device, row k
+        the values of function k (what `pinn_term_residual_system_fn` reads as fn_values)."""
+        N = int(t.numel())
+        out = torch.empty((len(self.functions), N), dtype=torch.float32, device=x.device)
+        with torch.no_grad():
+            xs, ts = x.detach().reshape(N, self.dimension), t.detach().reshape(N, 1)
+            for k, g in enumerate(self.functions):
+                v = g(xs, ts)
+                if not isinstance(v, Tensor) or tuple(v.shape) != (N,):
+                    got = tuple(v.shape) if isinstance(v, Tensor) else type(v).__name__
+                    raise ValueError(f"function {k} ('{self.function_names[k]}') returned {got}, expected a tensor of shape ({N},)")
+                out[k].copy_(v)
+        return out
 
 
 def pde_streams(pd) -> Tuple[int, int]:
@@ -870,14 +929,33 @@ def term_residual_system_mixed(td: MixedSystemTermDesc, jets: Sequence[Optional[
                                  loss_sum, want_cotangents, coef_grads, eq_loss_sums)
 
 
+def term_residual_system_fn(td: FnSystemTermDesc, jets: Sequence[Optional[Tensor]], fn_values: Optional[Tensor], x: Tensor, t: Tensor,
+                            grad_scale: float = 0.0, residual_cotangent: Optional[Tensor] = None, want_residual: bool = True,
+                            loss_sum: Optional[Tensor] = None, want_cotangents: bool = False, coef_grads: Optional[Tensor] = None,
+                            eq_loss_sums: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[List[Optional[Tensor]]]]:
+    """`pinn_term_residual_system_fn`: `term_residual_system_mixed` with the function values given explicitly — fn_values a
+    contiguous float32 (len(td.functions), N) tensor on the device of the jets (`td.fn_values(x, t)`), row k function k; None
+    only where the descriptor has no function.  The kernel reads it at launch time, and only the rows some term names."""
+    K = len(td.functions)
+    if fn_values is None:
+        if K:
+            raise ValueError(f"term_residual_system_fn: fn_values is None but the descriptor has {K} functions")
+    elif (fn_values.dim() != 2 or fn_values.shape[0] != K or fn_values.dtype != torch.float32 or not fn_values.is_contiguous()):
+        raise ValueError(f"term_residual_system_fn: fn_values must be a contiguous float32 ({K}, N) tensor "
+                         f"(got {fn_values.dtype} {tuple(fn_values.shape)})")
+    return _term_residual_system("term_residual_system_fn", True, td, jets, x, t, grad_scale, residual_cotangent, want_residual,
+                                 loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=fn_values, with_fn=True)
+
+
 def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t, grad_scale, residual_cotangent, want_residual,
-                          loss_sum, want_cotangents, coef_grads, eq_loss_sums):
-    """The body of `term_residual_system` / `term_residual_system_mixed`: the checks, the buffers and the one call."""
+                          loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=None, with_fn=False):
+    """The body of `term_residual_system` / `term_residual_system_mixed` / `term_residual_system_fn`: the checks, the buffers and
+    the one call."""
     lib = _lib.load()
     dim, C, E = td.dimension, td.n_fields, td.n_equations
     nb = _lib.PINN_SYSTEM_MIXED_BLOCKS(C) if mixed else 3 * C
     jets = list(jets) + [None] * (nb - len(jets))
-    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums)
+    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums, fn_values)
     rows = []
     for c in range(C):
         rows += [1 + td.nt[c] + td.nx[c][0]] + [(1 + td.nx[c][a]) if (a < dim and td.nx[c][a] > 0) else 0 for a in (1, 2)]
@@ -896,6 +974,8 @@ def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t,
     x, t = _f32c(x.detach()), _f32c(t.detach())
     if x.numel() != N * dim or t.numel() != N:
         raise ValueError(f"{who}: x is (N, {dim}) and t holds N values (N = {N}; got {tuple(x.shape)}, {tuple(t.shape)})")
+    if fn_values is not None and fn_values.shape[1] != N:
+        raise ValueError(f"{who}: fn_values holds {fn_values.shape[1]} values per function, the jets {N}")
     if residual_cotangent is not None:
         if tuple(residual_cotangent.shape) != (N, E):
             raise ValueError(f"{who}: residual_cotangent is (N, E) = ({N}, {E}); got {tuple(residual_cotangent.shape)}")
@@ -915,9 +995,14 @@ def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t,
     cptr = (ctypes.c_void_p * nb)(*[opt(c) for c in cot]) if cot is not None else None
     entry = lib.pinn_term_residual_system_mixed if mixed else lib.pinn_term_residual_system
     with torch.cuda.device(dev):
-        _lib.check(entry(ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), N, float(grad_scale),
-                         opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr, opt(coef_grads), opt(scratch),
-                         _stream(dev)))
+        if with_fn:
+            _lib.check(lib.pinn_term_residual_system_fn(
+                ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), opt(fn_values), N, float(grad_scale),
+                opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr, opt(coef_grads), opt(scratch), _stream(dev)))
+        else:
+            _lib.check(entry(ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), N, float(grad_scale),
+                             opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr, opt(coef_grads), opt(scratch),
+                             _stream(dev)))
     return (r.t() if r is not None else None), cot
 
 
@@ -926,8 +1011,12 @@ def _launch_line(key) -> dict:
     return {"direction": key} if isinstance(key, tuple) else {"axis": key}
 
 
-def _term_residual_sys(td: SystemTermDesc, *args, **kwargs):
-    return (term_residual_system_mixed if isinstance(td, MixedSystemTermDesc) else term_residual_system)(td, *args, **kwargs)
+def _term_residual_sys(td: SystemTermDesc, jets, x, t, **kwargs):
+    """The element-wise kernel of a system descriptor: the entry point of its class.  A `FnSystemTermDesc` has its functions
+    evaluated here, once per call."""
+    if isinstance(td, FnSystemTermDesc):
+        return term_residual_system_fn(td, jets, td.fn_values(x, t) if td.functions else None, x, t, **kwargs)
+    return (term_residual_system_mixed if isinstance(td, MixedSystemTermDesc) else term_residual_system)(td, jets, x, t, **kwargs)
 
 
 def _system_jets(prog: NetProgram, td: SystemTermDesc, x: Tensor, t: Tensor) -> List[Optional[Tensor]]:

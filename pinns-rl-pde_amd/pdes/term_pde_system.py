@@ -45,6 +45,21 @@ class TermPDESystem(PDEBase):
         most 32 terms of at most 4 factors over all equations.  Factor names: "<field>", "<field>_t", "<field>_tt",
         "<field>_x" .. "<field>_xxxx", "<field>_y", "<field>_yy", "<field>_z", "<field>_zz", "sin(<field>)", "cos(<field>)", "x",
         "y", "z", "t".  Per field the smallest compiled stream set that holds its factors is launched.
+    functions: {name: g} with at most 4 entries: known functions g(x: (n, dim), t: (n, 1)) -> (n,) (the convention of the value
+        callables of `face_conditions`) that the terms may name as factors — a source f(x, t), a coefficient kappa(x, y), a
+        velocity field, a body force.  A name is an identifier without "_", none of x, y, z, t, sin, cos and no field name; the
+        factor "<name>" is the function's value at the point (factor code 27 + k, k the position in the mapping).  A function
+        is a factor like a coordinate: it takes part in the products and nothing is differentiated through it — the residual
+        has no derivative with respect to x and t through a function, as it has none through a coordinate factor or through the
+        network: `compute_residual` detaches the points, they are constants of the residual's graph, and `x.requires_grad`
+        yields no gradient through the residual, with functions as without.  Every function is evaluated once per residual call under
+        `torch.no_grad()`, also one that no term names.  Under a captured training step a function must be pure device torch ops
+        without a host read (no `.item()`, no Python branch on a tensor): torch's own capture error is the refusal.  A function
+        may close over a device tensor, and rewriting that tensor in place changes the eager step and the replay.  With
+        functions the descriptor is an `engine.FnSystemTermDesc` (`pinn_term_residual_system_fn`); without, it is what it was.
+        Forced heat in 1-D, u_t - u_xx = f:
+            TermPDESystem(cfg, ("u",), [[(1.0, ("u_t",)), (-1.0, ("u_xx",)), (-1.0, ("f",))]], ic,
+                          functions={"f": lambda x, t: torch.exp(-t[:, 0]) * torch.sin(math.pi * x[:, 0]) * (math.pi**2 - 1)})
     equation_weights: omega_e >= 0 (default 1): the residual loss is sum_e omega_e mean l(r_e).
     initial_condition_fn(x: (n, dim)) -> (n, len(initial_condition_fields)); initial_condition_fields defaults to all fields.
     exact_solution_fn(x, t) -> (n, C): enables `validate()`.
@@ -78,7 +93,8 @@ class TermPDESystem(PDEBase):
                  exact_solution_fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
                  equation_weights: Optional[Sequence[float]] = None, initial_condition_fields: Optional[Sequence[str]] = None,
                  boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32,
-                 face_conditions: Optional[Dict[str, Any]] = None, **kwargs):
+                 face_conditions: Optional[Dict[str, Any]] = None,
+                 functions: Optional[Dict[str, Callable[[torch.Tensor, torch.Tensor], torch.Tensor]]] = None, **kwargs):
         who = type(self).__name__
         dim = int(getattr(config, "dimension", 1))
         if dim not in (1, 2, 3):
@@ -104,6 +120,18 @@ class TermPDESystem(PDEBase):
         C = len(fields)
         index = {name: c for c, name in enumerate(fields)}
         self.fields = fields
+        functions = dict(functions or {})
+        if len(functions) > _lib.PINN_SYSTEM_MAX_FUNCTIONS:
+            raise ValueError(f"{who}: {len(functions)} functions; a system names at most {_lib.PINN_SYSTEM_MAX_FUNCTIONS}")
+        for name, g in functions.items():
+            if (not isinstance(name, str) or not name.isidentifier() or "_" in name or name in _COORDS or name in index
+                    or name in ("sin", "cos")):
+                raise ValueError(f"{who}: function name {name!r}: an identifier without '_' that is none of x, y, z, t, sin, cos and "
+                                 f"no field name ({', '.join(fields)})")
+            if not callable(g):
+                raise TypeError(f"{who}: function '{name}' is not callable: g(x: (n, dim), t: (n, 1)) -> (n,)")
+        self._functions = tuple(functions.items())  # (name, callable); function k is factor code 27 + k
+        fn_index = {name: k for k, name in enumerate(functions)}
         self._term_coefs: List[Coef] = []
         self._term_factors: List[Tuple[object, ...]] = []
         self._equation_of: List[int] = []
@@ -117,6 +145,9 @@ class TermPDESystem(PDEBase):
                                      f"{_lib.PINN_TERM_MAX_FACTORS}")
                 row = []
                 for f in factors:
+                    if isinstance(f, str) and f in fn_index:  # a known function: a factor like a coordinate
+                        row.append(f"fn{fn_index[f]}")
+                        continue
                     parsed = self._parse_factor(f, index)
                     if parsed is None:
                         raise ValueError(f"{who}: equation {e}, term {m}: unknown factor '{f}' (a coordinate x, y, z, t, or one of "
@@ -256,7 +287,20 @@ class TermPDESystem(PDEBase):
             self._descs = {}
         return self._coef_values
 
+    def _fn_desc(self, loss: str, delta: float) -> "_E.FnSystemTermDesc":
+        """The descriptor of a problem with functions: a `FnSystemTermDesc` (here with all pair orders 0)."""
+        cv = self.coef_values
+        key = (loss, float(delta))
+        if key not in self._descs:
+            self._descs[key] = _E.FnSystemTermDesc(self._term_factors, self._equation_of, cv, self.dimension, self.n_fields,
+                                                   self.n_equations, self._nt, self._nx, getattr(self, "_pair", None),
+                                                   [g for _, g in self._functions], self._eq_weights, loss, delta,
+                                                   [name for name, _ in self._functions])
+        return self._descs[key]
+
     def _term_desc(self, loss: str, delta: float) -> "_E.SystemTermDesc":
+        if self._functions:
+            return self._fn_desc(loss, delta)
         cv = self.coef_values
         key = (loss, float(delta))
         if key not in self._descs:

@@ -76,6 +76,8 @@ class TermPDESystemMixed(TermPDESystem):
                 self._pair_rows[c][k] = 2
 
     def _term_desc(self, loss: str, delta: float) -> "_E.MixedSystemTermDesc":
+        if self._functions:  # known functions as factors: the parent's FnSystemTermDesc, with this class's pair orders
+            return self._fn_desc(loss, delta)
         cv = self.coef_values
         key = (loss, float(delta))
         if key not in self._descs:

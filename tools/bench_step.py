@@ -3,7 +3,8 @@
     python tools/bench_step.py [--configs C1,C2,C3,C4] [--steps 30] [--modes autograd,manual,graph]
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
                                [--term-pde] [--term-nd] [--term-mixed] [--causal M,EPS]
-                               [--system {gray_scott,navier_stokes,elasticity,elasticity_nomixed}]
+                               [--system {gray_scott,navier_stokes,elasticity,elasticity_nomixed,navier_stokes_forced,
+                                          advection_diffusion}]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -49,6 +50,13 @@ e_x + e_y.  `--system elasticity_nomixed` runs S4, the yardstick: the same syste
 dropped (four launches per sweep against six).  After the step table every launch of the chain is timed on its own; for S4 also
 `pinn_term_residual_system_mixed` on the same blocks with all pair orders 0, beside `pinn_term_residual_system`: the cost of
 the larger LDS footprint.
+
+`--system navier_stokes_forced` runs S2 beside S5, its forced twin: the same Navier-Stokes system with a body force (fx, fy)
+(x, y, t) in the two momentum equations, given as known functions (`TermPDESystem(..., functions=...)`): the same launches, the
+element-wise kernel `pinn_term_residual_system_fn` and two function evaluations (torch ops) per residual call.
+`--system advection_diffusion` runs S6: one field c in 2-D, c_t + a c_x + b c_y - kappa (c_xx + c_yy) with the rotating field
+(a, b) = (-(y - 1/2), x - 1/2) and kappa(x, y) as functions.  For S3 the launch table also times `pinn_term_residual_system_fn` on
+the same blocks with no function named, beside `pinn_term_residual_system_mixed`.
 
 `--causal M,EPS` turns on the causal (time-weighted) residual loss (`training.causal_weighting`: M time bins, sharpness
 EPS): the autograd mode builds the weighted loss with torch ops on the residual tensor, the other two run the residual part
@@ -129,14 +137,39 @@ NAVIER_STOKES = [
     [(1.0, ("u_x",)), (1.0, ("v_y",))]]
 
 
+def _body_force():
+    """A smooth body force (fx, fy)(x, y, t) of the forced Navier-Stokes twin: pure device torch ops, so the step captures."""
+    fx = lambda x, t: torch.sin(math.pi * x[:, 0]) * torch.cos(math.pi * x[:, 1]) * torch.exp(-t[:, 0])  # noqa: E731
+    fy = lambda x, t: -torch.cos(math.pi * x[:, 0]) * torch.sin(math.pi * x[:, 1]) * torch.exp(-t[:, 0])  # noqa: E731
+    return {"fx": fx, "fy": fy}
+
+
+def _advection_diffusion():
+    """One field in 2-D, c_t + a c_x + b c_y - kappa (c_xx + c_yy), velocity field and diffusivity as known functions, on fourier
+    4x128, 49 729 points, Dirichlet faces."""
+    fns = {"a": lambda x, t: -(x[:, 1] - 0.5), "b": lambda x, t: x[:, 0] - 0.5, "kappa": lambda x, t: 0.01 * (1.0 + x[:, 0] * x[:, 1])}
+    eqs = [[(1.0, ("c_t",)), (1.0, ("a", "c_x")), (1.0, ("b", "c_y")), (-1.0, ("kappa", "c_xx")), (-1.0, ("kappa", "c_yy"))]]
+    net = B.model("fourier", 128, 4, "tanh", input_dim=3, output_dim=1)
+    pc = P.PDEConfig(name="advection_diffusion", domain=[(0.0, 1.0)] * 2, time_domain=(0.0, 1.0), parameters={},
+                     boundary_conditions={"dirichlet": {"type": "fixed", "value": 0.0}}, initial_condition={}, exact_solution={},
+                     dimension=2, device=B.dev)
+    ic = lambda x: torch.exp(-40 * ((x[:, 0] - 0.7) ** 2 + (x[:, 1] - 0.5) ** 2)).unsqueeze(1)  # noqa: E731
+    return ("Advection-diffusion 2D (c; a, b, kappa as functions) as TermPDESystem, fourier 4x128", net,
+            P.TermPDESystem(pc, ("c",), eqs, ic, functions=fns), 49729)
+
+
 def _system(which):
     """Coupled systems as `TermPDESystem` on fourier 4x128 with one output per field, 49 729 points."""
+    forced = which == "navier_stokes_forced"
     if which == "gray_scott":
         fields, eqs, dim, label = ("u", "v"), GRAY_SCOTT, 1, "Gray-Scott 1D (u, v)"
         bcs, ic, icf = {"periodic": {}}, (lambda x: torch.stack([1 - 0.5 * torch.exp(-50 * (x[:, 0] - 0.5) ** 2),
                                                                    0.25 * torch.exp(-50 * (x[:, 0] - 0.5) ** 2)], 1)), None
     else:
         fields, eqs, dim, label = ("u", "v", "p"), NAVIER_STOKES, 2, "Navier-Stokes 2D (u, v, p)"
+        if forced:
+            eqs = [NAVIER_STOKES[0] + [(-1.0, ("fx",))], NAVIER_STOKES[1] + [(-1.0, ("fy",))], NAVIER_STOKES[2]]
+            label = "Navier-Stokes 2D (u, v, p) with a body force (fx, fy as functions)"
         bcs = {"dirichlet": {"type": "fixed", "value": [0.0, 0.0, None]}}
         ic, icf = (lambda x: torch.stack([torch.sin(math.pi * x[:, 0]) * torch.sin(math.pi * x[:, 1]),
                                           torch.zeros_like(x[:, 0])], 1)), ("u", "v")
@@ -144,7 +177,8 @@ def _system(which):
     pc = P.PDEConfig(name=which, domain=[(0.0, 1.0)] * dim, time_domain=(0.0, 1.0),
                      parameters={"Du": 2e-5, "Dv": 1e-5, "F": 0.04, "Fk": 0.1, "nu": 0.01}, boundary_conditions=bcs,
                      initial_condition={}, exact_solution={}, dimension=dim, device=B.dev)
-    return f"{label} as TermPDESystem, fourier 4x128", net, P.TermPDESystem(pc, fields, eqs, ic, initial_condition_fields=icf), 49729
+    return (f"{label} as TermPDESystem, fourier 4x128", net,
+            P.TermPDESystem(pc, fields, eqs, ic, initial_condition_fields=icf, functions=_body_force() if forced else None), 49729)
 
 
 def _elasticity_equations(mixed):
@@ -177,7 +211,8 @@ def _elasticity(mixed):
 ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2),
               "M1": lambda: _heat_nd(2), "M2": lambda: _mixed_2d("aniso"), "M3": lambda: _mixed_2d("ch"),
               "S1": lambda: _system("gray_scott"), "S2": lambda: _system("navier_stokes"),
-              "S3": lambda: _elasticity(True), "S4": lambda: _elasticity(False)}
+              "S3": lambda: _elasticity(True), "S4": lambda: _elasticity(False),
+              "S5": lambda: _system("navier_stokes_forced"), "S6": _advection_diffusion}
 
 
 def build(tag, adaptive="none", smoothness=0.0, term_pde=False, causal=None):
@@ -368,7 +403,8 @@ def time_system_launches(tag, iters=20):
     n = int(x.shape[0])
     flat, s = E.new_flat_grad(prog, B.dev), torch.zeros(1, device=B.dev)
     jets = E._system_jets(prog, td, x, t)
-    entry = "pinn_term_residual_system_mixed" if isinstance(td, E.MixedSystemTermDesc) else "pinn_term_residual_system"
+    entry = ("pinn_term_residual_system_fn + the functions' torch ops" if isinstance(td, E.FnSystemTermDesc) else
+             "pinn_term_residual_system_mixed" if isinstance(td, E.MixedSystemTermDesc) else "pinn_term_residual_system")
     _, cot = E._term_residual_sys(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
     calls = []
     for b, (c, key, nt, nx) in zip(td.blocks(), td.launches()):
@@ -387,6 +423,20 @@ def time_system_launches(tag, iters=20):
                       lambda: E.term_residual_system_mixed(tm, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
         calls.append(("pinn_term_residual_system_mixed, all pair orders 0 (residuals only, one launch)",
                       lambda: E.term_residual_system_mixed(tm, jets, x, t)))
+    if isinstance(td, E.FnSystemTermDesc):  # the kernel alone on values held, and the evaluation of the functions alone
+        fv = td.fn_values(x, t)
+        calls.append(("pinn_term_residual_system_fn on given values (loss sum + cotangents, two launches)",
+                      lambda: E.term_residual_system_fn(td, jets, fv, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s,
+                                                        want_cotangents=True)))
+        calls.append(("fn_values: the functions' torch ops", lambda: td.fn_values(x, t)))
+    if tag == "S3":  # the same program and blocks through the function entry point with no function named
+        tf = E.FnSystemTermDesc(td.terms, td.equation_of, td.coef_values, td.dimension, td.n_fields, td.n_equations, td.nt, td.nx, td.pair,
+                                (), td.eq_weights)
+        calls.append(("pinn_term_residual_system_fn, no function named (loss sum + cotangents, two launches)",
+                      lambda: E.term_residual_system_fn(tf, jets, None, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s,
+                                                        want_cotangents=True)))
+        calls.append(("pinn_term_residual_system_fn, no function named (residuals only, one launch)",
+                      lambda: E.term_residual_system_fn(tf, jets, None, x, t)))
     calls.append(("the chain through engine.residual_loss_grad", lambda: E.residual_loss_grad(prog, td, x, t, 1.0 / n, flat, loss_sum=s)))
     print()
     print(f"| {tag} launch ({n} points) | ms |")
@@ -458,12 +508,16 @@ def main():
     ap.add_argument("--term-nd", action="store_true", help="N1, N2: the heat Laplacian in 1-D (TermPDE) and 2-D (TermPDEnD), fourier 4x128")
     ap.add_argument("--term-mixed", action="store_true",
                     help="M1, M2, M3: 2-D heat (TermPDEnD), anisotropic diffusion and Cahn-Hilliard (TermPDEMixed), fourier 4x128")
-    ap.add_argument("--system", choices=["gray_scott", "navier_stokes", "elasticity", "elasticity_nomixed"], default=None,
+    ap.add_argument("--system", choices=["gray_scott", "navier_stokes", "elasticity", "elasticity_nomixed", "navier_stokes_forced",
+                                         "advection_diffusion"], default=None,
                     help="N1, S1 (gray_scott) or N2, S2 (navier_stokes): a TermPDESystem beside the single-field step; S3 (elasticity): 2-D "
-                         "elasticity as a TermPDESystemMixed; S4 (elasticity_nomixed): the same without its mixed terms; fourier 4x128")
+                         "elasticity as a TermPDESystemMixed; S4 (elasticity_nomixed): the same without its mixed terms; S2, S5 "
+                         "(navier_stokes_forced): Navier-Stokes and its twin with a body force given as functions; S6 "
+                         "(advection_diffusion): one field with a(x,y), b(x,y), kappa(x,y) as functions; fourier 4x128")
     args = ap.parse_args()
     if args.system and args.configs == "C1,C2,C3,C4":
-        args.configs = {"gray_scott": "N1,S1", "navier_stokes": "N2,S2", "elasticity": "S3", "elasticity_nomixed": "S4"}[args.system]
+        args.configs = {"gray_scott": "N1,S1", "navier_stokes": "N2,S2", "elasticity": "S3", "elasticity_nomixed": "S4",
+                        "navier_stokes_forced": "S2,S5", "advection_diffusion": "S6"}[args.system]
     if args.term_nd and args.configs == "C1,C2,C3,C4":
         args.configs = "N1,N2"
     if args.term_mixed and args.configs == "C1,C2,C3,C4":
@@ -526,7 +580,7 @@ def main():
             time_term_launches(tag)
         if args.term_mixed and tag in ND_CONFIGS:
             time_nd_launches(tag)
-        if args.system and tag in ("S1", "S2", "S3", "S4"):
+        if args.system and tag in ("S1", "S2", "S3", "S4", "S5", "S6"):
             time_system_launches(tag)
         if args.system and tag == "N2":
             time_nd_launches(tag)
