@@ -828,6 +828,89 @@ int pinn_term_residual_system_fn(const PinnTermPdeSystemFn* pde, const float* co
                                  const float* residual_cotangent, float* residual_out, float* loss_sum_out, float* eq_loss_sums,
                                  float* const* jet_cotangents, float* coef_grads, double* scratch, void* stream);
 
+/* ---- term residuals of coupled systems with nonlinear functions of the unknowns as factors ----------------------------------
+ * pinn_term_residual_system_fn plus up to PINN_SYSTEM_MAX_NONLINEAR factors w_k = g_k(shift_k + scale_k s_k), where s_k is a
+ * stream of a field or an earlier w_j (j < k, so functions nest): 1 / rho, exp(u), u / (K + u), exp(-E / T), u^m, kappa(u).
+ * The factor byte PINN_SYSTEM_FACTOR(k, PINN_TERM_NL) (code 31, the field bits carry k) names w_k; every other code keeps the
+ * meaning it has in pinn_term_residual_system_fn, and the codes 17 .. 20 and 24 .. 26 stay refused by name.
+ *   nl_op[k]           one of PINN_NL_*.
+ *   nl_source[k]       a factor byte of the same encoding: a stream of a field (codes 0 .. 6, 11 .. 14, 21 .. 23: derivative
+ *                      streams and u_ab included; no coordinate, no known function, no sin / cos code), or
+ *                      PINN_SYSTEM_FACTOR(j, PINN_TERM_NL) with j < k.  The descriptor must hold a source exactly as it must hold
+ *                      a term factor: the same checks, the messages saying "nonlinear function k" for "term m, factor f".
+ *   nl_params          3 n_nonlinear device floats, {shift, scale, exponent} of function k at nl_params + 3 k, read at launch
+ *                      time like coef_values.  exponent is read by PINN_NL_POW only.  May be NULL when no term names a
+ *                      nonlinear function.
+ * All in fp32.  arg = fmaf(scale, s, shift) (one rounding), w = g(arg) the value, slope = g'(arg), d_k = slope * scale (one
+ * rounding):
+ *   PINN_NL_EXP    w = expf(arg)      slope = w
+ *   PINN_NL_LOG    w = logf(arg)      slope = 1.0f / arg
+ *   PINN_NL_RECIP  w = 1.0f / arg     slope = -(w * w)
+ *   PINN_NL_SQRT   w = sqrtf(arg)     slope = 0.5f / w
+ *   PINN_NL_POW    w = powf(arg, p)   slope = p * powf(arg, p - 1.0f)       (p = exponent)
+ *   PINN_NL_TANH   w = tanhf(arg)     slope = 1.0f - w * w
+ *   PINN_NL_SINH   w = sinhf(arg)     slope = coshf(arg)
+ *   PINN_NL_COSH   w = coshf(arg)     slope = sinhf(arg)
+ *   PINN_NL_SIN    w = sinf(arg)      slope = cosf(arg)
+ *   PINN_NL_COS    w = cosf(arg)      slope = -sinf(arg)
+ * An argument outside a function's domain (log or sqrt of a negative number, 1 / 0, a negative base under a fractional
+ * exponent) is NOT checked: the value and the slope are what IEEE arithmetic gives, NaN or inf, and they spread through the
+ * residual, the loss sums and every cotangent the function reaches.
+ *   value pass         once per point, in ascending k, after the fields' values and the known functions: only the k of a
+ *                      host-made, wave-uniform mask, which holds the functions some term names, closed under "is the source of
+ *                      a masked function".  A function outside the mask is never evaluated and its parameters are never read.
+ *   sweep 1            a nonlinear factor enters the product ((c_m phi_0) phi_1) ... at its position, like a known function;
+ *                      likewise in coef_grads[m] = sum_n rbar prod_f phi_{m,f}.
+ *   sweep 2            w_k is a cotangent target of its own, wbar_k, under the rule of the other targets: the summands of one term
+ *                      that go to the same target are summed first in ascending f, multiplied by rbar, then added.  After the
+ *                      term loop, in descending k over the mask, wbar_k * d_k (one rounding) is added to the accumulator of the
+ *                      source: the (field, stream) accumulator, the pair accumulator g of a u_ab source, or wbar_j.  The
+ *                      transposed polarisation and the write-out follow unchanged.
+ * No gradient with respect to nl_params is produced.  Everything else as pinn_term_residual_system_fn: with n_nonlinear = 0, or
+ * with no nonlinear factor named by a term, the residuals, every cotangent block and the sums are bit-identical to it on the same
+ * inputs.
+ * Checked on the host before any HIP call: every check of pinn_term_residual_system_fn; n_nonlinear outside [0, 4]; an unknown
+ * nl_op; a source that is neither a stream nor an earlier nonlinear function, or that the descriptor does not hold; code 31 with
+ * k >= n_nonlinear; null nl_params under a non-empty mask with N > 0: PINN_ERR_BAD_DESC, the message naming the function or the
+ * term. */
+#define PINN_SYSTEM_MAX_NONLINEAR 4
+#define PINN_TERM_NL 31
+#define PINN_NL_EXP 0
+#define PINN_NL_LOG 1
+#define PINN_NL_RECIP 2
+#define PINN_NL_SQRT 3
+#define PINN_NL_POW 4
+#define PINN_NL_TANH 5
+#define PINN_NL_SINH 6
+#define PINN_NL_COSH 7
+#define PINN_NL_SIN 8
+#define PINN_NL_COS 9
+
+typedef struct PinnTermPdeSystemNl {
+  int32_t dimension;                                   /* 1 .. 3 (a mixed factor needs 2 or 3) */
+  int32_t n_fields;
+  int32_t n_equations;
+  int32_t time_order[PINN_SYSTEM_MAX_FIELDS];
+  int32_t space_order[PINN_SYSTEM_MAX_FIELDS][3];
+  int32_t n_terms;
+  int32_t equation_of[PINN_SYSTEM_MAX_TERMS];
+  float eq_weight[PINN_SYSTEM_MAX_EQUATIONS];
+  int32_t loss;
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_SYSTEM_MAX_TERMS];        /* factor[f] = PINN_SYSTEM_FACTOR(field, code), code 0 .. 16, 21 .. 23, 27 .. 31 */
+  int32_t pair_order[PINN_SYSTEM_MAX_FIELDS][3];       /* per field, pairs (x,y), (x,z), (y,z): 0 or 2 */
+  int32_t n_functions;                                 /* 0 .. PINN_SYSTEM_MAX_FUNCTIONS: rows of fn_values */
+  int32_t n_nonlinear;                                 /* 0 .. PINN_SYSTEM_MAX_NONLINEAR: triples of nl_params */
+  int32_t nl_op[PINN_SYSTEM_MAX_NONLINEAR];            /* PINN_NL_* */
+  int32_t nl_source[PINN_SYSTEM_MAX_NONLINEAR];        /* a stream byte, or PINN_SYSTEM_FACTOR(j, PINN_TERM_NL) with j < k */
+} PinnTermPdeSystemNl;
+
+int pinn_term_residual_system_nl(const PinnTermPdeSystemNl* pde, const float* coef_values, const float* const* jets,
+                                 const float* x, const float* t, const float* fn_values, const float* nl_params, int64_t N,
+                                 float grad_scale, const float* residual_cotangent, float* residual_out, float* loss_sum_out,
+                                 float* eq_loss_sums, float* const* jet_cotangents, float* coef_grads, double* scratch,
+                                 void* stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.
  * lr and step are DEVICE scalars (step = number of steps taken so far, incremented by the call) so that a captured

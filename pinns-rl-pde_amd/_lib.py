@@ -78,6 +78,12 @@ TERM_FACTOR_SYSTEM_MIXED = dict(TERM_FACTOR_ND, **{"u_xy": 21, "u_xz": 22, "u_yz
 PINN_SYSTEM_MAX_FUNCTIONS = 4
 PINN_TERM_FN0 = 27
 TERM_FACTOR_SYSTEM_FN = dict(TERM_FACTOR_SYSTEM_MIXED, **{f"fn{k}": PINN_TERM_FN0 + k for k in range(PINN_SYSTEM_MAX_FUNCTIONS)})
+# pinn_term_residual_system_nl: up to four nonlinear functions g(shift + scale * source) of the unknowns as factors (code 31, the
+# field bits carry k: "nl0" .. "nl3" map to the whole factor byte 32 k + 31)
+PINN_SYSTEM_MAX_NONLINEAR = 4
+PINN_TERM_NL = 31
+NL_OPS = {"exp": 0, "log": 1, "recip": 2, "sqrt": 3, "pow": 4, "tanh": 5, "sinh": 6, "cosh": 7, "sin": 8, "cos": 9}  # PINN_NL_*
+TERM_FACTOR_SYSTEM_NL = dict(TERM_FACTOR_SYSTEM_FN, **{f"nl{k}": 32 * k + PINN_TERM_NL for k in range(PINN_SYSTEM_MAX_NONLINEAR)})
 # pinn_face_losses: the loss terms of per-face boundary conditions
 PINN_FACE_MAX_TERMS = 32
 PINN_FACE_SCRATCH_DOUBLES = 64 * PINN_FACE_MAX_TERMS
@@ -107,6 +113,7 @@ EXPORTS = (
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
     "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system", "pinn_residual_unit_name",
     "pinn_face_losses", "pinn_term_residual_system_mixed", "pinn_term_residual_system_fn",
+    "pinn_term_residual_system_nl",
 )
 
 
@@ -169,6 +176,11 @@ class PinnTermPdeSystemMixed(ctypes.Structure):
 
 class PinnTermPdeSystemFn(ctypes.Structure):
     _fields_ = PinnTermPdeSystemMixed._fields_ + [("n_functions", ctypes.c_int32)]
+
+
+class PinnTermPdeSystemNl(ctypes.Structure):
+    _fields_ = PinnTermPdeSystemFn._fields_ + [("n_nonlinear", ctypes.c_int32), ("nl_op", ctypes.c_int32 * PINN_SYSTEM_MAX_NONLINEAR),
+                                               ("nl_source", ctypes.c_int32 * PINN_SYSTEM_MAX_NONLINEAR)]
 
 
 class PinnFaceTerm(ctypes.Structure):
@@ -323,6 +335,9 @@ def load():
         lib.pinn_term_residual_system_fn.restype = ctypes.c_int
         lib.pinn_term_residual_system_fn.argtypes = [P(PinnTermPdeSystemFn), vp, P(vp), vp, vp, vp, i64, f32, vp, vp, vp, vp, P(vp), vp,
                                                      vp, vp]
+        lib.pinn_term_residual_system_nl.restype = ctypes.c_int
+        lib.pinn_term_residual_system_nl.argtypes = [P(PinnTermPdeSystemNl), vp, P(vp), vp, vp, vp, vp, i64, f32, vp, vp, vp, vp, P(vp),
+                                                     vp, vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         lib.pinn_face_losses.restype = ctypes.c_int

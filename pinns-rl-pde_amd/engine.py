@@ -653,6 +653,85 @@ class FnSystemTermDesc(MixedSystemTermDesc):
         return out
 
 
+class NlSystemTermDesc(FnSystemTermDesc):
+    """A `FnSystemTermDesc` whose terms may name nonlinear functions of the unknowns (`pinn_term_residual_system_nl`): its factor
+    names plus "nl0" .. "nl3" (`_lib.TERM_FACTOR_SYSTEM_NL`), given like a coordinate, without a field.
+
+    The same arguments plus nonlinear: at most four tuples (op, source, shift, scale, exponent), w_k = g(shift + scale * s) with
+    op one of `_lib.NL_OPS`, the source s a stream of a field, (field index, "u" | "u_x" | ... | "u_xy"), or an earlier function
+    "nl<j>", j < k (no coordinate, no known function, no sin / cos factor); exponent is read by "pow" only.  The descriptor must
+    hold a source as it must hold a term factor.  nl_values: the (K, 3) float32 device tensor {shift, scale, exponent} the kernel
+    reads at LAUNCH time; when None it is built from the numbers of `nonlinear` on the device of coef_values.  A nonlinear
+    factor takes part in the products like a known function and is a cotangent target: its cotangent flows back to its source
+    through g'.  Only the functions some term names, and their sources, are evaluated.  `launches()` and `blocks()` are the
+    parent's.  An argument outside a function's domain is not checked: NaN or inf spreads."""
+
+    _STRUCT = _lib.PinnTermPdeSystemNl
+    _FACTORS = _lib.TERM_FACTOR_SYSTEM_NL
+    _FIELDLESS = FnSystemTermDesc._FIELDLESS + tuple(f"nl{k}" for k in range(_lib.PINN_SYSTEM_MAX_NONLINEAR))
+
+    def __init__(self, terms: Sequence[Sequence[object]], equation_of: Sequence[int], coef_values: Tensor, dimension: int,
+                 n_fields: int, n_equations: int, nt: Sequence[int], nx: Sequence[Sequence[int]],
+                 pair: Optional[Sequence[Sequence[int]]] = None, functions: Sequence[Callable] = (),
+                 nonlinear: Sequence[Sequence[object]] = (), eq_weights: Optional[Sequence[float]] = None, loss: str = "mse",
+                 huber_delta: float = 1.0, function_names: Optional[Sequence[str]] = None,
+                 nonlinear_names: Optional[Sequence[str]] = None, nl_values: Optional[Tensor] = None):
+        nonlinear = tuple(tuple(row) for row in nonlinear)
+        K = len(nonlinear)
+        if K > _lib.PINN_SYSTEM_MAX_NONLINEAR:
+            raise ValueError(f"nonlinear: at most {_lib.PINN_SYSTEM_MAX_NONLINEAR} nonlinear functions (got {K})")
+        names = tuple(f"nl{k}" for k in range(K)) if nonlinear_names is None else tuple(str(v) for v in nonlinear_names)
+        if len(names) != K:
+            raise ValueError(f"nonlinear_names: one name per nonlinear function ({K})")
+        super().__init__(terms, equation_of, coef_values, dimension, n_fields, n_equations, nt, nx, pair, functions, eq_weights, loss,
+                         huber_delta, function_names)
+        for m, factors in enumerate(self.terms):
+            for fac in factors:
+                if isinstance(fac, str) and fac.startswith("nl") and int(fac[2:]) >= K:
+                    raise ValueError(f"term {m}: factor '{fac}' names nonlinear function {int(fac[2:])} of {K}")
+        norm = []
+        for k, row in enumerate(nonlinear):
+            if len(row) != 5:
+                raise ValueError(f"nonlinear[{k}]: (op, source, shift, scale, exponent) (got {row!r})")
+            op, src = row[0], row[1]
+            if op not in _lib.NL_OPS:
+                raise ValueError(f"nonlinear[{k}]: unknown operation {op!r} (one of {', '.join(_lib.NL_OPS)})")
+            if isinstance(src, str):
+                if not (src.startswith("nl") and src[2:].isdigit() and int(src[2:]) < k):
+                    raise ValueError(f"nonlinear[{k}]: source {src!r}: a stream of a field, (field index, name), or an earlier "
+                                     f"nonlinear function 'nl<j>' with j < {k}")
+                byte = _lib.TERM_FACTOR_SYSTEM_NL[src]
+            else:
+                field, name = int(src[0]), src[1]
+                if name not in _lib.TERM_FACTOR_SYSTEM_MIXED or name in SystemTermDesc._FIELDLESS or name in ("sin(u)", "cos(u)"):
+                    raise ValueError(f"nonlinear[{k}]: source '{name}' is not a stream of a field (a coordinate, a known function "
+                                     f"and sin / cos are no sources)")
+                if not 0 <= field < self.n_fields:
+                    raise ValueError(f"nonlinear[{k}]: source '{name}' names field {field} of {self.n_fields}")
+                if name in _MIXED_2:
+                    a, b = _PAIRS[_MIXED_2[name]]
+                    if self.pair[field][_MIXED_2[name]] != 2 or self.nx[field][a] < 2 or self.nx[field][b] < 2:
+                        raise ValueError(f"nonlinear[{k}]: '{name}' of field {field} needs pair order 2 and space order >= 2 on both "
+                                         f"axes of that field (pair orders {self.pair[field]}, space orders {self.nx[field]})")
+                byte = _lib.PINN_SYSTEM_FACTOR(field, _lib.TERM_FACTOR_SYSTEM_MIXED[name])
+                src = (field, name)
+            self.desc.nl_op[k] = _lib.NL_OPS[op]
+            self.desc.nl_source[k] = byte
+            norm.append((op, src, float(row[2]), float(row[3]), float(row[4])))
+        self.desc.n_nonlinear = K
+        if nl_values is None:
+            nl_values = torch.tensor([list(r[2:]) for r in norm], dtype=torch.float32, device=coef_values.device).reshape(K, 3)
+        elif nl_values.dtype != torch.float32 or not nl_values.is_contiguous() or tuple(nl_values.shape) != (K, 3):
+            raise ValueError(f"nl_values: a contiguous float32 ({K}, 3) tensor (got {nl_values.dtype} {tuple(nl_values.shape)})")
+        self.nonlinear, self.nonlinear_names, self.nl_values = tuple(norm), names, nl_values
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "NlSystemTermDesc":
+        """The same program, the same coefficient and parameter tensors and the same functions under another loss kind."""
+        return NlSystemTermDesc(self.terms, self.equation_of, self.coef_values, self.dimension, self.n_fields, self.n_equations,
+                                self.nt, self.nx, self.pair, self.functions, self.nonlinear, self.eq_weights, loss, huber_delta,
+                                self.function_names, self.nonlinear_names, self.nl_values)
+
+
 def pde_streams(pd) -> Tuple[int, int]:
     if isinstance(pd, SystemTermDesc):  # the set of field 0's axis-0 launch
         return pd.nt[0], pd.nx[0][0]
@@ -947,15 +1026,43 @@ def term_residual_system_fn(td: FnSystemTermDesc, jets: Sequence[Optional[Tensor
                                  loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=fn_values, with_fn=True)
 
 
+def term_residual_system_nl(td: NlSystemTermDesc, jets: Sequence[Optional[Tensor]], fn_values: Optional[Tensor],
+                            nl_params: Optional[Tensor], x: Tensor, t: Tensor, grad_scale: float = 0.0,
+                            residual_cotangent: Optional[Tensor] = None, want_residual: bool = True, loss_sum: Optional[Tensor] = None,
+                            want_cotangents: bool = False, coef_grads: Optional[Tensor] = None,
+                            eq_loss_sums: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[List[Optional[Tensor]]]]:
+    """`pinn_term_residual_system_nl`: `term_residual_system_fn` with the parameters of the nonlinear functions given explicitly —
+    nl_params a contiguous float32 (len(td.nonlinear), 3) tensor on the device of the jets (`td.nl_values`), row k the
+    {shift, scale, exponent} of function k; None only where the descriptor has no nonlinear function.  The kernel reads it at
+    launch time, and only the rows of the functions it evaluates."""
+    K, KN = len(td.functions), len(td.nonlinear)
+    if fn_values is None:
+        if K:
+            raise ValueError(f"term_residual_system_nl: fn_values is None but the descriptor has {K} functions")
+    elif (fn_values.dim() != 2 or fn_values.shape[0] != K or fn_values.dtype != torch.float32 or not fn_values.is_contiguous()):
+        raise ValueError(f"term_residual_system_nl: fn_values must be a contiguous float32 ({K}, N) tensor "
+                         f"(got {fn_values.dtype} {tuple(fn_values.shape)})")
+    if nl_params is None:
+        if KN:
+            raise ValueError(f"term_residual_system_nl: nl_params is None but the descriptor has {KN} nonlinear functions")
+    elif tuple(nl_params.shape) != (KN, 3) or nl_params.dtype != torch.float32 or not nl_params.is_contiguous():
+        raise ValueError(f"term_residual_system_nl: nl_params must be a contiguous float32 ({KN}, 3) tensor "
+                         f"(got {nl_params.dtype} {tuple(nl_params.shape)})")
+    return _term_residual_system("term_residual_system_nl", True, td, jets, x, t, grad_scale, residual_cotangent, want_residual,
+                                 loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=fn_values, nl_params=nl_params,
+                                 with_nl=True)
+
+
 def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t, grad_scale, residual_cotangent, want_residual,
-                          loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=None, with_fn=False):
-    """The body of `term_residual_system` / `term_residual_system_mixed` / `term_residual_system_fn`: the checks, the buffers and
-    the one call."""
+                          loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=None, with_fn=False, nl_params=None,
+                          with_nl=False):
+    """The body of `term_residual_system` / `term_residual_system_mixed` / `term_residual_system_fn` / `term_residual_system_nl`:
+    the checks, the buffers and the one call."""
     lib = _lib.load()
     dim, C, E = td.dimension, td.n_fields, td.n_equations
     nb = _lib.PINN_SYSTEM_MIXED_BLOCKS(C) if mixed else 3 * C
     jets = list(jets) + [None] * (nb - len(jets))
-    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums, fn_values)
+    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums, fn_values, nl_params)
     rows = []
     for c in range(C):
         rows += [1 + td.nt[c] + td.nx[c][0]] + [(1 + td.nx[c][a]) if (a < dim and td.nx[c][a] > 0) else 0 for a in (1, 2)]
@@ -995,7 +1102,12 @@ def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t,
     cptr = (ctypes.c_void_p * nb)(*[opt(c) for c in cot]) if cot is not None else None
     entry = lib.pinn_term_residual_system_mixed if mixed else lib.pinn_term_residual_system
     with torch.cuda.device(dev):
-        if with_fn:
+        if with_nl:
+            _lib.check(lib.pinn_term_residual_system_nl(
+                ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), opt(fn_values), opt(nl_params), N,
+                float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr, opt(coef_grads),
+                opt(scratch), _stream(dev)))
+        elif with_fn:
             _lib.check(lib.pinn_term_residual_system_fn(
                 ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), opt(fn_values), N, float(grad_scale),
                 opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr, opt(coef_grads), opt(scratch), _stream(dev)))
@@ -1014,6 +1126,9 @@ def _launch_line(key) -> dict:
 def _term_residual_sys(td: SystemTermDesc, jets, x, t, **kwargs):
     """The element-wise kernel of a system descriptor: the entry point of its class.  A `FnSystemTermDesc` has its functions
     evaluated here, once per call."""
+    if isinstance(td, NlSystemTermDesc):
+        return term_residual_system_nl(td, jets, td.fn_values(x, t) if td.functions else None,
+                                       td.nl_values if td.nonlinear else None, x, t, **kwargs)
     if isinstance(td, FnSystemTermDesc):
         return term_residual_system_fn(td, jets, td.fn_values(x, t) if td.functions else None, x, t, **kwargs)
     return (term_residual_system_mixed if isinstance(td, MixedSystemTermDesc) else term_residual_system)(td, jets, x, t, **kwargs)

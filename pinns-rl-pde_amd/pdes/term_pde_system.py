@@ -60,6 +60,25 @@ class TermPDESystem(PDEBase):
         Forced heat in 1-D, u_t - u_xx = f:
             TermPDESystem(cfg, ("u",), [[(1.0, ("u_t",)), (-1.0, ("u_xx",)), (-1.0, ("f",))]], ic,
                           functions={"f": lambda x, t: torch.exp(-t[:, 0]) * torch.sin(math.pi * x[:, 0]) * (math.pi**2 - 1)})
+    nonlinear: {name: (op, source) | (op, source, {"shift": a, "scale": b, "exponent": p})} with at most 4 entries: nonlinear
+        functions of the unknowns that the terms may name as factors, "<name>" = g(shift + scale * source) at the point.  op is one
+        of exp, log, recip (1 / arg), sqrt, pow (arg ** exponent), tanh, sinh, cosh, sin, cos.  The source is a stream factor name
+        of a field ("T", "u_x", in `TermPDESystemMixed` also "v_xy") or the name of an EARLIER entry, so functions nest; the order
+        of the mapping is the order of evaluation.  No coordinate, no known function and no sin(<field>) / cos(<field>) is a
+        source.  A source's stream counts towards the stream orders of its field exactly as a term factor does.  shift, scale
+        and exponent (defaults 0, 1, 1) are a number, a parameter name of config.parameters or (number, "parameter name"); they
+        are held in `nl_values`, a (K, 3) float32 device tensor built once beside `coef_values` and read at launch time, so
+        rewriting it in place changes the eager step and a captured one.  They are not trainable.  Names follow the rule for
+        functions: an identifier without "_", none of x, y, z, t, sin, cos, no field, no function and no other nonlinear name.
+        The gradient flows through g' to the source.  An argument outside the domain of g (log of a negative number, 1 / 0) is
+        not checked: NaN or inf spreads into the loss.  ONLY THE VALUE of g is a factor: a space or time derivative of g(u) has
+        to be written out by the chain rule by hand, as with sin(<field>).  (kappa(u) u_x)_x = kappa'(u) u_x^2 + kappa(u) u_xx
+        needs kappa and kappa' as two declarations; with kappa = exp(u) both are the same one.  With nonlinear the descriptor
+        is an `engine.NlSystemTermDesc` (`pinn_term_residual_system_nl`); without, it is what it was.  Bratu-type in 1-D,
+        u_t - u_xx - lam e^u, and Monod kinetics u / (K + u):
+            TermPDESystem(cfg, ("u",), [[(1.0, ("u_t",)), (-1.0, ("u_xx",)), ((-1.0, "lam"), ("eu",))]], ic,
+                          nonlinear={"eu": ("exp", "u")})
+            nonlinear={"m": ("recip", "u", {"shift": "K"})}  with the term (1.0, ("u", "m"))
     equation_weights: omega_e >= 0 (default 1): the residual loss is sum_e omega_e mean l(r_e).
     initial_condition_fn(x: (n, dim)) -> (n, len(initial_condition_fields)); initial_condition_fields defaults to all fields.
     exact_solution_fn(x, t) -> (n, C): enables `validate()`.
@@ -94,7 +113,8 @@ class TermPDESystem(PDEBase):
                  equation_weights: Optional[Sequence[float]] = None, initial_condition_fields: Optional[Sequence[str]] = None,
                  boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32,
                  face_conditions: Optional[Dict[str, Any]] = None,
-                 functions: Optional[Dict[str, Callable[[torch.Tensor, torch.Tensor], torch.Tensor]]] = None, **kwargs):
+                 functions: Optional[Dict[str, Callable[[torch.Tensor, torch.Tensor], torch.Tensor]]] = None,
+                 nonlinear: Optional[Dict[str, Sequence[Any]]] = None, **kwargs):
         who = type(self).__name__
         dim = int(getattr(config, "dimension", 1))
         if dim not in (1, 2, 3):
@@ -136,6 +156,58 @@ class TermPDESystem(PDEBase):
         self._term_factors: List[Tuple[object, ...]] = []
         self._equation_of: List[int] = []
         nt, nx = [0] * C, [[0, 0, 0] for _ in range(C)]
+        nonlinear = dict(nonlinear or {})
+        if len(nonlinear) > _lib.PINN_SYSTEM_MAX_NONLINEAR:
+            raise ValueError(f"{who}: {len(nonlinear)} nonlinear functions; a system names at most {_lib.PINN_SYSTEM_MAX_NONLINEAR}")
+        nl_index: Dict[str, int] = {}
+        self._nonlinear: List[Tuple[str, str, object]] = []  # (name, op, source as the descriptor takes it); function k is "nl<k>"
+        self._nl_specs: List[Tuple[object, object, object]] = []  # (shift, scale, exponent): a number or (number, parameter name)
+        for k, (name, decl) in enumerate(nonlinear.items()):
+            if (not isinstance(name, str) or not name.isidentifier() or "_" in name or name in _COORDS or name in index
+                    or name in ("sin", "cos") or name in fn_index):
+                raise ValueError(f"{who}: nonlinear name {name!r}: an identifier without '_' that is none of x, y, z, t, sin, cos, no "
+                                 f"field name ({', '.join(fields)}) and no function name")
+            if not isinstance(decl, (tuple, list)) or len(decl) not in (2, 3) or (len(decl) == 3 and not isinstance(decl[2], dict)):
+                raise ValueError(f"{who}: nonlinear '{name}': (op, source) or (op, source, {{'shift': .., 'scale': .., 'exponent': ..}})")
+            op, source = decl[0], decl[1]
+            opts = dict(decl[2]) if len(decl) == 3 else {}
+            if op not in _lib.NL_OPS:
+                raise ValueError(f"{who}: nonlinear '{name}': unknown operation {op!r} (one of {', '.join(_lib.NL_OPS)})")
+            if set(opts) - {"shift", "scale", "exponent"}:
+                raise ValueError(f"{who}: nonlinear '{name}': unknown options {sorted(set(opts) - {'shift', 'scale', 'exponent'})} "
+                                 "(shift, scale, exponent)")
+            if isinstance(source, str) and source in nl_index:
+                src: object = f"nl{nl_index[source]}"
+            else:
+                parsed = None if (isinstance(source, str) and (source in fn_index or source in nonlinear)) else \
+                    self._parse_factor(source, index)
+                if parsed is None or parsed[0] is None or parsed[1] in ("sin(u)", "cos(u)"):
+                    raise ValueError(f"{who}: nonlinear '{name}': source {source!r} is neither a stream of a field ({self._FACTOR_NAMES} "
+                                     f"without sin and cos, <field> in {', '.join(fields)}) nor an earlier nonlinear name "
+                                     f"({', '.join(nl_index) or 'none so far'}); a coordinate, a known function and a later declaration "
+                                     "are no sources")
+                c, one, t_order, (axis, order) = parsed
+                if order and axis >= dim:
+                    raise ValueError(f"{who}: nonlinear '{name}': source '{source}' needs dimension {axis + 1}, the problem has {dim}")
+                nt[c] = max(nt[c], t_order)
+                nx[c][axis] = max(nx[c][axis], order)
+                self._factor_parsed(c, one, nx)
+                src = (c, one)
+            spec = []
+            for key, default in (("shift", 0.0), ("scale", 1.0), ("exponent", 1.0)):
+                v = opts.get(key, default)
+                if isinstance(v, str):
+                    v = (1.0, v)
+                if isinstance(v, (tuple, list)):
+                    if len(v) != 2 or not isinstance(v[1], str):
+                        raise ValueError(f"{who}: nonlinear '{name}': {key} is a number, a parameter name or (number, 'parameter name')")
+                    v = (float(v[0]), v[1])
+                else:
+                    v = float(v)
+                spec.append(v)
+            nl_index[name] = k
+            self._nonlinear.append((name, op, src))
+            self._nl_specs.append(tuple(spec))
         for e, eq in enumerate(equations):
             for coef, factors in eq:
                 m = len(self._term_coefs)
@@ -147,6 +219,9 @@ class TermPDESystem(PDEBase):
                 for f in factors:
                     if isinstance(f, str) and f in fn_index:  # a known function: a factor like a coordinate
                         row.append(f"fn{fn_index[f]}")
+                        continue
+                    if isinstance(f, str) and f in nl_index:  # a nonlinear function of the unknowns
+                        row.append(f"nl{nl_index[f]}")
                         continue
                     parsed = self._parse_factor(f, index)
                     if parsed is None:
@@ -234,6 +309,11 @@ class TermPDESystem(PDEBase):
         for coef in self._term_coefs:
             if isinstance(coef, tuple) and self.get_parameter(coef[1]) is None:
                 raise ValueError(f"{who}: coefficient parameter '{coef[1]}' is not in config.parameters")
+        for (name, _, _), spec in zip(self._nonlinear, self._nl_specs):
+            for v in spec:
+                if isinstance(v, tuple) and self.get_parameter(v[1]) is None:
+                    raise ValueError(f"{who}: nonlinear '{name}': parameter '{v[1]}' is not in config.parameters")
+        self._nl_values: Optional[torch.Tensor] = None
         self._initial_condition_fn = initial_condition_fn
         self._exact_solution_fn = exact_solution_fn
         self._nb, self._ni = int(boundary_points_per_axis), int(initial_points_per_axis)
@@ -283,14 +363,32 @@ class TermPDESystem(PDEBase):
         dev = torch.device(self.device)  # the REQUESTED device is remembered beside the tensor (see TermPDE.coef_values)
         if self._coef_values is None or self._coef_device != dev:
             self._coef_values = torch.tensor([float(c) for c in self._coefficients()], dtype=torch.float32, device=dev).reshape(-1)
+            self._nl_values = torch.tensor(
+                [[v[0] * float(self.get_parameter(v[1], required=True)) if isinstance(v, tuple) else v for v in spec]
+                 for spec in self._nl_specs], dtype=torch.float32, device=dev).reshape(len(self._nl_specs), 3)
             self._coef_device = dev
             self._descs = {}
         return self._coef_values
 
+    @property
+    def nl_values(self) -> torch.Tensor:
+        """{shift, scale, exponent} of every nonlinear function as a (K, 3) float32 tensor on the PDE's device, built once beside
+        `coef_values`: what the kernel reads at launch time."""
+        self.coef_values
+        return self._nl_values
+
     def _fn_desc(self, loss: str, delta: float) -> "_E.FnSystemTermDesc":
-        """The descriptor of a problem with functions: a `FnSystemTermDesc` (here with all pair orders 0)."""
+        """The descriptor of a problem with functions: a `FnSystemTermDesc` (here with all pair orders 0); with nonlinear
+        functions of the unknowns an `NlSystemTermDesc`."""
         cv = self.coef_values
         key = (loss, float(delta))
+        if key not in self._descs and self._nonlinear:
+            nl = [(op, src, 0.0, 1.0, 1.0) for _, op, src in self._nonlinear]  # the numbers are in nl_values
+            self._descs[key] = _E.NlSystemTermDesc(self._term_factors, self._equation_of, cv, self.dimension, self.n_fields,
+                                                   self.n_equations, self._nt, self._nx, getattr(self, "_pair", None),
+                                                   [g for _, g in self._functions], nl, self._eq_weights, loss, delta,
+                                                   [name for name, _ in self._functions], [name for name, _, _ in self._nonlinear],
+                                                   self.nl_values)
         if key not in self._descs:
             self._descs[key] = _E.FnSystemTermDesc(self._term_factors, self._equation_of, cv, self.dimension, self.n_fields,
                                                    self.n_equations, self._nt, self._nx, getattr(self, "_pair", None),
@@ -299,7 +397,7 @@ class TermPDESystem(PDEBase):
         return self._descs[key]
 
     def _term_desc(self, loss: str, delta: float) -> "_E.SystemTermDesc":
-        if self._functions:
+        if self._functions or self._nonlinear:
             return self._fn_desc(loss, delta)
         cv = self.coef_values
         key = (loss, float(delta))

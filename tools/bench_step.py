@@ -4,7 +4,7 @@
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
                                [--term-pde] [--term-nd] [--term-mixed] [--causal M,EPS]
                                [--system {gray_scott,navier_stokes,elasticity,elasticity_nomixed,navier_stokes_forced,
-                                          advection_diffusion}]
+                                          advection_diffusion,euler_nl}]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -57,6 +57,11 @@ element-wise kernel `pinn_term_residual_system_fn` and two function evaluations 
 `--system advection_diffusion` runs S6: one field c in 2-D, c_t + a c_x + b c_y - kappa (c_xx + c_yy) with the rotating field
 (a, b) = (-(y - 1/2), x - 1/2) and kappa(x, y) as functions.  For S3 the launch table also times `pinn_term_residual_system_fn` on
 the same blocks with no function named, beside `pinn_term_residual_system_mixed`.
+
+`--system euler_nl` runs S7 beside S8: 1-D compressible flow in primitive variables (rho, u, p), whose momentum equation
+u_t + u u_x + p_x / (2 + rho) names the nonlinear factor 1 / (2 + rho) (`TermPDESystem(..., nonlinear=...)`, the element-wise
+kernel `pinn_term_residual_system_nl`), and S7, its twin with the same nine terms and the same factor counts in which that
+factor is the stream rho itself (`pinn_term_residual_system`).
 
 `--causal M,EPS` turns on the causal (time-weighted) residual loss (`training.causal_weighting`: M time bins, sharpness
 EPS): the autograd mode builds the weighted loss with torch ops on the residual tensor, the other two run the residual part
@@ -158,6 +163,23 @@ def _advection_diffusion():
             P.TermPDESystem(pc, ("c",), eqs, ic, functions=fns), 49729)
 
 
+def _euler(nonlinear):
+    """1-D compressible flow in (rho, u, p) on fourier 4x128, 49 729 points, periodic: rho_t + u rho_x + rho u_x,
+    u_t + u u_x + F p_x, p_t + u p_x + gamma p u_x with F = 1 / (2 + rho) as a nonlinear factor, or, in the twin, F = rho."""
+    F = "ir" if nonlinear else "rho"
+    eqs = [[(1.0, ("rho_t",)), (1.0, ("u", "rho_x")), (1.0, ("rho", "u_x"))],
+           [(1.0, ("u_t",)), (1.0, ("u", "u_x")), (1.0, (F, "p_x"))],
+           [(1.0, ("p_t",)), (1.0, ("u", "p_x")), ((1.0, "gamma"), ("p", "u_x"))]]
+    net = B.model("fourier", 128, 4, "tanh", input_dim=2, output_dim=3)
+    pc = P.PDEConfig(name="euler_nl" if nonlinear else "euler_twin", domain=[(0.0, 1.0)], time_domain=(0.0, 1.0), parameters={"gamma": 1.4},
+                     boundary_conditions={"periodic": {}}, initial_condition={}, exact_solution={}, dimension=1, device=B.dev)
+    ic = lambda x: torch.stack([0.2 * torch.sin(2 * math.pi * x[:, 0]), 0.5 * torch.cos(2 * math.pi * x[:, 0]),  # noqa: E731
+                                1.0 + 0.1 * torch.sin(2 * math.pi * x[:, 0])], 1)
+    label = "Euler 1D (rho, u, p) with 1 / (2 + rho) as a nonlinear factor" if nonlinear else "Euler 1D twin (rho in place of 1 / (2 + rho))"
+    return (f"{label} as TermPDESystem, fourier 4x128", net,
+            P.TermPDESystem(pc, ("rho", "u", "p"), eqs, ic, nonlinear={"ir": ("recip", "rho", {"shift": 2.0})} if nonlinear else None), 49729)
+
+
 def _system(which):
     """Coupled systems as `TermPDESystem` on fourier 4x128 with one output per field, 49 729 points."""
     forced = which == "navier_stokes_forced"
@@ -212,7 +234,8 @@ ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2),
               "M1": lambda: _heat_nd(2), "M2": lambda: _mixed_2d("aniso"), "M3": lambda: _mixed_2d("ch"),
               "S1": lambda: _system("gray_scott"), "S2": lambda: _system("navier_stokes"),
               "S3": lambda: _elasticity(True), "S4": lambda: _elasticity(False),
-              "S5": lambda: _system("navier_stokes_forced"), "S6": _advection_diffusion}
+              "S5": lambda: _system("navier_stokes_forced"), "S6": _advection_diffusion,
+              "S7": lambda: _euler(False), "S8": lambda: _euler(True)}
 
 
 def build(tag, adaptive="none", smoothness=0.0, term_pde=False, causal=None):
@@ -403,7 +426,8 @@ def time_system_launches(tag, iters=20):
     n = int(x.shape[0])
     flat, s = E.new_flat_grad(prog, B.dev), torch.zeros(1, device=B.dev)
     jets = E._system_jets(prog, td, x, t)
-    entry = ("pinn_term_residual_system_fn + the functions' torch ops" if isinstance(td, E.FnSystemTermDesc) else
+    entry = ("pinn_term_residual_system_nl" if isinstance(td, E.NlSystemTermDesc) else
+             "pinn_term_residual_system_fn + the functions' torch ops" if isinstance(td, E.FnSystemTermDesc) else
              "pinn_term_residual_system_mixed" if isinstance(td, E.MixedSystemTermDesc) else "pinn_term_residual_system")
     _, cot = E._term_residual_sys(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
     calls = []
@@ -423,7 +447,7 @@ def time_system_launches(tag, iters=20):
                       lambda: E.term_residual_system_mixed(tm, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
         calls.append(("pinn_term_residual_system_mixed, all pair orders 0 (residuals only, one launch)",
                       lambda: E.term_residual_system_mixed(tm, jets, x, t)))
-    if isinstance(td, E.FnSystemTermDesc):  # the kernel alone on values held, and the evaluation of the functions alone
+    if isinstance(td, E.FnSystemTermDesc) and not isinstance(td, E.NlSystemTermDesc):  # the kernel alone on values held, and the evaluation of the functions alone
         fv = td.fn_values(x, t)
         calls.append(("pinn_term_residual_system_fn on given values (loss sum + cotangents, two launches)",
                       lambda: E.term_residual_system_fn(td, jets, fv, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s,
@@ -509,15 +533,16 @@ def main():
     ap.add_argument("--term-mixed", action="store_true",
                     help="M1, M2, M3: 2-D heat (TermPDEnD), anisotropic diffusion and Cahn-Hilliard (TermPDEMixed), fourier 4x128")
     ap.add_argument("--system", choices=["gray_scott", "navier_stokes", "elasticity", "elasticity_nomixed", "navier_stokes_forced",
-                                         "advection_diffusion"], default=None,
+                                         "advection_diffusion", "euler_nl"], default=None,
                     help="N1, S1 (gray_scott) or N2, S2 (navier_stokes): a TermPDESystem beside the single-field step; S3 (elasticity): 2-D "
                          "elasticity as a TermPDESystemMixed; S4 (elasticity_nomixed): the same without its mixed terms; S2, S5 "
                          "(navier_stokes_forced): Navier-Stokes and its twin with a body force given as functions; S6 "
-                         "(advection_diffusion): one field with a(x,y), b(x,y), kappa(x,y) as functions; fourier 4x128")
+                         "(advection_diffusion): one field with a(x,y), b(x,y), kappa(x,y) as functions; S7, S8 (euler_nl): 1-D Euler in "
+                         "(rho, u, p) with 1 / (2 + rho) as a nonlinear factor beside its twin without; fourier 4x128")
     args = ap.parse_args()
     if args.system and args.configs == "C1,C2,C3,C4":
         args.configs = {"gray_scott": "N1,S1", "navier_stokes": "N2,S2", "elasticity": "S3", "elasticity_nomixed": "S4",
-                        "navier_stokes_forced": "S2,S5", "advection_diffusion": "S6"}[args.system]
+                        "navier_stokes_forced": "S2,S5", "advection_diffusion": "S6", "euler_nl": "S7,S8"}[args.system]
     if args.term_nd and args.configs == "C1,C2,C3,C4":
         args.configs = "N1,N2"
     if args.term_mixed and args.configs == "C1,C2,C3,C4":
@@ -580,7 +605,7 @@ def main():
             time_term_launches(tag)
         if args.term_mixed and tag in ND_CONFIGS:
             time_nd_launches(tag)
-        if args.system and tag in ("S1", "S2", "S3", "S4", "S5", "S6"):
+        if args.system and tag in ("S1", "S2", "S3", "S4", "S5", "S6", "S7", "S8"):
             time_system_launches(tag)
         if args.system and tag == "N2":
             time_nd_launches(tag)
