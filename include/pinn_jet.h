@@ -911,6 +911,69 @@ int pinn_term_residual_system_nl(const PinnTermPdeSystemNl* pde, const float* co
                                  float* eq_loss_sums, float* const* jet_cotangents, float* coef_grads, double* scratch,
                                  void* stream);
 
+/* ---- term residuals of coupled systems with learnable parameters (inverse problems) -----------------------------------------
+ * pinn_term_residual_system_nl with up to PINN_SYSTEM_MAX_PARAMS learnable scalars theta_p behind the coefficients and the
+ * entries of the nonlinear triples: a viscosity, a diffusion tensor, a Monod constant K in u / (K + u), an exponent.
+ *   coef_param[m]      -1, or the index p of the parameter c_m is a multiple of;
+ *   nl_param[k][j]     the same for shift (j = 0), scale (1) and exponent (2) of function k; a learnable exponent needs PINN_NL_POW;
+ *   param_values       n_params device floats, read at launch time like coef_values (no host copy: a captured graph follows an
+ *                      optimiser that updates them in place); may be NULL when every index is -1;
+ *   effective values   c_m = coef_param[m] < 0 ? coef_values[m] : coef_values[m] * param_values[coef_param[m]] (one rounding), and
+ *                      the same rule for each entry of a triple from nl_params: for a learnable entry the stored number is the
+ *                      scale.  A function outside the evaluation mask has none of its three entries read.
+ * Residuals, losses, cotangent blocks, eq_loss_sums and coef_grads are pinn_term_residual_system_nl's on the effective values,
+ * in its arithmetic and rounding order; coef_grads[m] is the derivative with respect to the EFFECTIVE c_m.  With n_params = 0
+ * and both parameter pointers NULL every output is bit-identical to pinn_term_residual_system_nl on the same inputs.
+ *   param_grads        nullable, n_params floats:
+ *                        param_grads[p] += sum_{m: coef_param[m] = p} coef_values[m] G_m
+ *                                        + sum_{(k, j): nl_param[k][j] = p} nl_params[3 k + j] H_kj,
+ *                      G_m = sum_n rbar prod_f phi_{m,f} (the coefficient sum), and with wbar_k the COMPLETE cotangent of w_k (after
+ *                      the pushes of the later functions, in descending k), slope = g_k'(arg_k) as tabulated above (without the
+ *                      scale) and s_k the source value:
+ *                        H_k0 = sum_n wbar_k * slope,   H_k1 = sum_n (wbar_k * slope) * s_k,
+ *                        H_k2 = sum_n (wbar_k * w_k) * logf(arg_k)          (PINN_NL_POW only).
+ *                      Each product is rounded to fp32 in the order written; the sums over the points are per-block partials in
+ *                      double, added in block order by the finish launch, which also forms the combination in double, over m,
+ *                      then over (k, j), ascending, and rounds once at the add to param_grads[p].  A function outside the mask
+ *                      contributes 0.  param_grads carries grad_scale, the equation weights and a given residual_cotangent exactly
+ *                      as coef_grads does (through rbar).  With jet_cotangents NULL the kernel still runs sweep 2 where an H sum is
+ *                      wanted, and the sums have the bits of the full call.  No atomics: two calls are bit-identical.
+ *   scratch            PINN_SYSTEM_INV_SCRATCH_DOUBLES doubles, 8-byte aligned: 64 blocks x {4 equation sums, 32 G, 12 H (3 k + j)}.
+ * Checked on the host before any HIP call: every check of pinn_term_residual_system_nl; n_params outside [0, 8]; a coef_param
+ * (m < n_terms) or nl_param (k < n_nonlinear) outside [-1, n_params); a learnable exponent on another operation than
+ * PINN_NL_POW; NULL param_values with any index >= 0 and N > 0; param_grads without scratch: PINN_ERR_BAD_DESC, the message
+ * naming the term or the function. */
+#define PINN_SYSTEM_MAX_PARAMS 8
+#define PINN_SYSTEM_INV_SCRATCH_DOUBLES (64 * (4 + 32 + 12))
+
+typedef struct PinnTermPdeSystemInv {
+  int32_t dimension;                                   /* the fields of PinnTermPdeSystemNl, in its order */
+  int32_t n_fields;
+  int32_t n_equations;
+  int32_t time_order[PINN_SYSTEM_MAX_FIELDS];
+  int32_t space_order[PINN_SYSTEM_MAX_FIELDS][3];
+  int32_t n_terms;
+  int32_t equation_of[PINN_SYSTEM_MAX_TERMS];
+  float eq_weight[PINN_SYSTEM_MAX_EQUATIONS];
+  int32_t loss;
+  float huber_delta;
+  PinnTermPdeTerm terms[PINN_SYSTEM_MAX_TERMS];
+  int32_t pair_order[PINN_SYSTEM_MAX_FIELDS][3];
+  int32_t n_functions;
+  int32_t n_nonlinear;
+  int32_t nl_op[PINN_SYSTEM_MAX_NONLINEAR];
+  int32_t nl_source[PINN_SYSTEM_MAX_NONLINEAR];
+  int32_t n_params;                                    /* 0 .. PINN_SYSTEM_MAX_PARAMS */
+  int32_t coef_param[PINN_SYSTEM_MAX_TERMS];           /* -1 or a parameter index */
+  int32_t nl_param[PINN_SYSTEM_MAX_NONLINEAR][3];      /* -1 or a parameter index: shift, scale, exponent */
+} PinnTermPdeSystemInv;
+
+int pinn_term_residual_system_inv(const PinnTermPdeSystemInv* pde, const float* coef_values, const float* const* jets,
+                                  const float* x, const float* t, const float* fn_values, const float* nl_params,
+                                  const float* param_values, int64_t N, float grad_scale, const float* residual_cotangent,
+                                  float* residual_out, float* loss_sum_out, float* eq_loss_sums, float* const* jet_cotangents,
+                                  float* coef_grads, float* param_grads, double* scratch, void* stream);
+
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (skipped when max_norm <= 0) followed by
  * torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay).step() on ONE flat fp32 buffer of n elements.
  * lr and step are DEVICE scalars (step = number of steps taken so far, incremented by the call) so that a captured

@@ -84,6 +84,9 @@ PINN_SYSTEM_MAX_NONLINEAR = 4
 PINN_TERM_NL = 31
 NL_OPS = {"exp": 0, "log": 1, "recip": 2, "sqrt": 3, "pow": 4, "tanh": 5, "sinh": 6, "cosh": 7, "sin": 8, "cos": 9}  # PINN_NL_*
 TERM_FACTOR_SYSTEM_NL = dict(TERM_FACTOR_SYSTEM_FN, **{f"nl{k}": 32 * k + PINN_TERM_NL for k in range(PINN_SYSTEM_MAX_NONLINEAR)})
+# pinn_term_residual_system_inv: up to eight learnable parameters behind the coefficients and the nonlinear triples
+PINN_SYSTEM_MAX_PARAMS = 8
+PINN_SYSTEM_INV_SCRATCH_DOUBLES = 64 * (4 + 32 + 12)
 # pinn_face_losses: the loss terms of per-face boundary conditions
 PINN_FACE_MAX_TERMS = 32
 PINN_FACE_SCRATCH_DOUBLES = 64 * PINN_FACE_MAX_TERMS
@@ -113,7 +116,7 @@ EXPORTS = (
     "pinn_unit_tail_plan", "pinn_term_residual", "pinn_causal_weights", "pinn_term_residual_axes",
     "pinn_term_residual_mixed", "pinn_lm_plan", "pinn_term_residual_system", "pinn_residual_unit_name",
     "pinn_face_losses", "pinn_term_residual_system_mixed", "pinn_term_residual_system_fn",
-    "pinn_term_residual_system_nl",
+    "pinn_term_residual_system_nl", "pinn_term_residual_system_inv",
 )
 
 
@@ -181,6 +184,11 @@ class PinnTermPdeSystemFn(ctypes.Structure):
 class PinnTermPdeSystemNl(ctypes.Structure):
     _fields_ = PinnTermPdeSystemFn._fields_ + [("n_nonlinear", ctypes.c_int32), ("nl_op", ctypes.c_int32 * PINN_SYSTEM_MAX_NONLINEAR),
                                                ("nl_source", ctypes.c_int32 * PINN_SYSTEM_MAX_NONLINEAR)]
+
+
+class PinnTermPdeSystemInv(ctypes.Structure):
+    _fields_ = PinnTermPdeSystemNl._fields_ + [("n_params", ctypes.c_int32), ("coef_param", ctypes.c_int32 * PINN_SYSTEM_MAX_TERMS),
+                                               ("nl_param", (ctypes.c_int32 * 3) * PINN_SYSTEM_MAX_NONLINEAR)]
 
 
 class PinnFaceTerm(ctypes.Structure):
@@ -338,6 +346,9 @@ def load():
         lib.pinn_term_residual_system_nl.restype = ctypes.c_int
         lib.pinn_term_residual_system_nl.argtypes = [P(PinnTermPdeSystemNl), vp, P(vp), vp, vp, vp, vp, i64, f32, vp, vp, vp, vp, P(vp),
                                                      vp, vp, vp]
+        lib.pinn_term_residual_system_inv.restype = ctypes.c_int
+        lib.pinn_term_residual_system_inv.argtypes = [P(PinnTermPdeSystemInv), vp, P(vp), vp, vp, vp, vp, vp, i64, f32, vp, vp, vp, vp,
+                                                      P(vp), vp, vp, vp, vp]
         lib.pinn_causal_weights.restype = ctypes.c_int
         lib.pinn_causal_weights.argtypes = [vp, vp, i64, i32, f64, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]
         lib.pinn_face_losses.restype = ctypes.c_int

@@ -732,6 +732,59 @@ class NlSystemTermDesc(FnSystemTermDesc):
                                 self.function_names, self.nonlinear_names, self.nl_values)
 
 
+class InvSystemTermDesc(NlSystemTermDesc):
+    """A `NlSystemTermDesc` with learnable parameters behind its numbers (`pinn_term_residual_system_inv`): an inverse problem.
+
+    The same arguments plus param_values, a contiguous float32 (P,) device tensor of at most eight parameters that the kernel
+    reads at LAUNCH time (an optimiser updates it in place), coef_param: per term -1 or the index of the parameter its
+    coefficient is a multiple of, and nl_param: per nonlinear function three such entries for shift, scale and exponent (a
+    learnable exponent on "pow" only).  For a learnable entry coef_values / nl_values hold the SCALE: the effective number is
+    scale * parameter.  `launches()`, `blocks()` and `with_loss` are the parent's (with_loss keeps the maps and the tensor)."""
+
+    _STRUCT = _lib.PinnTermPdeSystemInv
+
+    def __init__(self, terms: Sequence[Sequence[object]], equation_of: Sequence[int], coef_values: Tensor, dimension: int,
+                 n_fields: int, n_equations: int, nt: Sequence[int], nx: Sequence[Sequence[int]],
+                 pair: Optional[Sequence[Sequence[int]]] = None, functions: Sequence[Callable] = (),
+                 nonlinear: Sequence[Sequence[object]] = (), eq_weights: Optional[Sequence[float]] = None, loss: str = "mse",
+                 huber_delta: float = 1.0, function_names: Optional[Sequence[str]] = None,
+                 nonlinear_names: Optional[Sequence[str]] = None, nl_values: Optional[Tensor] = None,
+                 param_values: Optional[Tensor] = None, coef_param: Optional[Sequence[int]] = None,
+                 nl_param: Optional[Sequence[Sequence[int]]] = None):
+        super().__init__(terms, equation_of, coef_values, dimension, n_fields, n_equations, nt, nx, pair, functions, nonlinear,
+                         eq_weights, loss, huber_delta, function_names, nonlinear_names, nl_values)
+        T, K = len(self.terms), len(self.nonlinear)
+        P = 0 if param_values is None else int(param_values.numel())
+        if P > _lib.PINN_SYSTEM_MAX_PARAMS:
+            raise ValueError(f"param_values: at most {_lib.PINN_SYSTEM_MAX_PARAMS} learnable parameters (got {P})")
+        if param_values is not None and (param_values.dtype != torch.float32 or not param_values.is_contiguous() or param_values.dim() != 1):
+            raise ValueError(f"param_values: a contiguous float32 (P,) tensor (got {param_values.dtype} {tuple(param_values.shape)})")
+        cp = [-1] * T if coef_param is None else [int(v) for v in coef_param]
+        np_ = [(-1, -1, -1)] * K if nl_param is None else [tuple(int(v) for v in row) for row in nl_param]
+        if len(cp) != T or any(not -1 <= v < P for v in cp):
+            raise ValueError(f"coef_param: one entry per term ({T}), -1 or a parameter index below {P} (got {coef_param})")
+        if len(np_) != K or any(len(row) != 3 or any(not -1 <= v < P for v in row) for row in np_):
+            raise ValueError(f"nl_param: one (shift, scale, exponent) row per nonlinear function ({K}), -1 or a parameter index "
+                             f"below {P} (got {nl_param})")
+        for k, row in enumerate(np_):
+            if row[2] >= 0 and self.nonlinear[k][0] != "pow":
+                raise ValueError(f"nl_param[{k}]: a learnable exponent needs the operation 'pow' (got '{self.nonlinear[k][0]}')")
+        self.desc.n_params = P
+        for m in range(_lib.PINN_SYSTEM_MAX_TERMS):
+            self.desc.coef_param[m] = cp[m] if m < T else -1
+        for k in range(_lib.PINN_SYSTEM_MAX_NONLINEAR):
+            for j in range(3):
+                self.desc.nl_param[k][j] = np_[k][j] if k < K else -1
+        self.param_values, self.coef_param, self.nl_param = param_values, tuple(cp), tuple(np_)
+
+    def with_loss(self, loss: str, huber_delta: float = 1.0) -> "InvSystemTermDesc":
+        """The same program, tensors, functions and parameter maps under another loss kind."""
+        return InvSystemTermDesc(self.terms, self.equation_of, self.coef_values, self.dimension, self.n_fields, self.n_equations,
+                                 self.nt, self.nx, self.pair, self.functions, self.nonlinear, self.eq_weights, loss, huber_delta,
+                                 self.function_names, self.nonlinear_names, self.nl_values, self.param_values, self.coef_param,
+                                 self.nl_param)
+
+
 def pde_streams(pd) -> Tuple[int, int]:
     if isinstance(pd, SystemTermDesc):  # the set of field 0's axis-0 launch
         return pd.nt[0], pd.nx[0][0]
@@ -1053,16 +1106,54 @@ def term_residual_system_nl(td: NlSystemTermDesc, jets: Sequence[Optional[Tensor
                                  with_nl=True)
 
 
+def term_residual_system_inv(td: InvSystemTermDesc, jets: Sequence[Optional[Tensor]], fn_values: Optional[Tensor],
+                             nl_params: Optional[Tensor], param_values: Optional[Tensor], x: Tensor, t: Tensor,
+                             grad_scale: float = 0.0, residual_cotangent: Optional[Tensor] = None, want_residual: bool = True,
+                             loss_sum: Optional[Tensor] = None, want_cotangents: bool = False, coef_grads: Optional[Tensor] = None,
+                             eq_loss_sums: Optional[Tensor] = None,
+                             param_grads: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Optional[List[Optional[Tensor]]]]:
+    """`pinn_term_residual_system_inv`: `term_residual_system_nl` on the effective numbers — param_values a contiguous float32
+    (td.desc.n_params,) tensor on the device of the jets (`td.param_values`), read at launch time; None only where the
+    descriptor has no parameter.  coef_grads[m] is the sum with respect to the EFFECTIVE coefficient;
+    param_grads[p] += the derivative of the same scalar with respect to parameter p (>= n_params floats, accumulated)."""
+    K, KN, P = len(td.functions), len(td.nonlinear), int(td.desc.n_params)
+    if fn_values is None:
+        if K:
+            raise ValueError(f"term_residual_system_inv: fn_values is None but the descriptor has {K} functions")
+    elif (fn_values.dim() != 2 or fn_values.shape[0] != K or fn_values.dtype != torch.float32 or not fn_values.is_contiguous()):
+        raise ValueError(f"term_residual_system_inv: fn_values must be a contiguous float32 ({K}, N) tensor "
+                         f"(got {fn_values.dtype} {tuple(fn_values.shape)})")
+    if nl_params is None:
+        if KN:
+            raise ValueError(f"term_residual_system_inv: nl_params is None but the descriptor has {KN} nonlinear functions")
+    elif tuple(nl_params.shape) != (KN, 3) or nl_params.dtype != torch.float32 or not nl_params.is_contiguous():
+        raise ValueError(f"term_residual_system_inv: nl_params must be a contiguous float32 ({KN}, 3) tensor "
+                         f"(got {nl_params.dtype} {tuple(nl_params.shape)})")
+    if param_values is None:
+        if P:
+            raise ValueError(f"term_residual_system_inv: param_values is None but the descriptor has {P} parameters")
+    elif tuple(param_values.shape) != (P,) or param_values.dtype != torch.float32 or not param_values.is_contiguous():
+        raise ValueError(f"term_residual_system_inv: param_values must be a contiguous float32 ({P},) tensor "
+                         f"(got {param_values.dtype} {tuple(param_values.shape)})")
+    if param_grads is not None and (param_grads.dtype != torch.float32 or not param_grads.is_contiguous() or param_grads.numel() < P):
+        raise ValueError(f"term_residual_system_inv: param_grads must hold {P} contiguous float32 values")
+    return _term_residual_system("term_residual_system_inv", True, td, jets, x, t, grad_scale, residual_cotangent, want_residual,
+                                 loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=fn_values, nl_params=nl_params,
+                                 with_inv=True, param_values=None if param_values is None else param_values.detach(),
+                                 param_grads=param_grads)
+
+
 def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t, grad_scale, residual_cotangent, want_residual,
                           loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=None, with_fn=False, nl_params=None,
-                          with_nl=False):
-    """The body of `term_residual_system` / `term_residual_system_mixed` / `term_residual_system_fn` / `term_residual_system_nl`:
-    the checks, the buffers and the one call."""
+                          with_nl=False, with_inv=False, param_values=None, param_grads=None):
+    """The body of `term_residual_system` / `term_residual_system_mixed` / `term_residual_system_fn` / `term_residual_system_nl` /
+    `term_residual_system_inv`: the checks, the buffers and the one call."""
     lib = _lib.load()
     dim, C, E = td.dimension, td.n_fields, td.n_equations
     nb = _lib.PINN_SYSTEM_MIXED_BLOCKS(C) if mixed else 3 * C
     jets = list(jets) + [None] * (nb - len(jets))
-    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums, fn_values, nl_params)
+    dev = _require_device(*jets, x, t, td.coef_values, residual_cotangent, loss_sum, coef_grads, eq_loss_sums, fn_values, nl_params,
+                          param_values, param_grads)
     rows = []
     for c in range(C):
         rows += [1 + td.nt[c] + td.nx[c][0]] + [(1 + td.nx[c][a]) if (a < dim and td.nx[c][a] > 0) else 0 for a in (1, 2)]
@@ -1095,14 +1186,20 @@ def _term_residual_system(who: str, mixed: bool, td: SystemTermDesc, jets, x, t,
     cot = [torch.empty((k, N), dtype=torch.float32, device=dev) if k else None for k in rows] if want_cotangents else None
     if N == 0:
         return (r.t() if r is not None else None), cot
-    reduce = loss_sum is not None or coef_grads is not None or eq_loss_sums is not None
-    scratch = torch.empty(_lib.PINN_SYSTEM_SCRATCH_DOUBLES, dtype=torch.float64, device=dev) if reduce else None
+    reduce = loss_sum is not None or coef_grads is not None or eq_loss_sums is not None or param_grads is not None
+    doubles = _lib.PINN_SYSTEM_INV_SCRATCH_DOUBLES if with_inv else _lib.PINN_SYSTEM_SCRATCH_DOUBLES
+    scratch = torch.empty(doubles, dtype=torch.float64, device=dev) if reduce else None
     opt = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
     jptr = (ctypes.c_void_p * nb)(*[opt(j) for j in jets])
     cptr = (ctypes.c_void_p * nb)(*[opt(c) for c in cot]) if cot is not None else None
     entry = lib.pinn_term_residual_system_mixed if mixed else lib.pinn_term_residual_system
     with torch.cuda.device(dev):
-        if with_nl:
+        if with_inv:
+            _lib.check(lib.pinn_term_residual_system_inv(
+                ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), opt(fn_values), opt(nl_params),
+                opt(param_values), N, float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr,
+                opt(coef_grads), opt(param_grads), opt(scratch), _stream(dev)))
+        elif with_nl:
             _lib.check(lib.pinn_term_residual_system_nl(
                 ctypes.byref(td.desc), td.coef_values.data_ptr(), jptr, x.data_ptr(), t.data_ptr(), opt(fn_values), opt(nl_params), N,
                 float(grad_scale), opt(residual_cotangent), opt(r), opt(loss_sum), opt(eq_loss_sums), cptr, opt(coef_grads),
@@ -1126,6 +1223,13 @@ def _launch_line(key) -> dict:
 def _term_residual_sys(td: SystemTermDesc, jets, x, t, **kwargs):
     """The element-wise kernel of a system descriptor: the entry point of its class.  A `FnSystemTermDesc` has its functions
     evaluated here, once per call."""
+    param_grads = kwargs.pop("param_grads", None)
+    if isinstance(td, InvSystemTermDesc):
+        return term_residual_system_inv(td, jets, td.fn_values(x, t) if td.functions else None,
+                                        td.nl_values if td.nonlinear else None, td.param_values, x, t, param_grads=param_grads,
+                                        **kwargs)
+    if param_grads is not None:
+        raise ValueError("param_grads: only an `InvSystemTermDesc` has learnable parameters")
     if isinstance(td, NlSystemTermDesc):
         return term_residual_system_nl(td, jets, td.fn_values(x, t) if td.functions else None,
                                        td.nl_values if td.nonlinear else None, x, t, **kwargs)
@@ -1213,8 +1317,10 @@ def residual_forward(prog: NetProgram, pd, x: Tensor, t: Tensor, want_residual: 
 
 def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: float, flat_grad: Tensor,
                        want_residual: bool = False, loss_sum: Optional[Tensor] = None,
-                       coef_grads: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor]:
+                       coef_grads: Optional[Tensor] = None, param_grads: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor]:
     """One launch: flat_grad += grad_scale * d(sum_n l(r_n))/d(theta); returns (residual | None, loss_sum).
+    `param_grads` (an `InvSystemTermDesc` only; >= n_params floats on the device, accumulated): the same derivative with respect
+    to its learnable parameters, from the same element-wise launch.
     `coef_grads` (>= 2 floats on the device, accumulated): the same derivative w.r.t. the by-value coefficients
     pd.coef[0..1] through `pinn_residual_loss_grad_coef`, which runs on the layer-major engine only: the descriptor must
     carry PINN_FLAG_LAYER_MAJOR (`set_layer_major`).  Inverse problems use `residual_loss_grad_inverse`."""
@@ -1228,9 +1334,11 @@ def residual_loss_grad(prog: NetProgram, pd, x: Tensor, t: Tensor, grad_scale: f
         if N == 0:
             return (torch.empty((0, pd.n_equations), dtype=torch.float32, device=dev) if want_residual else None), s
         r, cot = _term_residual_sys(pd, _system_jets(prog, pd, x, t), x, t, grad_scale=grad_scale, want_residual=want_residual,
-                                    loss_sum=s, want_cotangents=True, coef_grads=coef_grads)
+                                    loss_sum=s, want_cotangents=True, coef_grads=coef_grads, param_grads=param_grads)
         _system_backward(prog, pd, x, t, cot, flat_grad)
         return r, s
+    if param_grads is not None:
+        raise ValueError("param_grads: only an `InvSystemTermDesc` has learnable parameters")
     if isinstance(pd, AxisTermDesc) and N:
         # the chain over the axes: one jet launch per axis, the element-wise residual with its loss sum and one block of
         # cotangents per launch, one reverse sweep per axis into the same flat gradient
@@ -1881,3 +1989,34 @@ class ResidualLossCoefFunction(torch.autograd.Function):
         for k, (shape, dtype) in enumerate(ctx.coef_meta):
             cgs.append((ctx.cg[k] * g).to(dtype).reshape(shape) if k < 2 and ctx.needs_input_grad[6 + k] else None)
         return (None, None, None, None, None, None, *cgs, *grads)
+
+
+class ResidualLossParamFunction(torch.autograd.Function):
+    """`ResidualLossFunction` for an `InvSystemTermDesc`: its (P,) parameter tensor `learned` is an input of the node, and its
+    gradient comes from the SAME chain as the weight gradient (`residual_loss_grad(..., param_grads=)`: one element-wise launch,
+    the sums combined on the device) — no torch formula, no second pass.  `learned` must be the tensor the descriptor reads
+    (`pd.param_values`): the kernel reads it at launch time."""
+
+    @staticmethod
+    def forward(ctx, prog: NetProgram, pd, x: Tensor, t: Tensor, n_total: int, learned: Tensor, *params: Tensor):
+        if not isinstance(pd, InvSystemTermDesc) or pd.param_values is None or pd.param_values.data_ptr() != learned.data_ptr():
+            raise ValueError("ResidualLossParamFunction: `learned` must be the param_values tensor of an InvSystemTermDesc")
+        need_grad = any(ctx.needs_input_grad[5:])
+        dev = x.device
+        ctx.prog = prog
+        if need_grad:
+            flat = new_flat_grad(prog, dev)
+            pg = torch.zeros(learned.numel(), dtype=torch.float32, device=dev)
+            _, s = residual_loss_grad(prog, pd, x, t, 1.0 / float(n_total), flat, param_grads=pg)
+            ctx.flat, ctx.pg = flat, pg
+        else:
+            _, s = residual_forward(prog, pd, x, t, want_residual=False)
+            ctx.flat, ctx.pg = None, None
+        return (s / float(n_total)).reshape(())
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        if ctx.flat is None:
+            return (None,) * 6 + (None,) * len(ctx.prog.tensors)
+        grads = split_flat_grad(ctx.prog, ctx.flat * g)
+        return (None, None, None, None, None, (ctx.pg * g) if ctx.needs_input_grad[5] else None, *grads)

@@ -22,7 +22,7 @@ import torch
 from .. import _lib
 from .. import engine as _E
 from .face_conditions import FaceConditions, check_face_arguments, check_term_count
-from .pde_base import PDEBase, PDEConfig, _pick_stream_set
+from .pde_base import PDEBase, PDEConfig, _jets_of, _pick_stream_set
 from .term_pde import Coef
 from .term_pde_nd import box_points
 
@@ -68,7 +68,7 @@ class TermPDESystem(PDEBase):
         source.  A source's stream counts towards the stream orders of its field exactly as a term factor does.  shift, scale
         and exponent (defaults 0, 1, 1) are a number, a parameter name of config.parameters or (number, "parameter name"); they
         are held in `nl_values`, a (K, 3) float32 device tensor built once beside `coef_values` and read at launch time, so
-        rewriting it in place changes the eager step and a captured one.  They are not trainable.  Names follow the rule for
+        rewriting it in place changes the eager step and a captured one.  They are trainable only through `learn` (below).  Names follow the rule for
         functions: an identifier without "_", none of x, y, z, t, sin, cos, no field, no function and no other nonlinear name.
         The gradient flows through g' to the source.  An argument outside the domain of g (log of a negative number, 1 / 0) is
         not checked: NaN or inf spreads into the loss.  ONLY THE VALUE of g is a factor: a space or time derivative of g(u) has
@@ -79,6 +79,26 @@ class TermPDESystem(PDEBase):
             TermPDESystem(cfg, ("u",), [[(1.0, ("u_t",)), (-1.0, ("u_xx",)), ((-1.0, "lam"), ("eu",))]], ic,
                           nonlinear={"eu": ("exp", "u")})
             nonlinear={"m": ("recip", "u", {"shift": "K"})}  with the term (1.0, ("u", "m"))
+    learn: {name: initial guess | None} with at most 8 names of config.parameters (None: start at the config's value): an inverse
+        problem.  A learnable name may stand wherever a parameter name may: a term coefficient (scale, "name"), or shift / scale /
+        exponent of `nonlinear` as "name" or (scale, "name") — the exponent under "pow" only.  A name that nothing uses, a name
+        missing from config.parameters and more than 8 names are refused.  `pde.learned` is ONE (P,) float32 nn.Parameter on the
+        device, in the order of `learn`: the buffer the kernel reads at launch time (for a learnable entry `coef_values` /
+        `nl_values` hold the scale, the effective number is scale * parameter).  `trainable_parameters_iter()` yields it, so
+        `PDETrainer`'s optimiser holds it; `learned_values()` returns {name: float}, and `get_parameter(name)` of a learnable name
+        its current value.  Under autograd `compute_loss(...)["total"].backward()` fills `pde.learned.grad` from the same chain
+        and kernel (`engine.ResidualLossParamFunction`); the launch list (Adam, fixed loss weights, eager and captured) steps it
+        with one more Adam call, unclipped.  With `learn` the descriptor is an `engine.InvSystemTermDesc`
+        (`pinn_term_residual_system_inv`); without, it is what it was.  config.trainable_parameters stays refused.
+            TermPDESystem(cfg, ("u",), [[(1.0, ("u_t",)), ((-1.0, "D"), ("u_xx",)), ((1.0, "R"), ("u", "m"))]], ic,
+                          nonlinear={"m": ("recip", "u", {"shift": "K"})}, learn={"D": 0.08, "R": None, "K": 2.5})
+    observations: {"x": (n, dim), "t": (n, 1), "u": (n, k), "fields": names} — data on k of the fields ("fields" defaults to all;
+        fields not named stay hidden, e.g. the pressure).  `compute_loss` returns "data" = sum over the observed fields of
+        mean l(u_c(obs) - target_c), which enters "total" with loss_weights["data"] (default 1).  On the launch list the points
+        are appended to the fixed points of the boundary / initial chain, one loss term per observed field, and count towards its
+        term limit (8, or 32 with face_conditions).  training.mode stays "forward"; config.observation_data and the data modes
+        stay refused.  Shapes, unknown field names and NaN / inf are refused here.  `initial_condition_fields=()` (then
+        initial_condition_fn may be None) is a problem known from data alone.
     equation_weights: omega_e >= 0 (default 1): the residual loss is sum_e omega_e mean l(r_e).
     initial_condition_fn(x: (n, dim)) -> (n, len(initial_condition_fields)); initial_condition_fields defaults to all fields.
     exact_solution_fn(x, t) -> (n, C): enables `validate()`.
@@ -114,7 +134,8 @@ class TermPDESystem(PDEBase):
                  boundary_points_per_axis: int = 16, initial_points_per_axis: int = 32,
                  face_conditions: Optional[Dict[str, Any]] = None,
                  functions: Optional[Dict[str, Callable[[torch.Tensor, torch.Tensor], torch.Tensor]]] = None,
-                 nonlinear: Optional[Dict[str, Sequence[Any]]] = None, **kwargs):
+                 nonlinear: Optional[Dict[str, Sequence[Any]]] = None, learn: Optional[Dict[str, Optional[float]]] = None,
+                 observations: Optional[Dict[str, Any]] = None, **kwargs):
         who = type(self).__name__
         dim = int(getattr(config, "dimension", 1))
         if dim not in (1, 2, 3):
@@ -133,7 +154,8 @@ class TermPDESystem(PDEBase):
         n_terms = sum(len(eq) for eq in equations)
         if n_terms > _lib.PINN_SYSTEM_MAX_TERMS:
             raise ValueError(f"{who}: {n_terms} terms over all equations; a system has at most {_lib.PINN_SYSTEM_MAX_TERMS}")
-        if not callable(initial_condition_fn):
+        no_initial = initial_condition_fields is not None and len(tuple(initial_condition_fields)) == 0
+        if not callable(initial_condition_fn) and not (no_initial and initial_condition_fn is None):
             raise TypeError(f"{who}: initial_condition_fn(x: (n, dim)) -> (n, number of initial fields) is required")
         if int(boundary_points_per_axis) < 2 or int(initial_points_per_axis) < 2:
             raise ValueError(f"{who}: at least 2 boundary and 2 initial points per axis")
@@ -293,19 +315,54 @@ class TermPDESystem(PDEBase):
         if len(set(ic_fields)) != len(ic_fields):
             raise ValueError(f"{who}: initial_condition_fields {ic_fields} repeat")
         self._ic_fields = tuple(index[name] for name in ic_fields)
+        # the data terms of `observations` (one per observed field) ride the same chain: they count
+        n_data = 0
+        if isinstance(observations, dict):
+            of = observations.get("fields")
+            n_data = C if of is None else (1 if isinstance(of, str) else len(tuple(of)))
         if self._faces is not None:
+            if n_data and n_bc_terms + len(self._ic_fields) + n_data > _lib.PINN_FACE_MAX_TERMS:
+                raise ValueError(f"{who}: the boundary / initial / data chain has {n_bc_terms + len(self._ic_fields) + n_data} loss terms "
+                                 f"({n_bc_terms} boundary + {len(self._ic_fields)} initial + {n_data} data); one pinn_face_losses call "
+                                 f"takes at most {_lib.PINN_FACE_MAX_TERMS}")
             check_term_count(who, n_bc_terms, len(self._ic_fields))
-        elif n_bc_terms + len(self._ic_fields) > PINN_MAX_POINT_TERMS:
+        elif n_bc_terms + len(self._ic_fields) + n_data > PINN_MAX_POINT_TERMS:
             raise NotImplementedError(
-                f"{who}: the boundary / initial chain has {n_bc_terms + len(self._ic_fields)} loss terms ({n_bc_terms} boundary + "
-                f"{len(self._ic_fields)} initial); one pinn_jet_losses call takes at most {PINN_MAX_POINT_TERMS}")
+                f"{who}: the boundary / initial chain has {n_bc_terms + len(self._ic_fields) + n_data} loss terms ({n_bc_terms} boundary + "
+                f"{len(self._ic_fields)} initial" + (f" + {n_data} data" if n_data else "") + f"); one pinn_jet_losses call takes at most "
+                f"{PINN_MAX_POINT_TERMS}")
         if list(getattr(config, "trainable_parameters", []) or []):
             raise NotImplementedError(f"{who}: trainable parameters (inverse problems) are not covered: the coefficients of a "
                                       "term residual are read by value")
+        # ---- learnable parameters: names of config.parameters behind term coefficients and nonlinear entries
+        learn = dict(learn or {})
+        if len(learn) > _lib.PINN_SYSTEM_MAX_PARAMS:
+            raise ValueError(f"{who}: learn names {len(learn)} parameters; a system learns at most {_lib.PINN_SYSTEM_MAX_PARAMS}")
+        used = {c[1] for c in self._term_coefs if isinstance(c, tuple)}
+        used |= {v[1] for spec in self._nl_specs for v in spec if isinstance(v, tuple)}
+        for name, guess in learn.items():
+            if not isinstance(name, str) or name not in (getattr(config, "parameters", None) or {}):
+                raise ValueError(f"{who}: learn names '{name}', which is not in config.parameters")
+            if name not in used:
+                raise ValueError(f"{who}: learn names '{name}', which no term coefficient and no nonlinear shift / scale / exponent uses")
+            if guess is not None and not (isinstance(guess, (int, float)) and float(guess) == float(guess)
+                                          and abs(float(guess)) != float("inf")):
+                raise ValueError(f"{who}: learn['{name}'] = {guess!r}: a finite initial guess, or None for the config's value")
+        for (name, op, _), spec in zip(self._nonlinear, self._nl_specs):
+            if isinstance(spec[2], tuple) and spec[2][1] in learn and op != "pow":
+                raise ValueError(f"{who}: nonlinear '{name}': the exponent '{spec[2][1]}' is learnable, which needs the operation 'pow' "
+                                 f"(got '{op}': it does not read the exponent)")
+        self._learn: Tuple[str, ...] = tuple(learn)
         super().__init__(config)
         self.config.output_dim = C
         if self._training_mode() != "forward" or self.observation_data:
             raise NotImplementedError(f"{who}: data modes and observation data are not covered (forward problems only)")
+        # the one (P,) tensor the kernel reads at launch time and the optimiser updates in place, in the order of `learn`
+        self.learned: Optional[torch.nn.Parameter] = None
+        if self._learn:
+            init = [float(self.config.parameters[name]) if learn[name] is None else float(learn[name]) for name in self._learn]
+            self.learned = torch.nn.Parameter(torch.tensor(init, dtype=torch.float32, device=self.device))
+        self._obs = self._check_observations(who, observations, index)
         for coef in self._term_coefs:
             if isinstance(coef, tuple) and self.get_parameter(coef[1]) is None:
                 raise ValueError(f"{who}: coefficient parameter '{coef[1]}' is not in config.parameters")
@@ -351,8 +408,65 @@ class TermPDESystem(PDEBase):
     def n_equations(self) -> int:
         return len(self._eq_weights)
 
+    def _stored(self, v):
+        """The number the kernel is handed for a coefficient or a nonlinear entry: the value, or for a learnable entry its SCALE
+        (the kernel multiplies it with the parameter it reads from `learned`)."""
+        if not isinstance(v, tuple):
+            return v
+        return v[0] if v[1] in self._learn else v[0] * float(self.get_parameter(v[1], required=True))
+
     def _coefficients(self):
-        return tuple(c[0] * float(self.get_parameter(c[1], required=True)) if isinstance(c, tuple) else c for c in self._term_coefs)
+        return tuple(self._stored(c) for c in self._term_coefs)
+
+    def get_parameter(self, name: str, default=None, required: bool = False):
+        """`PDEBase.get_parameter`; a learnable name returns its CURRENT value (a host read of `learned`)."""
+        learn = getattr(self, "_learn", ())
+        if name in learn and getattr(self, "learned", None) is not None:
+            return float(self.learned.detach()[learn.index(name)].cpu())
+        return super().get_parameter(name, default, required)
+
+    def trainable_parameters_iter(self):
+        """The learnable parameter tensor, so that `PDETrainer`'s optimiser holds it beside the network's."""
+        return iter([self.learned]) if self._learn else super().trainable_parameters_iter()
+
+    def learned_values(self) -> Dict[str, float]:
+        """{name: current value} of the learnable parameters, in the order of `learn`."""
+        if not self._learn:
+            return {}
+        vals = self.learned.detach().cpu().tolist()
+        return {name: float(v) for name, v in zip(self._learn, vals)}
+
+    def _param_index(self, v) -> int:
+        return self._learn.index(v[1]) if isinstance(v, tuple) and v[1] in self._learn else -1
+
+    def _check_observations(self, who: str, obs, index: Dict[str, int]):
+        """The `observations` keyword as device tensors: {"x": (n, dim), "t": (n, 1), "u": (k, n) one contiguous row per observed
+        field, "fields": their indices}, or None."""
+        if obs is None:
+            return None
+        if not isinstance(obs, dict) or set(obs) - {"x", "t", "u", "fields"} or not {"x", "t", "u"} <= set(obs):
+            raise ValueError(f"{who}: observations is a mapping with 'x': (n, {self.dimension}), 't': (n, 1), 'u': (n, k) and "
+                             "optionally 'fields'")
+        names = self.fields if obs.get("fields") is None else ((obs["fields"],) if isinstance(obs["fields"], str) else tuple(obs["fields"]))
+        for name in names:
+            if name not in index:
+                raise ValueError(f"{who}: observations names the field '{name}', which is none of the fields {self.fields}")
+        if not names or len(set(names)) != len(names):
+            raise ValueError(f"{who}: observations['fields'] {names}: at least one field, none twice")
+        dev = self.device
+        x, t, u = (torch.as_tensor(obs[k], dtype=torch.float32).detach() for k in ("x", "t", "u"))
+        n = x.shape[0] if x.dim() == 2 else -1
+        if x.dim() != 2 or x.shape[1] != self.dimension or n < 1:
+            raise ValueError(f"{who}: observations['x'] has shape {tuple(x.shape)}, expected (n, {self.dimension}) with n >= 1")
+        if tuple(t.shape) != (n, 1):
+            raise ValueError(f"{who}: observations['t'] has shape {tuple(t.shape)}, expected ({n}, 1)")
+        if tuple(u.shape) != (n, len(names)):
+            raise ValueError(f"{who}: observations['u'] has shape {tuple(u.shape)}, expected ({n}, {len(names)}): one column per "
+                             f"observed field {names}")
+        if not (bool(torch.isfinite(x).all()) and bool(torch.isfinite(t).all()) and bool(torch.isfinite(u).all())):
+            raise ValueError(f"{who}: observations hold NaN or inf")
+        return {"x": x.to(dev).contiguous(), "t": t.to(dev).contiguous(), "u": u.t().contiguous().to(dev),
+                "fields": tuple(index[name] for name in names), "n": n}
 
     def _has_trainable_coefficients(self) -> bool:
         return False
@@ -364,8 +478,10 @@ class TermPDESystem(PDEBase):
         if self._coef_values is None or self._coef_device != dev:
             self._coef_values = torch.tensor([float(c) for c in self._coefficients()], dtype=torch.float32, device=dev).reshape(-1)
             self._nl_values = torch.tensor(
-                [[v[0] * float(self.get_parameter(v[1], required=True)) if isinstance(v, tuple) else v for v in spec]
+                [[self._stored(v) for v in spec]
                  for spec in self._nl_specs], dtype=torch.float32, device=dev).reshape(len(self._nl_specs), 3)
+            if self.learned is not None and self.learned.device != self._coef_values.device:
+                self.learned.data = self.learned.data.to(self._coef_values.device)  # the same Parameter object: an optimiser keeps it
             self._coef_device = dev
             self._descs = {}
         return self._coef_values
@@ -382,6 +498,13 @@ class TermPDESystem(PDEBase):
         functions of the unknowns an `NlSystemTermDesc`."""
         cv = self.coef_values
         key = (loss, float(delta))
+        if key not in self._descs and self._learn:  # an inverse problem: the maps from terms and entries to `learned`
+            nl = [(op, src, 0.0, 1.0, 1.0) for _, op, src in self._nonlinear]
+            self._descs[key] = _E.InvSystemTermDesc(
+                self._term_factors, self._equation_of, cv, self.dimension, self.n_fields, self.n_equations, self._nt, self._nx,
+                getattr(self, "_pair", None), [g for _, g in self._functions], nl, self._eq_weights, loss, delta,
+                [name for name, _ in self._functions], [name for name, _, _ in self._nonlinear], self.nl_values, self.learned,
+                [self._param_index(c) for c in self._term_coefs], [[self._param_index(v) for v in spec] for spec in self._nl_specs])
         if key not in self._descs and self._nonlinear:
             nl = [(op, src, 0.0, 1.0, 1.0) for _, op, src in self._nonlinear]  # the numbers are in nl_values
             self._descs[key] = _E.NlSystemTermDesc(self._term_factors, self._equation_of, cv, self.dimension, self.n_fields,
@@ -397,7 +520,7 @@ class TermPDESystem(PDEBase):
         return self._descs[key]
 
     def _term_desc(self, loss: str, delta: float) -> "_E.SystemTermDesc":
-        if self._functions or self._nonlinear:
+        if self._functions or self._nonlinear or self._learn:
             return self._fn_desc(loss, delta)
         cv = self.coef_values
         key = (loss, float(delta))
@@ -449,8 +572,11 @@ class TermPDESystem(PDEBase):
         if self._points is not None and self._points[0] == dev:
             return self._points[1]
         pts = box_points(self.domain, self.time_domain, self.dimension, self._nb, self._ni, dev)
-        with torch.no_grad():
-            u0 = self._initial_condition_fn(pts["xi"])
+        if self._ic_fields:
+            with torch.no_grad():
+                u0 = self._initial_condition_fn(pts["xi"])
+        else:  # a problem known only from data: no initial term, the function is not called
+            u0 = torch.zeros((pts["n_ic"], 0), dtype=torch.float32, device=dev)
         u0 = (u0.reshape(-1, 1) if u0.dim() == 1 else u0).float()
         if tuple(u0.shape) != (pts["n_ic"], len(self._ic_fields)):
             raise ValueError(f"{type(self).__name__}: initial_condition_fn returned {tuple(u0.shape)} for {pts['n_ic']} points, expected "
@@ -492,7 +618,27 @@ class TermPDESystem(PDEBase):
         for k, c in enumerate(self._ic_fields):
             initial_loss = initial_loss + self._apply_loss_fn(u[nbc:, c] - P["u0"][k])
         zero = torch.zeros((), device=dev)
-        return self._compose_losses(residual_loss, boundary_loss, initial_loss, zero, zero, aux_scale)
+        data_loss = zero
+        if self._obs is not None:  # sum over the observed fields of mean l(u_c(obs) - target_c); the other fields stay hidden
+            uo = model(torch.cat([self._obs["x"], self._obs["t"]], dim=1))
+            for k, c in enumerate(self._obs["fields"]):
+                data_loss = data_loss + self._apply_loss_fn(uo[:, c] - self._obs["u"][k])
+        return self._compose_losses(residual_loss, boundary_loss, initial_loss, zero, data_loss, aux_scale)
+
+    def _residual_loss(self, model, x: torch.Tensor, t: torch.Tensor, n_total: Optional[int] = None) -> torch.Tensor:
+        """`PDEBase._residual_loss`; with `learn` the node also carries d loss / d learned, from the same chain
+        (`engine.ResidualLossParamFunction`)."""
+        if not self._learn:
+            return super()._residual_loss(model, x, t, n_total)
+        if self._causal_weighting() is not None:
+            raise NotImplementedError(f"{type(self).__name__}: causal weighting with learn is not covered")
+        _jets_of(model)
+        self._prepare_model(model)
+        prog = model.program()
+        x = x.detach().to(self.device)
+        t = t.detach().to(self.device)
+        n = int(n_total) if n_total is not None else x.shape[0]
+        return _E.ResidualLossParamFunction.apply(prog, self._pde_desc(), x, t, n, self.learned, *prog.tensors)
 
     def _manual_chain(self, n_batch: int) -> Dict[str, Any]:
         """`compute_loss`' boundary / initial part as data for the launch list.  "components" = C: the value rows of the C
@@ -502,10 +648,33 @@ class TermPDESystem(PDEBase):
         lw = self._loss_weights()
         bw, iw = (lw.get("boundary", 10.0), lw.get("initial", 10.0)) if lw else (10.0, 10.0)
         nbc, nf = P["n_bc"], P["n_face"]
+        obs = self._obs
+        xs, ts, n_fixed = P["x"], P["t"], P["x"].shape[0]
+        dw = 1.0
+        if obs is not None:  # the observation points behind the fixed ones; one loss term per observed field, its field the stream
+            xs, ts = torch.cat([P["x"], obs["x"]], 0).contiguous(), torch.cat([P["t"], obs["t"]], 0).contiguous()
+            dw = float(self._data_loss_weight(1.0))
         if self._faces is not None:  # no "terms": "face" holds the jet launches and the pinn_face_losses table
             initial = [(c, P["u0"][k], float(iw)) for k, c in enumerate(self._ic_fields)]
-            return {"x": P["x"], "t": P["t"], "nt": 0, "nx": 0, "terms": [], "n_bc": len(self._faces), "components": self.n_fields,
-                    "face": self._faces.chain(P, P["face_targets"], float(bw), initial)}
+            face = self._faces.chain(P, P["face_targets"], float(bw), initial)
+            out = {"x": xs, "t": ts, "nt": 0, "nx": 0, "terms": [], "n_bc": len(self._faces), "components": self.n_fields, "face": face}
+            if obs is not None:
+                # the value launch of an observed field is extended over the observation points (a field without one gets a launch
+                # over them alone); the data terms come after the initial ones
+                launches = list(face["launches"])
+                for k, c in enumerate(obs["fields"]):
+                    hit = [i for i, (lo, hi, nt, nx, axis, comp) in enumerate(launches)
+                           if (lo, nt, nx, axis, comp) == (0, 0, 0, 0, c) and hi >= n_fixed]
+                    if hit:
+                        launches[hit[0]] = (0, n_fixed + obs["n"], 0, 0, 0, c)
+                        where = (hit[0], 0, n_fixed)
+                    else:
+                        launches.append((n_fixed, n_fixed + obs["n"], 0, 0, 0, c))
+                        where = (len(launches) - 1, 0, 0)
+                    face["terms"].append({"n": obs["n"], "alpha": 1.0, "beta": 0.0, "target": obs["u"][k], "weight": dw, "value": where})
+                face["launches"] = launches
+                out["n_data"] = len(obs["fields"])
+            return out
         terms = []
         for c in range(self.n_fields):
             if self._bc[0] == "dirichlet":
@@ -516,4 +685,8 @@ class TermPDESystem(PDEBase):
         n_bc_terms = len(terms)
         for k, c in enumerate(self._ic_fields):
             terms.append((nbc, nbc + P["n_ic"], c, 0, P["u0"][k], float(iw)))
-        return {"x": P["x"], "t": P["t"], "nt": 0, "nx": 0, "terms": terms, "n_bc": n_bc_terms, "components": self.n_fields}
+        out = {"x": xs, "t": ts, "nt": 0, "nx": 0, "terms": terms, "n_bc": n_bc_terms, "components": self.n_fields}
+        if obs is not None:
+            terms += [(n_fixed, n_fixed + obs["n"], c, 0, obs["u"][k], dw) for k, c in enumerate(obs["fields"])]
+            out["n_data"] = len(obs["fields"])
+        return out

@@ -76,7 +76,7 @@ class TermPDESystemMixed(TermPDESystem):
                 self._pair_rows[c][k] = 2
 
     def _term_desc(self, loss: str, delta: float) -> "_E.MixedSystemTermDesc":
-        if self._functions or self._nonlinear:  # functions as factors: the parent's descriptor, with this class's pair orders
+        if self._functions or self._nonlinear or self._learn:  # the parent's descriptor, with this class's pair orders
             return self._fn_desc(loss, delta)
         cv = self.coef_values
         key = (loss, float(delta))

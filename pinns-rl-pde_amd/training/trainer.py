@@ -573,6 +573,8 @@ class PDETrainer:
         tc = self.config.training
         if len(getattr(self.pde, "_trainable_params", {})) or self.pde._has_trainable_coefficients():
             return "L-BFGS with trainable PDE coefficients (the flat vector would be [theta || coefficients])"
+        if getattr(self.pde, "_learn", ()):
+            return "L-BFGS with learn (learnable parameters of a term system: the flat vector would be [theta || parameters])"
         if self.process_group is not None:
             return "L-BFGS under a process group"
         if self.use_adaptive_weights:
@@ -690,6 +692,24 @@ class PDETrainer:
                       "pd_inverse": _E.pde_desc(self.pde.KIND, self.pde.dimension, [], self.pde._loss_function_name(),
                                                 self.pde._huber_delta())})
         F = self._flat
+        learned = getattr(self.pde, "learned", None)
+        if learned is not None:
+            # a term system with `learn`: its (P,) parameter tensor IS the buffer the kernel reads, so it stays where it is; beside
+            # it its own Adam moments and step counter (those of eager steps taken so far come along), and a slice of the gradient
+            # buffer behind the loss sum that the residual launch writes d loss / d parameters into
+            P = int(learned.numel())
+            self.pde.coef_values  # places `learned` on the PDE's device
+            lm, lv = torch.zeros(P, dtype=torch.float32, device=dev), torch.zeros(P, dtype=torch.float32, device=dev)
+            lsteps = 0.0
+            st = self.optimizer.state.get(learned, {})
+            if "exp_avg" in st:
+                lm.copy_(st["exp_avg"].reshape(-1))
+                lv.copy_(st["exp_avg_sq"].reshape(-1))
+                lsteps = float(st["step"])
+            F["grad"] = torch.zeros(n + 4 + 8, dtype=torch.float32, device=dev)  # [gradient | loss sum, pad | parameter gradients]
+            F.update({"learn": learned.data, "learn_m": lm, "learn_v": lv, "learn_grad": F["grad"][n + 4 : n + 4 + P],
+                      "learn_step": torch.tensor([lsteps], dtype=torch.float32, device=dev),
+                      "learn_scratch": torch.zeros(64, dtype=torch.float32, device=dev)})
         F["extra"] = torch.zeros(2, dtype=torch.float32, device=dev)  # {initial, data} when the chain carries a data term
         if self._causal is not None:
             # causal weighting: the sharpness as a device scalar (read at launch time: `set_causal_eps`), the bin means and
@@ -730,7 +750,8 @@ class PDETrainer:
             ch = dict(self.pde._manual_chain(int(n_batch)))
             dev = self.device
             obs = getattr(self.pde, "observation_data", None)
-            ch["has_data"] = False
+            ch["has_data"] = bool(ch.get("n_data"))  # a term system's `observations`: its chain carries the data terms already
+            ch.setdefault("n_data", 1)
             if obs and self.pde._training_mode() in ("inverse", "data_augmented"):
                 # the data term l(model(obs) - u_obs) (pde_base.py:281-291): one more point range and one more term of the chain
                 dw = self.pde._data_loss_weight(1.0)
@@ -836,6 +857,9 @@ class PDETrainer:
             _E.adam_clip_step(F["coef"][lo:hi], F["coef_grad"][lo:hi], F["coef_m"][lo:hi], F["coef_v"][lo:hi], F["lr"],
                               F["coef_step"], F["coef_scratch"], beta1=F["betas"][0], beta2=F["betas"][1], eps=F["eps"],
                               weight_decay=F["wd"], max_norm=0.0)
+        if "learn" in F:  # the same rule for the learnable parameters of a term system: unclipped, the shared lr
+            _E.adam_clip_step(F["learn"], F["learn_grad"], F["learn_m"], F["learn_v"], F["lr"], F["learn_step"], F["learn_scratch"],
+                              beta1=F["betas"][0], beta2=F["betas"][1], eps=F["eps"], weight_decay=F["wd"], max_norm=0.0)
 
     def _loss_grad_launches(self, x, t, F, prog, pd, ch, side=None):
         """The launch list up to, but not including, its optimiser tail: leaves [flat gradient || loss sum] in F["grad"] and
@@ -861,6 +885,9 @@ class PDETrainer:
             if "coef" in F:  # trainable coefficients: read from the device buffer, cotangents into their gradient slots
                 _E.residual_loss_grad_inverse(prog, F["pd_inverse"], F["coef"], x, t, F["rw"] / float(N), F["grad"][:n],
                                               F["coef_grad"], loss_sum=F["grad"][n : n + 1])
+            elif "learn" in F:  # a term system with `learn`: the parameter gradients from the same element-wise launch
+                _E.residual_loss_grad(prog, pd, x, t, F["rw"] / float(N), F["grad"][:n], loss_sum=F["grad"][n : n + 1],
+                                      param_grads=F["learn_grad"])
             else:
                 _E.residual_loss_grad(prog, pd, x, t, F["rw"] / float(N), F["grad"][:n], loss_sum=F["grad"][n : n + 1])
 
@@ -930,10 +957,11 @@ class PDETrainer:
             _E.jets_backward(prog, sm["x3"], sm["t3"], 0, 0, sm["cot3"], F["grad"][:n])
         F["has_data"] = ch["has_data"]
         if ch["has_data"]:
-            # summary4's `initial` is "all terms after the boundary ones": split the data term (the last one) out of it
+            # summary4's `initial` is "all terms after the boundary ones": split the data terms (the last ones) out of it
             tl = ch["term_losses"]
-            F["extra"][0:1].copy_(tl[ch["n_bc"] : -1].sum(0, keepdim=True))
-            F["extra"][1:2].copy_(tl[-1:])
+            nd = int(ch["n_data"])
+            F["extra"][0:1].copy_(tl[ch["n_bc"] : tl.numel() - nd].sum(0, keepdim=True))
+            F["extra"][1:2].copy_(tl[tl.numel() - nd :].sum(0, keepdim=True))
 
     def _manual_launches_adaptive(self, x, t, F, prog, pd, ch, side=None):
         """The launch list with adaptive loss weights (RBW / LRW, trainer.py:586-684).  The weights are detached numbers, so

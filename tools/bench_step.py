@@ -4,7 +4,7 @@
                                [--adaptive {none,rbw,lrw}] [--repeats 1] [--optimizer {adam,lbfgs}] [--smoothness W]
                                [--term-pde] [--term-nd] [--term-mixed] [--causal M,EPS]
                                [--system {gray_scott,navier_stokes,elasticity,elasticity_nomixed,navier_stokes_forced,
-                                          advection_diffusion,euler_nl}]
+                                          advection_diffusion,euler_nl,navier_stokes_inverse}]
 
 One step = fresh collocation sample (the configuration's own sampler: uniform, or the DQN-adaptive sampler for C3) ->
 residual + boundary + initial loss terms -> gradient -> clip_grad_norm_ -> Adam, i.e. the reference's inner loop
@@ -62,6 +62,12 @@ the same blocks with no function named, beside `pinn_term_residual_system_mixed`
 u_t + u u_x + p_x / (2 + rho) names the nonlinear factor 1 / (2 + rho) (`TermPDESystem(..., nonlinear=...)`, the element-wise
 kernel `pinn_term_residual_system_nl`), and S7, its twin with the same nine terms and the same factor counts in which that
 factor is the stream rho itself (`pinn_term_residual_system`).
+
+`--system navier_stokes_inverse` runs S2 beside S9, its inverse twin: the same Navier-Stokes system with the convective
+coefficient lam and the viscosity nu learnable (`TermPDESystem(..., learn=...)`, starting off their true values) and velocity
+observations on 2 000 seeded points with the pressure hidden (`observations=`): the same launches over 2 000 more fixed points,
+the element-wise kernel `pinn_term_residual_system_inv`, which also returns d loss / d (lam, nu), and one more three-launch Adam
+step on the two parameters.  `--learned STEPS` then trains S9 for STEPS captured steps and prints the learned values.
 
 `--causal M,EPS` turns on the causal (time-weighted) residual loss (`training.causal_weighting`: M time bins, sharpness
 EPS): the autograd mode builds the weighted loss with torch ops on the residual tensor, the other two run the residual part
@@ -183,6 +189,7 @@ def _euler(nonlinear):
 def _system(which):
     """Coupled systems as `TermPDESystem` on fourier 4x128 with one output per field, 49 729 points."""
     forced = which == "navier_stokes_forced"
+    inverse = which == "navier_stokes_inverse"
     if which == "gray_scott":
         fields, eqs, dim, label = ("u", "v"), GRAY_SCOTT, 1, "Gray-Scott 1D (u, v)"
         bcs, ic, icf = {"periodic": {}}, (lambda x: torch.stack([1 - 0.5 * torch.exp(-50 * (x[:, 0] - 0.5) ** 2),
@@ -192,15 +199,28 @@ def _system(which):
         if forced:
             eqs = [NAVIER_STOKES[0] + [(-1.0, ("fx",))], NAVIER_STOKES[1] + [(-1.0, ("fy",))], NAVIER_STOKES[2]]
             label = "Navier-Stokes 2D (u, v, p) with a body force (fx, fy as functions)"
+        if inverse:  # lam in front of the four convective terms; lam and nu start off their true values 1 and 0.01
+            conv = lambda tm: ((1.0, "lam"), tm[1]) if len(tm[1]) == 2 else tm  # noqa: E731
+            eqs = [[conv(tm) for tm in NAVIER_STOKES[0]], [conv(tm) for tm in NAVIER_STOKES[1]], NAVIER_STOKES[2]]
+            label = "Navier-Stokes 2D (u, v, p), lam and nu learnable, 2 000 velocity observations"
         bcs = {"dirichlet": {"type": "fixed", "value": [0.0, 0.0, None]}}
         ic, icf = (lambda x: torch.stack([torch.sin(math.pi * x[:, 0]) * torch.sin(math.pi * x[:, 1]),
                                           torch.zeros_like(x[:, 0])], 1)), ("u", "v")
     net = B.model("fourier", 128, 4, "tanh", input_dim=dim + 1, output_dim=len(fields))
     pc = P.PDEConfig(name=which, domain=[(0.0, 1.0)] * dim, time_domain=(0.0, 1.0),
-                     parameters={"Du": 2e-5, "Dv": 1e-5, "F": 0.04, "Fk": 0.1, "nu": 0.01}, boundary_conditions=bcs,
+                     parameters={"Du": 2e-5, "Dv": 1e-5, "F": 0.04, "Fk": 0.1, "nu": 0.01, "lam": 1.0}, boundary_conditions=bcs,
                      initial_condition={}, exact_solution={}, dimension=dim, device=B.dev)
+    extra = {}
+    if inverse:
+        # velocity data of the decaying Taylor-Green-type field that the initial condition starts: u = e^(-2 pi^2 nu t) sin sin,
+        # v = 0 is no Navier-Stokes solution, so the learned values are informational only
+        g = torch.Generator().manual_seed(7)
+        xo, to = torch.rand(2000, 2, generator=g), torch.rand(2000, 1, generator=g)
+        uo = torch.exp(-2 * math.pi**2 * 0.01 * to[:, 0]) * torch.sin(math.pi * xo[:, 0]) * torch.sin(math.pi * xo[:, 1])
+        extra = {"learn": {"lam": 0.5, "nu": 0.05},
+                 "observations": {"x": xo, "t": to, "u": torch.stack([uo, torch.zeros_like(uo)], 1), "fields": ("u", "v")}}
     return (f"{label} as TermPDESystem, fourier 4x128", net,
-            P.TermPDESystem(pc, fields, eqs, ic, initial_condition_fields=icf, functions=_body_force() if forced else None), 49729)
+            P.TermPDESystem(pc, fields, eqs, ic, initial_condition_fields=icf, functions=_body_force() if forced else None, **extra), 49729)
 
 
 def _elasticity_equations(mixed):
@@ -235,7 +255,7 @@ ND_CONFIGS = {"N1": lambda: _heat_nd(1), "N2": lambda: _heat_nd(2),
               "S1": lambda: _system("gray_scott"), "S2": lambda: _system("navier_stokes"),
               "S3": lambda: _elasticity(True), "S4": lambda: _elasticity(False),
               "S5": lambda: _system("navier_stokes_forced"), "S6": _advection_diffusion,
-              "S7": lambda: _euler(False), "S8": lambda: _euler(True)}
+              "S7": lambda: _euler(False), "S8": lambda: _euler(True), "S9": lambda: _system("navier_stokes_inverse")}
 
 
 def build(tag, adaptive="none", smoothness=0.0, term_pde=False, causal=None):
@@ -426,7 +446,8 @@ def time_system_launches(tag, iters=20):
     n = int(x.shape[0])
     flat, s = E.new_flat_grad(prog, B.dev), torch.zeros(1, device=B.dev)
     jets = E._system_jets(prog, td, x, t)
-    entry = ("pinn_term_residual_system_nl" if isinstance(td, E.NlSystemTermDesc) else
+    entry = ("pinn_term_residual_system_inv" if isinstance(td, E.InvSystemTermDesc) else
+             "pinn_term_residual_system_nl" if isinstance(td, E.NlSystemTermDesc) else
              "pinn_term_residual_system_fn + the functions' torch ops" if isinstance(td, E.FnSystemTermDesc) else
              "pinn_term_residual_system_mixed" if isinstance(td, E.MixedSystemTermDesc) else "pinn_term_residual_system")
     _, cot = E._term_residual_sys(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)
@@ -440,6 +461,11 @@ def time_system_launches(tag, iters=20):
     calls.append((f"{entry} (loss sum + cotangents, two launches)",
                   lambda: E._term_residual_sys(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True)))
     calls.append((f"{entry} (residuals only, one launch)", lambda: E._term_residual_sys(td, jets, x, t)))
+    if isinstance(td, E.InvSystemTermDesc):  # the launch the step takes: with the parameter gradients
+        pg = torch.zeros(int(td.desc.n_params), device=B.dev)
+        calls.append((f"{entry} (loss sum + cotangents + param_grads, two launches)",
+                      lambda: E._term_residual_sys(td, jets, x, t, grad_scale=1.0 / n, want_residual=False, loss_sum=s, want_cotangents=True,
+                                                   param_grads=pg)))
     if tag == "S4":  # the same program and blocks through the mixed entry point with all pair orders 0: the larger LDS footprint
         tm = E.MixedSystemTermDesc(td.terms, td.equation_of, td.coef_values, td.dimension, td.n_fields, td.n_equations, td.nt, td.nx, None,
                                    td.eq_weights)
@@ -476,6 +502,22 @@ def time_system_launches(tag, iters=20):
         b.record()
         torch.cuda.synchronize()
         print(f"| {label} | {a.elapsed_time(b) / iters:.4f} |", flush=True)
+
+
+def learned_values(tag, steps):
+    """Train the inverse twin for `steps` captured steps (fresh samples, the default Adam) and print what it learned."""
+    torch.manual_seed(0)
+    name, net, eq, agent, cfg, n_req = build(tag)
+    tr = PDETrainer(net, eq, None, cfg, device=B.dev, fast_step=False)
+    tr._build_flat_state()
+    start = eq.learned_values()
+    replay, losses = tr.make_graphed_step(n_req)
+    for _ in range(steps):
+        replay()
+    torch.cuda.synchronize()
+    print()
+    print(f"{tag} after {steps} captured steps (lr {cfg.training.learning_rate:g}): learned {eq.learned_values()} from {start}; "
+          f"losses {({k: float(v) for k, v in losses.items()})}", flush=True)
 
 
 def time_causal_launches(tag, causal, iters=20):
@@ -533,16 +575,20 @@ def main():
     ap.add_argument("--term-mixed", action="store_true",
                     help="M1, M2, M3: 2-D heat (TermPDEnD), anisotropic diffusion and Cahn-Hilliard (TermPDEMixed), fourier 4x128")
     ap.add_argument("--system", choices=["gray_scott", "navier_stokes", "elasticity", "elasticity_nomixed", "navier_stokes_forced",
-                                         "advection_diffusion", "euler_nl"], default=None,
+                                         "advection_diffusion", "euler_nl", "navier_stokes_inverse"], default=None,
                     help="N1, S1 (gray_scott) or N2, S2 (navier_stokes): a TermPDESystem beside the single-field step; S3 (elasticity): 2-D "
                          "elasticity as a TermPDESystemMixed; S4 (elasticity_nomixed): the same without its mixed terms; S2, S5 "
                          "(navier_stokes_forced): Navier-Stokes and its twin with a body force given as functions; S6 "
                          "(advection_diffusion): one field with a(x,y), b(x,y), kappa(x,y) as functions; S7, S8 (euler_nl): 1-D Euler in "
-                         "(rho, u, p) with 1 / (2 + rho) as a nonlinear factor beside its twin without; fourier 4x128")
+                         "(rho, u, p) with 1 / (2 + rho) as a nonlinear factor beside its twin without; S2, S9 (navier_stokes_inverse): "
+                         "Navier-Stokes and its inverse twin with lam and nu learnable and velocity observations; fourier 4x128")
+    ap.add_argument("--learned", type=int, default=0, metavar="STEPS",
+                    help="S9 only: after the tables, train S9 for STEPS captured steps and print the learned values")
     args = ap.parse_args()
     if args.system and args.configs == "C1,C2,C3,C4":
         args.configs = {"gray_scott": "N1,S1", "navier_stokes": "N2,S2", "elasticity": "S3", "elasticity_nomixed": "S4",
-                        "navier_stokes_forced": "S2,S5", "advection_diffusion": "S6", "euler_nl": "S7,S8"}[args.system]
+                        "navier_stokes_forced": "S2,S5", "advection_diffusion": "S6", "euler_nl": "S7,S8",
+                        "navier_stokes_inverse": "S2,S9"}[args.system]
     if args.term_nd and args.configs == "C1,C2,C3,C4":
         args.configs = "N1,N2"
     if args.term_mixed and args.configs == "C1,C2,C3,C4":
@@ -605,8 +651,10 @@ def main():
             time_term_launches(tag)
         if args.term_mixed and tag in ND_CONFIGS:
             time_nd_launches(tag)
-        if args.system and tag in ("S1", "S2", "S3", "S4", "S5", "S6", "S7", "S8"):
+        if args.system and tag in ("S1", "S2", "S3", "S4", "S5", "S6", "S7", "S8", "S9"):
             time_system_launches(tag)
+        if args.learned > 0 and tag == "S9":
+            learned_values(tag, args.learned)
         if args.system and tag == "N2":
             time_nd_launches(tag)
         if causal is not None and not args.term_pde:
