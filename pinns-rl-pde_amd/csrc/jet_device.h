@@ -17,10 +17,14 @@ namespace pinn {
 constexpr int kMaxOrd = 4;
 
 // ---------------------------------------------------------------------------
-// sin and cos together, ~1 ulp for |x| < 2^13: Cody-Waite reduction by pi/2 in three exact pieces, then the
+// sin and cos together for |x| <= 2^13: Cody-Waite reduction by pi/2 in three exact pieces, then the
 // Cephes single-precision minimax polynomials on [-pi/4, pi/4].  The Fourier features evaluate 2*M of these per
 // point and SIREN one per hidden unit; the library sincosf (Payne-Hanek capable, ~150 instructions) made the
 // encoding the slowest phase of a tile.  Larger arguments take the library path.
+// Accuracy (tests/test_jet_device_gpu.py, profiles/jet_device_accuracy.md): the ABSOLUTE error stays below 1.6 x 2^-24
+// over the whole range (measured 1.55; 1.23 for |x| <= pi/4, where that is also 1.23 ulp of the result).  It is not a
+// bound in ulps of the result: the reduced argument carries an absolute error of that size, so near the zeros of sin
+// and cos the relative error grows with |x| (5.8 ulp below 64, 688 ulp at x = 0x1.17cc5p+12).  sin(-0.0f) is +0.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void fast_sincosf(float x, float* sn, float* cs) {
   if (fabsf(x) > 8192.0f) {
@@ -44,10 +48,13 @@ __device__ __forceinline__ void fast_sincosf(float x, float* sn, float* cs) {
 }
 
 // ---------------------------------------------------------------------------
-// tanh, branch-free, ~1-2 ulp: |z| < 0.625 -> the odd minimax polynomial the ROCm device library uses;
+// tanh, branch-free: |z| < 0.625 -> the odd minimax polynomial the ROCm device library uses;
 // otherwise 1 - 2 / (exp(2|z|) + 1) on v_exp_f32 / v_rcp_f32 (the argument error of the hardware exp2 is damped
 // by 2e/(e+1)^2 <= 0.35 in this range).  The library tanhf diverges on the 0.625 threshold, so a wave pays
 // for both of its branches (~45 instructions); this is ~20.
+// Accuracy measured on the MI355X over all of fp32 (tests/test_jet_device_gpu.py, profiles/jet_device_accuracy.md):
+// 0.64 ulp of the result on the polynomial branch, 1.55 ulp just above the switch (the library tanhf: 0.64 / 1.32);
+// |tanh| <= 1 always, tanh(+-0) = +-0, +-inf -> +-1, NaN -> NaN.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float fast_tanhf(float z) {
   const float a = fabsf(z);
@@ -56,10 +63,12 @@ __device__ __forceinline__ float fast_tanhf(float z) {
   p = fmaf(p, t, -0.053737930953502655f);
   p = fmaf(p, t, 0.13331416249275208f);
   p = fmaf(p, t, -0.3333328068256378f);
+  // The sign goes on last, over both branches: fmaf(z * t, p, z) is +0 at z = -0 (p < 0 makes the product +0), and every
+  // other z keeps its bits.  With the polynomial on |z| as well, jet_wide_1_4_0 / jet_widec_1_4_0 lost their VGPR-form build.
   const float small = fmaf(z * t, p, z);
   const float e = __builtin_amdgcn_exp2f(a * 2.8853900817779268f);  // exp(2a); +inf for large a -> big = 1
-  const float big = copysignf(fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f), z);
-  return a < 0.625f ? small : big;
+  const float big = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
+  return copysignf(a < 0.625f ? small : big, z);
 }
 
 // ---------------------------------------------------------------------------
