@@ -1,584 +1,15 @@
 // Coupled PDE systems with known functions of (x, t) as factors (include/pinn_jet.h, "term residuals of coupled systems with
-// known functions"): the element-wise middle of
-//   one pinn_jet_forward per (field, axis with streams) and per (field, pair of order 2: a component launch along e_a + e_b)
-//   -> pinn_term_residual_system_fn -> one pinn_jet_backward per block.
-// The kernel is term_system_mixed_kernels.hip's, kept in a translation unit of its own so that that kernel's code does not move:
-// one thread per point per grid-stride round, a point's values and accumulators in LDS, one column per thread, a factor's slot a
-// wave-uniform row offset, u_xy, u_xz, u_yz derived at load and spread again at write-out.  A known function g_k is, to the
-// kernel, one more value row: its value at the point is read once per round from row k of fn_values into row 16 C + k of the
-// thread's LDS column, only if a term names it (a host-made, wave-uniform mask); it takes part in the products at its position
-// and is no cotangent target.  Four more rows are 4 KB of LDS; held in registers behind a wave-uniform switch instead, the
-// function values pushed the forms with coefficient sums, whose term loop is unrolled over 32 terms of scalar operands, from
-// scalar spills into scratch memory.  Every other factor rounds exactly as in term_system_mixed_kernels.hip.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-
-#include "../../include/pinn_jet.h"
-
-namespace {
-
-constexpr int kSfBlocks = 64;                                             // fixed grid: the partials are summed in block order
-constexpr int kSfRow = PINN_SYSTEM_MAX_EQUATIONS + PINN_SYSTEM_MAX_TERMS;  // doubles per block: {equation loss sums, coefficient sums}
-constexpr int kSfVals = 16;  // value slots of a field: codes 0 .. 6, sin, cos, u_y, u_yy, u_z, u_zz, u_xy, u_xz, u_yz
-constexpr int kSfAcc = 14;   // derivative accumulators of a field: codes 0 .. 6, u_y, u_yy, u_z, u_zz, then g of the three pairs
-constexpr int kSfFns = PINN_SYSTEM_MAX_FUNCTIONS;  // function rows behind the C fields' value rows: slot 16 C + k is g_k
-constexpr int kSfCoord = PINN_SYSTEM_MAX_FIELDS * kSfVals + kSfFns;  // slots 68 .. 71: x, y, z, t (registers, not LDS)
-
-static_assert(PINN_SYSTEM_SCRATCH_DOUBLES == kSfBlocks * kSfRow, "scratch constant and grid disagree");
-static_assert(PINN_SYSTEM_MAX_FIELDS == 4 && PINN_SYSTEM_MAX_EQUATIONS == 4, "the kernel unrolls over four fields and four equations");
-static_assert(PINN_SYSTEM_MAX_FUNCTIONS == 4 && PINN_TERM_FN3 - PINN_TERM_FN0 == 3, "the kernel holds four function values in registers");
-
-enum { USE_X = 1, USE_Y = 2, USE_Z = 4, USE_T = 8 };
-
-// the descriptor as the kernel reads it: one byte per factor = its slot (field * 16 + value slot, 16 C + k the known function
-// g_k, 68 .. 71 a coordinate, 255 unused)
-struct SysFnProg {
-  int n_terms, n_eq, dim, loss;
-  float huber_delta;
-  int uses_coord;
-  int uses_fn;                                // bit k: a term names g_k (a row no term names is never read)
-  int nt[PINN_SYSTEM_MAX_FIELDS], nx0[PINN_SYSTEM_MAX_FIELDS], nx1[PINN_SYSTEM_MAX_FIELDS], nx2[PINN_SYSTEM_MAX_FIELDS];
-  int uses_trig[PINN_SYSTEM_MAX_FIELDS];
-  float gw[PINN_SYSTEM_MAX_EQUATIONS];        // grad_scale * eq_weight[e], rounded once on the host
-  double w[PINN_SYSTEM_MAX_EQUATIONS];        // eq_weight[e]
-  unsigned slots[PINN_SYSTEM_MAX_TERMS];      // byte f = slot of factor f
-  unsigned char n_factors[PINN_SYSTEM_MAX_TERMS];
-  unsigned char eq[PINN_SYSTEM_MAX_TERMS];
-  unsigned pairs;                             // bit 3 c + k: field c has pair k of (x,y), (x,z), (y,z) (pair_order 2)
-  const float* jets[6 * PINN_SYSTEM_MAX_FIELDS];  // 3 c + a: axis block (c, a);  3 C + 3 c + k: the P block of (c, pair k)
-  float* cot[6 * PINN_SYSTEM_MAX_FIELDS];     // all null when no cotangents are wanted
-};
-
-// l(r) and l'(r) of PDEBase._apply_loss_fn per sample (term_kernels.hip::term_loss)
-__device__ __forceinline__ float sxf_loss(int kind, float d, float r, float* dl) {
-  if (kind == PINN_LOSS_MAE) {
-    *dl = r > 0.0f ? 1.0f : (r < 0.0f ? -1.0f : 0.0f);
-    return fabsf(r);
-  }
-  if (kind == PINN_LOSS_HUBER) {
-    const float a = fabsf(r);
-    if (a < d) {
-      *dl = r;
-      return 0.5f * r * r;
-    }
-    *dl = r > 0.0f ? d : -d;
-    return d * (a - 0.5f * d);
-  }
-  *dl = 2.0f * r;
-  return r * r;
-}
-
-// row of block (c, 0) that holds code s (0 .. 6) in the (nt, nx) set, or -1 when the set does not hold it
-__host__ __device__ inline int sxf_row0(int code, int nt, int nx) {
-  if (code == 0) return 0;
-  if (code <= 2) return code <= nt ? code : -1;
-  return code - 2 <= nx ? nt + code - 2 : -1;
-}
-
-// value slot (0 .. 15) of a stream / trig / mixed code, or -1 for a coordinate or an unknown code
-__host__ inline int sxf_value_slot(int code) {
-  if (code >= 0 && code <= 6) return code;
-  if (code == PINN_TERM_SIN_U) return 7;
-  if (code == PINN_TERM_COS_U) return 8;
-  if (code >= PINN_TERM_UY && code <= PINN_TERM_UZZ) return 9 + (code - PINN_TERM_UY);
-  if (code >= PINN_TERM_UXY && code <= PINN_TERM_UYZ) return 13 + (code - PINN_TERM_UXY);
-  return -1;
-}
-
-// accumulator (field * 14 + k) the derivative of a value slot goes to: u, sin(u) and cos(u) all go to the value stream
-__device__ __forceinline__ int sxf_target(unsigned slot) {
-  const int c = (int)slot / kSfVals, v = (int)slot - c * kSfVals;
-  return c * kSfAcc + (v < 7 ? v : (v < 9 ? 0 : v - 2));
-}
-
-// the value of a slot: a wave-uniform row of this thread's LDS column (a field's value or a known function), or a coordinate
-// register
-__device__ __forceinline__ float sxf_value(const float* col, unsigned slot, float cx, float cy, float cz, float ct) {
-  if (slot < (unsigned)kSfCoord) return col[slot * 256];
-  switch (slot - kSfCoord) {
-    case 0: return cx;
-    case 1: return cy;
-    case 2: return cz;
-    default: return ct;
-  }
-}
-
-// C: the number of fields (sizes the LDS block);  REDUCE: loss and / or coefficient sums are wanted (per-block partials);
-// COEF: coefficient sums are wanted.  partial[b * kSfRow + e] = sum l(r_e,n), partial[b * kSfRow + 4 + m] = sum rbar_e(m),n
-// prod_f phi_{m,f} over block b's points.
-template <int C, bool REDUCE, bool COEF>
-__global__ __launch_bounds__(256) void term_system_fn_kernel(SysFnProg p, const float* __restrict__ coef, const float* __restrict__ x,
-                                                          const float* __restrict__ t, const float* __restrict__ fn, long long N,
-                                                       const float* __restrict__ rbar_in, float* __restrict__ residual_out,
-                                                       double* __restrict__ partial) {
-  __shared__ float sval[(C * kSfVals + kSfFns) * 256];
-  __shared__ float sacc[C * kSfAcc * 256];
-  float* vcol = sval + threadIdx.x;
-  float* acol = sacc + threadIdx.x;
-  double loss_acc[PINN_SYSTEM_MAX_EQUATIONS];
-#pragma unroll
-  for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e) loss_acc[e] = 0.0;
-  double cg[COEF ? PINN_SYSTEM_MAX_TERMS : 1];
-#pragma unroll
-  for (int m = 0; m < (COEF ? PINN_SYSTEM_MAX_TERMS : 1); ++m) cg[m] = 0.0;
-  const bool want_cot = p.cot[0] != nullptr;
-
-  for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < N; n += (long long)gridDim.x * 256) {
-    // ---- the values of every field ----
-    // the fields one after the other (not unrolled): only one field's block pointers are held in scalar registers at a time
-#pragma unroll 1
-    for (int c = 0; c < C; ++c) {
-      const float* __restrict__ j0 = p.jets[3 * c];
-      float* v = vcol + c * kSfVals * 256;
-#pragma unroll
-      for (int s = 0; s < 7; ++s) {
-        const int row = sxf_row0(s, p.nt[c], p.nx0[c]);
-        v[s * 256] = row >= 0 ? j0[(long long)row * N + n] : 0.0f;
-      }
-      if (p.uses_trig[c]) {
-        const float u = v[0];
-        v[7 * 256] = sinf(u);
-        v[8 * 256] = cosf(u);
-      }
-      const float* __restrict__ j1 = p.jets[3 * c + 1];
-      const float* __restrict__ j2 = p.jets[3 * c + 2];
-      v[9 * 256] = p.nx1[c] >= 1 ? j1[N + n] : 0.0f;
-      v[10 * 256] = p.nx1[c] >= 2 ? j1[2 * N + n] : 0.0f;
-      v[11 * 256] = p.nx2[c] >= 1 ? j2[N + n] : 0.0f;
-      v[12 * 256] = p.nx2[c] >= 2 ? j2[2 * N + n] : 0.0f;
-      // the derived factors, in the evaluation order the header states: u_ab = 0.5f * ((P_2 - A_2) - B_2)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float* __restrict__ pk = p.jets[3 * C + 3 * c + k];
-        const int sa = k == 2 ? 10 : 4, sb = k == 0 ? 10 : 12;  // value slots of the order-2 rows of the pair's two axes
-        v[(13 + k) * 256] = ((p.pairs >> (3 * c + k)) & 1u) ? 0.5f * ((pk[2 * N + n] - v[sa * 256]) - v[sb * 256]) : 0.0f;
-      }
-    }
-    const float cx = (p.uses_coord & USE_X) ? x[n * p.dim] : 0.0f;
-    const float cy = (p.uses_coord & USE_Y) ? x[n * p.dim + 1] : 0.0f;
-    const float cz = (p.uses_coord & USE_Z) ? x[n * p.dim + 2] : 0.0f;
-    const float ct = (p.uses_coord & USE_T) ? t[n] : 0.0f;
-    // function k at fn + k N; the mask is the host's, so a row that no term names is not touched (its LDS row is never read).
-    // Not unrolled, like the field loop above: unrolled, the C = 3 and C = 4 forms with coefficient sums reserved scratch memory.
-#pragma unroll 1
-    for (int k = 0; k < kSfFns; ++k)
-      if ((p.uses_fn >> k) & 1) vcol[(C * kSfVals + k) * 256] = fn[(long long)k * N + n];
-
-    // ---- sweep 1: r_e = sum_{m: equation_of[m] = e} c_m prod_f phi_{m,f}, terms in ascending m ----
-    float r[PINN_SYSTEM_MAX_EQUATIONS];
-#pragma unroll
-    for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e) r[e] = 0.0f;
-    for (int m = 0; m < p.n_terms; ++m) {
-      const unsigned slots = p.slots[m];
-      const int nf = p.n_factors[m];
-      const int eq = p.eq[m];
-      float prod = coef[m];
-#pragma unroll
-      for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f)
-        if (f < nf) prod *= sxf_value(vcol, (slots >> (8 * f)) & 255u, cx, cy, cz, ct);
-#pragma unroll
-      for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e)
-        if (e == eq) r[e] += prod;
-    }
-
-    // ---- the loss and rbar_e of every equation ----
-    float rbar[PINN_SYSTEM_MAX_EQUATIONS];
-#pragma unroll
-    for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e) {
-      rbar[e] = 0.0f;
-      if (e < p.n_eq) {
-        float dl;
-        const float lv = sxf_loss(p.loss, p.huber_delta, r[e], &dl);
-        rbar[e] = rbar_in ? rbar_in[(long long)e * N + n] : p.gw[e] * dl;
-        if (residual_out) residual_out[(long long)e * N + n] = r[e];
-        if (REDUCE) loss_acc[e] += (double)lv;
-      }
-    }
-
-    // ---- sweep 2: terms in ascending m again.  The derivative summands of ONE term that go to the same (field, stream)
-    // accumulator (at most four) are summed first, in ascending factor order, multiplied by rbar of the term's equation and
-    // then added to the accumulator ----
-    if (want_cot) {
-#pragma unroll
-      for (int k = 0; k < C * kSfAcc; ++k) acol[k * 256] = 0.0f;
-      for (int m = 0; m < p.n_terms; ++m) {
-        const float c = coef[m];
-        const unsigned slots = p.slots[m];
-        const int nf = p.n_factors[m];
-        const int eq = p.eq[m];
-        float rb = rbar[0];
-#pragma unroll
-        for (int e = 1; e < PINN_SYSTEM_MAX_EQUATIONS; ++e)
-          if (e == eq) rb = rbar[e];
-        float phi[PINN_TERM_MAX_FACTORS];
-#pragma unroll
-        for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f)
-          phi[f] = f < nf ? sxf_value(vcol, (slots >> (8 * f)) & 255u, cx, cy, cz, ct) : 1.0f;
-        {
-          // contribution of factor f to its target: c * prod_{g != f} phi_g, times cos(u) / -sin(u) under sin(u) / cos(u)
-          float contrib[PINN_TERM_MAX_FACTORS];
-          int target[PINN_TERM_MAX_FACTORS];
-#pragma unroll
-          for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f) {
-            contrib[f] = 0.0f;
-            target[f] = -1;
-            const unsigned slot = (slots >> (8 * f)) & 255u;
-            if (f < nf && slot < (unsigned)(C * kSfVals)) {  // coordinates and known functions carry no cotangent
-              float others = c;
-#pragma unroll
-              for (int g = 0; g < PINN_TERM_MAX_FACTORS; ++g)
-                if (g != f && g < nf) others *= phi[g];
-              const int fc = (int)slot / kSfVals, fv = (int)slot - fc * kSfVals;
-              if (fv == 7) others = others * vcol[(fc * kSfVals + 8) * 256];
-              else if (fv == 8) others = -(others * vcol[(fc * kSfVals + 7) * 256]);
-              contrib[f] = others;
-              target[f] = sxf_target(slot);
-            }
-          }
-#pragma unroll
-          for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f) {
-            if (target[f] < 0) continue;
-            bool first = true;
-#pragma unroll
-            for (int g = 0; g < f; ++g)
-              if (target[g] == target[f]) first = false;
-            if (!first) continue;  // summed with the first factor of this target
-            float sum = 0.0f;
-#pragma unroll
-            for (int g = f; g < PINN_TERM_MAX_FACTORS; ++g)
-              if (target[g] == target[f]) sum += contrib[g];
-            acol[target[f] * 256] += rb * sum;
-          }
-        }
-      }
-    }
-
-    // ---- the coefficient sums: rbar_e(m) prod_f phi_{m,f}, the product from 1.0f in ascending f ----
-    if (COEF) {
-      // The loop is unrolled so that cg[] stays in registers.  The term index goes through an opaque scalar once per round:
-      // otherwise the descriptor loads of all 32 terms are hoisted out of the grid-stride loop and held in scalar registers
-      // across it, which, with the function rows, no longer fit (they spilled into scratch memory).
-      int mb = 0;
-      asm volatile("" : "+s"(mb));
-#pragma unroll
-      for (int m = 0; m < PINN_SYSTEM_MAX_TERMS; ++m) {
-        if (m < p.n_terms) {
-          const unsigned slots = p.slots[mb + m];
-          const int nf = p.n_factors[mb + m];
-          const int eq = p.eq[mb + m];
-          float rb = rbar[0];
-#pragma unroll
-          for (int e = 1; e < PINN_SYSTEM_MAX_EQUATIONS; ++e)
-            if (e == eq) rb = rbar[e];
-          float prod = 1.0f;
-#pragma unroll
-          for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f)
-            if (f < nf) prod *= sxf_value(vcol, (slots >> (8 * f)) & 255u, cx, cy, cz, ct);
-          cg[m] += (double)(rb * prod);
-        }
-      }
-    }
-
-    // ---- the cotangent blocks: every row of every block is written.  The transposed polarisation first, per field and in
-    // ascending pair index: p_k = g_k / 2 to row 2 of the P block, and subtracted from the order-2 accumulators of the pair's
-    // two axes (accumulators 4, 8, 10: u_xx, u_yy, u_zz) ----
-    if (want_cot) {
-#pragma unroll 1
-      for (int c = 0; c < C; ++c) {
-        float* a = acol + c * kSfAcc * 256;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          if ((p.pairs >> (3 * c + k)) & 1u) {
-            const int ta = k == 2 ? 8 : 4, tb = k == 0 ? 8 : 10;
-            const float pk = 0.5f * a[(11 + k) * 256];
-            a[ta * 256] -= pk;
-            a[tb * 256] -= pk;
-            float* __restrict__ cp = p.cot[3 * C + 3 * c + k];  // rows 0 and 1 of a P block are never read: zeros
-            cp[n] = 0.0f;
-            cp[N + n] = 0.0f;
-            cp[2 * N + n] = pk;
-          }
-        }
-        float* __restrict__ c0 = p.cot[3 * c];
-#pragma unroll
-        for (int s = 0; s < 7; ++s) {
-          const int row = sxf_row0(s, p.nt[c], p.nx0[c]);
-          if (row >= 0) c0[(long long)row * N + n] = a[s * 256];
-        }
-        if (p.nx1[c] >= 1) {  // row 0 of a further block is zero: the whole cotangent of the value went to block (c, 0)
-          float* __restrict__ c1 = p.cot[3 * c + 1];
-          c1[n] = 0.0f;
-          c1[N + n] = a[7 * 256];
-          if (p.nx1[c] >= 2) c1[2 * N + n] = a[8 * 256];
-        }
-        if (p.nx2[c] >= 1) {
-          float* __restrict__ c2 = p.cot[3 * c + 2];
-          c2[n] = 0.0f;
-          c2[N + n] = a[9 * 256];
-          if (p.nx2[c] >= 2) c2[2 * N + n] = a[10 * 256];
-        }
-      }
-    }
-  }
-
-  if (REDUCE) {
-    __shared__ double red[256];
-    const int rows = COEF ? kSfRow : PINN_SYSTEM_MAX_EQUATIONS;
-#pragma unroll
-    for (int k = 0; k < kSfRow; ++k) {
-      if (k < rows) {
-        red[threadIdx.x] = k < PINN_SYSTEM_MAX_EQUATIONS ? loss_acc[k < PINN_SYSTEM_MAX_EQUATIONS ? k : 0]
-                                                         : cg[COEF ? k - PINN_SYSTEM_MAX_EQUATIONS : 0];
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-          if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-          __syncthreads();
-        }
-        if (threadIdx.x == 0) partial[blockIdx.x * kSfRow + k] = red[0];
-        __syncthreads();
-      }
-    }
-  }
-}
-
-// thread k: sum k of the block partials in block order, in double.  k < 4: the loss sum of equation k, added to
-// eq_loss_sums[k]; thread 0 also adds sum_e w_e S_e (ascending e, in double) to loss_sum_out.  k >= 4: coefficient sum k - 4.
-__global__ void term_system_fn_finish_kernel(const double* partial, int blocks, int n_eq, int n_terms, double w0, double w1, double w2,
-                                          double w3, float* loss_sum_out, float* eq_loss_sums, float* coef_grads) {
-  const int k = threadIdx.x;
-  if (k == 0 && loss_sum_out) {
-    const double w[PINN_SYSTEM_MAX_EQUATIONS] = {w0, w1, w2, w3};
-    double total = 0.0;
-    for (int e = 0; e < n_eq; ++e) {
-      double s = 0.0;
-      for (int b = 0; b < blocks; ++b) s += partial[b * kSfRow + e];
-      total += w[e] * s;
-    }
-    loss_sum_out[0] = (float)((double)loss_sum_out[0] + total);
-  }
-  float* out = nullptr;
-  if (k < PINN_SYSTEM_MAX_EQUATIONS) {
-    if (k < n_eq && eq_loss_sums) out = eq_loss_sums + k;
-  } else if (k - PINN_SYSTEM_MAX_EQUATIONS < n_terms && coef_grads) {
-    out = coef_grads + (k - PINN_SYSTEM_MAX_EQUATIONS);
-  }
-  if (!out) return;
-  double s = 0.0;
-  for (int b = 0; b < blocks; ++b) s += partial[b * kSfRow + k];
-  out[0] = (float)((double)out[0] + s);
-}
-
-// the stream sets the library has axis-0 units for (csrc/Makefile: SETS)
-bool sxf_set_compiled(int nt, int nx) {
-  static const int sets[][2] = {{0, 0}, {1, 0}, {1, 1}, {1, 2}, {1, 3}, {1, 4}, {2, 0}, {2, 2}};
-  for (const auto& s : sets)
-    if (s[0] == nt && s[1] == nx) return true;
-  return false;
-}
-
-constexpr int kPairA[3] = {0, 0, 1}, kPairB[3] = {1, 2, 2};  // the axes of pair k
-
-template <int C>
-void sxf_launch(bool reduce, bool coef_sums, int blocks, hipStream_t st, const SysFnProg& p, const float* coef, const float* x,
-                const float* t, const float* fn, long long N, const float* rbar_in, float* residual_out, double* partial) {
-  if (!reduce)
-    hipLaunchKernelGGL((term_system_fn_kernel<C, false, false>), dim3(blocks), dim3(256), 0, st, p, coef, x, t, fn, N, rbar_in, residual_out, partial);
-  else if (coef_sums)
-    hipLaunchKernelGGL((term_system_fn_kernel<C, true, true>), dim3(blocks), dim3(256), 0, st, p, coef, x, t, fn, N, rbar_in, residual_out, partial);
-  else
-    hipLaunchKernelGGL((term_system_fn_kernel<C, true, false>), dim3(blocks), dim3(256), 0, st, p, coef, x, t, fn, N, rbar_in, residual_out, partial);
-}
-
-}  // namespace
-
-extern "C" int pinn_internal_fail(int code, const char* msg);  // pinn_abi.hip: sets pinn_last_error()
-
-static int sxf_launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return PINN_OK;
-  char msg[256];
-  snprintf(msg, sizeof(msg), "HIP error %d: %s (%s)", (int)e, hipGetErrorString(e), what);
-  return pinn_internal_fail(PINN_ERR_HIP, msg);
-}
+// known functions"): level FN of term_system_kernel.h.  A known function g_k is one more value row, four rows are 4 KB of LDS;
+// held in registers behind a wave-uniform switch instead, the function values pushed the forms with coefficient sums, whose
+// term loop is unrolled over 32 terms of scalar operands, from scalar spills into scratch memory.
+#include "term_system_host.h"
 
 extern "C" int pinn_term_residual_system_fn(const PinnTermPdeSystemFn* pde, const float* coef_values, const float* const* jets,
-                                         const float* x, const float* t, const float* fn_values, int64_t N, float grad_scale,
-                                         const float* residual_cotangent, float* residual_out, float* loss_sum_out,
-                                         float* eq_loss_sums, float* const* jet_cotangents, float* coef_grads, double* scratch,
-                                         void* stream) {
-  char msg[256];
-#define SXF_BAD(...)                                  \
-  do {                                                \
-    snprintf(msg, sizeof(msg), __VA_ARGS__);          \
-    return pinn_internal_fail(PINN_ERR_BAD_DESC, msg); \
-  } while (0)
-  if (!pde) SXF_BAD("pinn_term_residual_system_fn: null descriptor");
-  const int dim = pde->dimension, C = pde->n_fields, E = pde->n_equations;
-  if (dim < 1 || dim > 3) SXF_BAD("pinn_term_residual_system_fn: dimension %d outside [1, 3]", dim);
-  if (C < 1 || C > PINN_SYSTEM_MAX_FIELDS) SXF_BAD("pinn_term_residual_system_fn: n_fields %d outside [1, %d]", C, PINN_SYSTEM_MAX_FIELDS);
-  if (E < 1 || E > PINN_SYSTEM_MAX_EQUATIONS)
-    SXF_BAD("pinn_term_residual_system_fn: n_equations %d outside [1, %d]", E, PINN_SYSTEM_MAX_EQUATIONS);
-  if (pde->n_terms < 0 || pde->n_terms > PINN_SYSTEM_MAX_TERMS)
-    SXF_BAD("pinn_term_residual_system_fn: n_terms %d outside [0, %d]", (int)pde->n_terms, PINN_SYSTEM_MAX_TERMS);
-  const int K = pde->n_functions;
-  if (K < 0 || K > PINN_SYSTEM_MAX_FUNCTIONS)
-    SXF_BAD("pinn_term_residual_system_fn: n_functions %d outside [0, %d]", K, PINN_SYSTEM_MAX_FUNCTIONS);
-  SysFnProg p;
-  memset(&p, 0, sizeof(p));
-  p.n_terms = pde->n_terms;
-  p.n_eq = E;
-  p.dim = dim;
-  p.loss = pde->loss;
-  p.huber_delta = pde->huber_delta;
-  for (int c = 0; c < C; ++c) {
-    const int nt = pde->time_order[c], nx0 = pde->space_order[c][0];
-    if (!sxf_set_compiled(nt, nx0))
-      SXF_BAD("pinn_term_residual_system_fn: field %d: axis-0 stream set (nt=%d, nx=%d) is not compiled", c, nt, nx0);
-    for (int a = 1; a < 3; ++a) {
-      const int so = pde->space_order[c][a];
-      if (so < 0 || so > (a < dim ? 2 : 0))
-        SXF_BAD("pinn_term_residual_system_fn: field %d: space_order[%d] = %d outside [0, %d] (dimension %d)", c, a, so, a < dim ? 2 : 0, dim);
-    }
-    p.nt[c] = nt;
-    p.nx0[c] = nx0;
-    p.nx1[c] = pde->space_order[c][1];
-    p.nx2[c] = pde->space_order[c][2];
-    for (int k = 0; k < 3; ++k) {
-      const int po = pde->pair_order[c][k];
-      if (po != 0 && po != 2)
-        SXF_BAD("pinn_term_residual_system_fn: field %d: pair_order[%d] = %d on the pair of axes (%d, %d) (0 or 2)", c, k, po, kPairA[k], kPairB[k]);
-      if (po != 0 && dim < 2)
-        SXF_BAD("pinn_term_residual_system_fn: field %d: pair_order[%d] = %d on the pair of axes (%d, %d) in dimension %d (a mixed derivative needs 2 or 3)",
-                c, k, po, kPairA[k], kPairB[k], dim);
-      if (po != 0 && kPairB[k] >= dim)
-        SXF_BAD("pinn_term_residual_system_fn: field %d: pair_order[%d] = %d on the pair of axes (%d, %d), dimension %d", c, k, po, kPairA[k],
-                kPairB[k], dim);
-      if (po) p.pairs |= 1u << (3 * c + k);
-    }
-  }
-  for (int e = 0; e < E; ++e) {
-    const float w = pde->eq_weight[e];
-    if (!std::isfinite(w) || w < 0.0f) SXF_BAD("pinn_term_residual_system_fn: eq_weight[%d] = %g is negative or not finite", e, (double)w);
-    p.gw[e] = grad_scale * w;
-    p.w[e] = (double)w;
-  }
-  for (int m = 0; m < PINN_SYSTEM_MAX_TERMS; ++m) p.slots[m] = 0xffffffffu;
-  for (int m = 0; m < pde->n_terms; ++m) {
-    const PinnTermPdeTerm& tm = pde->terms[m];
-    const int eq = pde->equation_of[m];
-    if (eq < 0 || eq >= E) SXF_BAD("pinn_term_residual_system_fn: equation_of[%d] = %d outside [0, %d)", m, eq, E);
-    if (tm.n_factors < 0 || tm.n_factors > PINN_TERM_MAX_FACTORS)
-      SXF_BAD("pinn_term_residual_system_fn: term %d has n_factors %d outside [0, %d]", m, (int)tm.n_factors, PINN_TERM_MAX_FACTORS);
-    unsigned packed = 0xffffffffu;
-    for (int f = 0; f < tm.n_factors; ++f) {
-      const int byte = tm.factor[f];
-      if (byte < 0 || byte > 255) SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d: %d is not one byte (field * 32 + code)", m, f, byte);
-      const int code = byte & 31, field = byte >> 5;
-      int slot;
-      if (code == PINN_TERM_X || code == PINN_TERM_Y || code == PINN_TERM_Z || code == PINN_TERM_T) {  // the field bits are ignored
-        if ((code == PINN_TERM_Y && dim < 2) || (code == PINN_TERM_Z && dim < 3))
-          SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d names a coordinate (code %d) that dimension %d does not hold", m, f, code, dim);
-        p.uses_coord |= code == PINN_TERM_X ? USE_X : (code == PINN_TERM_Y ? USE_Y : (code == PINN_TERM_Z ? USE_Z : USE_T));
-        slot = kSfCoord + (code == PINN_TERM_X ? 0 : (code == PINN_TERM_Y ? 1 : (code == PINN_TERM_Z ? 2 : 3)));
-      } else if (code >= PINN_TERM_FN0 && code <= PINN_TERM_FN3) {  // the field bits are ignored here too
-        const int k = code - PINN_TERM_FN0;
-        if (k >= K)
-          SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d names function %d (code %d) of %d (n_functions)", m, f, k, code, K);
-        p.uses_fn |= 1 << k;
-        slot = C * kSfVals + k;
-      } else {
-        const int vs = sxf_value_slot(code);
-        if (code >= PINN_TERM_UYYY && code <= PINN_TERM_UZZZZ)
-          SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d: code %d (u_yyy, u_yyyy, u_zzz, u_zzzz): orders above 2 along y and z are "
-                  "not available in systems", m, f, code);
-        if (code >= PINN_TERM_UXXYY && code <= PINN_TERM_UYYZZ)
-          SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d: code %d (u_xxyy, u_xxzz, u_yyzz): u_aabb is not available in systems", m, f, code);
-        if (vs < 0) SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d: unknown factor code %d", m, f, code);
-        if (field >= C) SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d names field %d of %d", m, f, field, C);
-        bool held = true;
-        if (code < 7) held = sxf_row0(code, p.nt[field], p.nx0[field]) >= 0;
-        else if (code == PINN_TERM_UY || code == PINN_TERM_UYY) held = p.nx1[field] >= code - PINN_TERM_UY + 1;
-        else if (code == PINN_TERM_UZ || code == PINN_TERM_UZZ) held = p.nx2[field] >= code - PINN_TERM_UZ + 1;
-        if (vs >= 13) {
-          const int k = vs - 13;
-          const int order[3] = {p.nx0[field], p.nx1[field], p.nx2[field]};
-          const int po = (p.pairs >> (3 * field + k)) & 1u ? 2 : 0;
-          if (po != 2 || order[kPairA[k]] < 2 || order[kPairB[k]] < 2)
-            SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d names the mixed derivative (code %d) of field %d along the pair of axes "
-                    "(%d, %d), which needs pair_order[%d][%d] = 2 and order >= 2 on both axes (pair_order %d, orders %d, %d)", m, f, code, field,
-                    kPairA[k], kPairB[k], field, k, po, order[kPairA[k]], order[kPairB[k]]);
-        }
-        if (!held)
-          SXF_BAD("pinn_term_residual_system_fn: term %d, factor %d names a stream (code %d) that field %d (nt=%d, space orders %d, %d, %d) does not hold",
-                  m, f, code, field, p.nt[field], p.nx0[field], p.nx1[field], p.nx2[field]);
-        if (vs == 7 || vs == 8) p.uses_trig[field] = 1;
-        slot = field * kSfVals + vs;
-      }
-      packed = (packed & ~(255u << (8 * f))) | ((unsigned)slot << (8 * f));
-    }
-    p.slots[m] = packed;
-    p.n_factors[m] = (unsigned char)tm.n_factors;
-    p.eq[m] = (unsigned char)eq;
-  }
-  if (N < 0) SXF_BAD("pinn_term_residual_system_fn: N < 0");
-  if (N == 0) return PINN_OK;
-  if (!jets || !coef_values) SXF_BAD("pinn_term_residual_system_fn: null jets table or coef_values");
-  for (int c = 0; c < C; ++c) {
-    const int so[3] = {1, p.nx1[c], p.nx2[c]};  // block (c, 0) always holds the value stream
-    for (int a = 0; a < 3; ++a) {
-      const bool need = a < dim && so[a] > 0;
-      p.jets[3 * c + a] = need ? jets[3 * c + a] : nullptr;
-      p.cot[3 * c + a] = (jet_cotangents && need) ? jet_cotangents[3 * c + a] : nullptr;
-      if (need && (!p.jets[3 * c + a] || (jet_cotangents && !p.cot[3 * c + a])))
-        SXF_BAD("pinn_term_residual_system_fn: null block (field %d, axis %d) of the jets or jet_cotangents table", c, a);
-    }
-    for (int k = 0; k < 3; ++k) {
-      const int b = 3 * C + 3 * c + k;
-      const bool need = (p.pairs >> (3 * c + k)) & 1u;
-      p.jets[b] = need ? jets[b] : nullptr;
-      p.cot[b] = (jet_cotangents && need) ? jet_cotangents[b] : nullptr;
-      if (need && (!p.jets[b] || (jet_cotangents && !p.cot[b])))
-        SXF_BAD("pinn_term_residual_system_fn: null block %d of the jets or jet_cotangents table (the P block of field %d, pair of axes (%d, %d))",
-                b, c, kPairA[k], kPairB[k]);
-    }
-  }
-  if (((p.uses_coord & (USE_X | USE_Y | USE_Z)) && !x) || ((p.uses_coord & USE_T) && !t))
-    SXF_BAD("pinn_term_residual_system_fn: a term names X / Y / Z / T but the coordinate array is null");
-  if (p.uses_fn && !fn_values) {
-    int m = 0, k = 0;  // the first term that names a function, for the message
-    for (; m < pde->n_terms; ++m) {
-      bool found = false;
-      for (int f = 0; f < p.n_factors[m] && !found; ++f) {
-        const unsigned slot = (p.slots[m] >> (8 * f)) & 255u;
-        if (slot >= (unsigned)(C * kSfVals) && slot < (unsigned)(C * kSfVals + kSfFns)) found = true, k = (int)slot - C * kSfVals;
-      }
-      if (found) break;
-    }
-    SXF_BAD("pinn_term_residual_system_fn: term %d names function %d but fn_values is null", m, k);
-  }
-  const bool reduce = loss_sum_out || eq_loss_sums || coef_grads;
-  if (reduce && !scratch) SXF_BAD("pinn_term_residual_system_fn: null scratch with a loss or coefficient sum");
-#undef SXF_BAD
-  if (reinterpret_cast<uintptr_t>(scratch) & 7u)
-    return pinn_internal_fail(PINN_ERR_MISALIGNED, "pinn_term_residual_system_fn: scratch must be 8-byte aligned");
-
-  long long nb = ((long long)N + 255) / 256;
-  const int blocks = (int)(nb > kSfBlocks ? kSfBlocks : nb);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool cs = coef_grads != nullptr;
-  switch (C) {
-    case 1: sxf_launch<1>(reduce, cs, blocks, st, p, coef_values, x, t, fn_values, (long long)N, residual_cotangent, residual_out, scratch); break;
-    case 2: sxf_launch<2>(reduce, cs, blocks, st, p, coef_values, x, t, fn_values, (long long)N, residual_cotangent, residual_out, scratch); break;
-    case 3: sxf_launch<3>(reduce, cs, blocks, st, p, coef_values, x, t, fn_values, (long long)N, residual_cotangent, residual_out, scratch); break;
-    default: sxf_launch<4>(reduce, cs, blocks, st, p, coef_values, x, t, fn_values, (long long)N, residual_cotangent, residual_out, scratch); break;
-  }
-  int rc = sxf_launched("term_system_fn_kernel");
-  if (rc || !reduce) return rc;
-  hipLaunchKernelGGL(term_system_fn_finish_kernel, dim3(1), dim3(64), 0, st, scratch, blocks, E, (int)p.n_terms, p.w[0], p.w[1], p.w[2], p.w[3],
-                     loss_sum_out, eq_loss_sums, coef_grads);
-  return sxf_launched("term_system_fn_finish_kernel");
+                                            const float* x, const float* t, const float* fn_values, int64_t N, float grad_scale,
+                                            const float* residual_cotangent, float* residual_out, float* loss_sum_out,
+                                            float* eq_loss_sums, float* const* jet_cotangents, float* coef_grads, double* scratch,
+                                            void* stream) {
+  const SysCall a = {coef_values, jets, x, t, fn_values, nullptr, nullptr, (long long)N, grad_scale, residual_cotangent, residual_out,
+                     loss_sum_out, eq_loss_sums, jet_cotangents, coef_grads, nullptr, scratch, static_cast<hipStream_t>(stream)};
+  return sys_residual<FN>("pinn_term_residual_system_fn", pde, a);
 }

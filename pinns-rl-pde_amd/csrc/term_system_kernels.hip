@@ -1,482 +1,13 @@
-// Coupled PDE systems given as data (include/pinn_jet.h, "term residuals of coupled systems"): the element-wise middle of
-//   one pinn_jet_forward per (field, axis with streams) -> pinn_term_residual_system -> one pinn_jet_backward per block,
-// where field c of a C-output network is a component launch (the width-1 descriptor with the output-layer entries of both
-// tables at row c).  The scheme is term_axes_kernels.hip's: one thread per point per grid-stride round, the term list in the
-// kernel arguments, the coefficients read from the device at launch time, per-block partials in double summed in block order.
-// What differs is where a point's numbers live: up to 4 x 13 values and 4 x 11 derivative accumulators do not fit the
-// switch-per-register form of the siblings, so they sit in LDS, one column per thread, and a factor's slot is a wave-uniform
-// row offset into it.  No thread reads another's column: there is no barrier in the point loop.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-
-#include "../../include/pinn_jet.h"
-
-namespace {
-
-constexpr int kSyBlocks = 64;                                             // fixed grid: the partials are summed in block order
-constexpr int kSyRow = PINN_SYSTEM_MAX_EQUATIONS + PINN_SYSTEM_MAX_TERMS;  // doubles per block: {equation loss sums, coefficient sums}
-constexpr int kSyVals = 13;  // value slots of a field: codes 0 .. 6, sin, cos, u_y, u_yy, u_z, u_zz
-constexpr int kSyAcc = 11;   // derivative accumulators of a field: codes 0 .. 6, u_y, u_yy, u_z, u_zz
-constexpr int kSyCoord = PINN_SYSTEM_MAX_FIELDS * kSyVals;  // slots 52 .. 55: x, y, z, t (registers, not LDS)
-
-static_assert(PINN_SYSTEM_SCRATCH_DOUBLES == kSyBlocks * kSyRow, "scratch constant and grid disagree");
-static_assert(PINN_SYSTEM_MAX_FIELDS == 4 && PINN_SYSTEM_MAX_EQUATIONS == 4, "the kernel unrolls over four fields and four equations");
-
-enum { USE_X = 1, USE_Y = 2, USE_Z = 4, USE_T = 8 };
-
-// the descriptor as the kernel reads it: one byte per factor = its slot (field * 13 + value slot, 52 .. 55 a coordinate,
-// 255 unused)
-struct SysProg {
-  int n_terms, n_eq, dim, loss;
-  float huber_delta;
-  int uses_coord;
-  int nt[PINN_SYSTEM_MAX_FIELDS], nx0[PINN_SYSTEM_MAX_FIELDS], nx1[PINN_SYSTEM_MAX_FIELDS], nx2[PINN_SYSTEM_MAX_FIELDS];
-  int uses_trig[PINN_SYSTEM_MAX_FIELDS];
-  float gw[PINN_SYSTEM_MAX_EQUATIONS];        // grad_scale * eq_weight[e], rounded once on the host
-  double w[PINN_SYSTEM_MAX_EQUATIONS];        // eq_weight[e]
-  unsigned slots[PINN_SYSTEM_MAX_TERMS];      // byte f = slot of factor f
-  unsigned char n_factors[PINN_SYSTEM_MAX_TERMS];
-  unsigned char eq[PINN_SYSTEM_MAX_TERMS];
-  const float* jets[3 * PINN_SYSTEM_MAX_FIELDS];
-  float* cot[3 * PINN_SYSTEM_MAX_FIELDS];     // all null when no cotangents are wanted
-};
-
-// l(r) and l'(r) of PDEBase._apply_loss_fn per sample (term_kernels.hip::term_loss)
-__device__ __forceinline__ float sys_loss(int kind, float d, float r, float* dl) {
-  if (kind == PINN_LOSS_MAE) {
-    *dl = r > 0.0f ? 1.0f : (r < 0.0f ? -1.0f : 0.0f);
-    return fabsf(r);
-  }
-  if (kind == PINN_LOSS_HUBER) {
-    const float a = fabsf(r);
-    if (a < d) {
-      *dl = r;
-      return 0.5f * r * r;
-    }
-    *dl = r > 0.0f ? d : -d;
-    return d * (a - 0.5f * d);
-  }
-  *dl = 2.0f * r;
-  return r * r;
-}
-
-// row of block (c, 0) that holds code s (0 .. 6) in the (nt, nx) set, or -1 when the set does not hold it
-__host__ __device__ inline int sys_row0(int code, int nt, int nx) {
-  if (code == 0) return 0;
-  if (code <= 2) return code <= nt ? code : -1;
-  return code - 2 <= nx ? nt + code - 2 : -1;
-}
-
-// value slot (0 .. 12) of a stream / trig code, or -1 for a coordinate or an unknown code
-__host__ inline int sys_value_slot(int code) {
-  if (code >= 0 && code <= 6) return code;
-  if (code == PINN_TERM_SIN_U) return 7;
-  if (code == PINN_TERM_COS_U) return 8;
-  if (code >= PINN_TERM_UY && code <= PINN_TERM_UZZ) return 9 + (code - PINN_TERM_UY);
-  return -1;
-}
-
-// accumulator (field * 11 + k) the derivative of a value slot goes to: u, sin(u) and cos(u) all go to the value stream
-__device__ __forceinline__ int sys_target(unsigned slot) {
-  const int c = (int)slot / kSyVals, v = (int)slot - c * kSyVals;
-  return c * kSyAcc + (v < 7 ? v : (v < 9 ? 0 : v - 2));
-}
-
-// the value of a slot: a wave-uniform row of this thread's LDS column, or a coordinate register
-__device__ __forceinline__ float sys_value(const float* col, unsigned slot, float cx, float cy, float cz, float ct) {
-  if (slot < (unsigned)kSyCoord) return col[slot * 256];
-  switch (slot - kSyCoord) {
-    case 0: return cx;
-    case 1: return cy;
-    case 2: return cz;
-    default: return ct;
-  }
-}
-
-// C: the number of fields (sizes the LDS block);  REDUCE: loss and / or coefficient sums are wanted (per-block partials);
-// COEF: coefficient sums are wanted.  partial[b * kSyRow + e] = sum l(r_e,n), partial[b * kSyRow + 4 + m] = sum rbar_e(m),n
-// prod_f phi_{m,f} over block b's points.
-template <int C, bool REDUCE, bool COEF>
-__global__ __launch_bounds__(256) void term_system_kernel(SysProg p, const float* __restrict__ coef, const float* __restrict__ x,
-                                                          const float* __restrict__ t, long long N, const float* __restrict__ rbar_in,
-                                                          float* __restrict__ residual_out, double* __restrict__ partial) {
-  __shared__ float sval[C * kSyVals * 256];
-  __shared__ float sacc[C * kSyAcc * 256];
-  float* vcol = sval + threadIdx.x;
-  float* acol = sacc + threadIdx.x;
-  double loss_acc[PINN_SYSTEM_MAX_EQUATIONS];
-#pragma unroll
-  for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e) loss_acc[e] = 0.0;
-  double cg[COEF ? PINN_SYSTEM_MAX_TERMS : 1];
-#pragma unroll
-  for (int m = 0; m < (COEF ? PINN_SYSTEM_MAX_TERMS : 1); ++m) cg[m] = 0.0;
-  const bool want_cot = p.cot[0] != nullptr;
-
-  for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < N; n += (long long)gridDim.x * 256) {
-    // ---- the values of every field ----
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float* __restrict__ j0 = p.jets[3 * c];
-      float* v = vcol + c * kSyVals * 256;
-#pragma unroll
-      for (int s = 0; s < 7; ++s) {
-        const int row = sys_row0(s, p.nt[c], p.nx0[c]);
-        v[s * 256] = row >= 0 ? j0[(long long)row * N + n] : 0.0f;
-      }
-      if (p.uses_trig[c]) {
-        const float u = v[0];
-        v[7 * 256] = sinf(u);
-        v[8 * 256] = cosf(u);
-      }
-      const float* __restrict__ j1 = p.jets[3 * c + 1];
-      const float* __restrict__ j2 = p.jets[3 * c + 2];
-      v[9 * 256] = p.nx1[c] >= 1 ? j1[N + n] : 0.0f;
-      v[10 * 256] = p.nx1[c] >= 2 ? j1[2 * N + n] : 0.0f;
-      v[11 * 256] = p.nx2[c] >= 1 ? j2[N + n] : 0.0f;
-      v[12 * 256] = p.nx2[c] >= 2 ? j2[2 * N + n] : 0.0f;
-    }
-    const float cx = (p.uses_coord & USE_X) ? x[n * p.dim] : 0.0f;
-    const float cy = (p.uses_coord & USE_Y) ? x[n * p.dim + 1] : 0.0f;
-    const float cz = (p.uses_coord & USE_Z) ? x[n * p.dim + 2] : 0.0f;
-    const float ct = (p.uses_coord & USE_T) ? t[n] : 0.0f;
-
-    // ---- sweep 1: r_e = sum_{m: equation_of[m] = e} c_m prod_f phi_{m,f}, terms in ascending m ----
-    float r[PINN_SYSTEM_MAX_EQUATIONS];
-#pragma unroll
-    for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e) r[e] = 0.0f;
-    for (int m = 0; m < p.n_terms; ++m) {
-      const unsigned slots = p.slots[m];
-      const int nf = p.n_factors[m];
-      const int eq = p.eq[m];
-      float prod = coef[m];
-#pragma unroll
-      for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f)
-        if (f < nf) prod *= sys_value(vcol, (slots >> (8 * f)) & 255u, cx, cy, cz, ct);
-#pragma unroll
-      for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e)
-        if (e == eq) r[e] += prod;
-    }
-
-    // ---- the loss and rbar_e of every equation ----
-    float rbar[PINN_SYSTEM_MAX_EQUATIONS];
-#pragma unroll
-    for (int e = 0; e < PINN_SYSTEM_MAX_EQUATIONS; ++e) {
-      rbar[e] = 0.0f;
-      if (e < p.n_eq) {
-        float dl;
-        const float lv = sys_loss(p.loss, p.huber_delta, r[e], &dl);
-        rbar[e] = rbar_in ? rbar_in[(long long)e * N + n] : p.gw[e] * dl;
-        if (residual_out) residual_out[(long long)e * N + n] = r[e];
-        if (REDUCE) loss_acc[e] += (double)lv;
-      }
-    }
-
-    // ---- sweep 2: terms in ascending m again.  The derivative summands of ONE term that go to the same (field, stream)
-    // accumulator (at most four) are summed first, in ascending factor order, multiplied by rbar of the term's equation and
-    // then added to the accumulator ----
-    if (want_cot) {
-#pragma unroll
-      for (int k = 0; k < C * kSyAcc; ++k) acol[k * 256] = 0.0f;
-      for (int m = 0; m < p.n_terms; ++m) {
-        const float c = coef[m];
-        const unsigned slots = p.slots[m];
-        const int nf = p.n_factors[m];
-        const int eq = p.eq[m];
-        float rb = rbar[0];
-#pragma unroll
-        for (int e = 1; e < PINN_SYSTEM_MAX_EQUATIONS; ++e)
-          if (e == eq) rb = rbar[e];
-        float phi[PINN_TERM_MAX_FACTORS];
-#pragma unroll
-        for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f)
-          phi[f] = f < nf ? sys_value(vcol, (slots >> (8 * f)) & 255u, cx, cy, cz, ct) : 1.0f;
-        {
-          // contribution of factor f to its target: c * prod_{g != f} phi_g, times cos(u) / -sin(u) under sin(u) / cos(u)
-          float contrib[PINN_TERM_MAX_FACTORS];
-          int target[PINN_TERM_MAX_FACTORS];
-#pragma unroll
-          for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f) {
-            contrib[f] = 0.0f;
-            target[f] = -1;
-            const unsigned slot = (slots >> (8 * f)) & 255u;
-            if (f < nf && slot < (unsigned)kSyCoord) {  // coordinates carry no cotangent
-              float others = c;
-#pragma unroll
-              for (int g = 0; g < PINN_TERM_MAX_FACTORS; ++g)
-                if (g != f && g < nf) others *= phi[g];
-              const int fc = (int)slot / kSyVals, fv = (int)slot - fc * kSyVals;
-              if (fv == 7) others = others * vcol[(fc * kSyVals + 8) * 256];
-              else if (fv == 8) others = -(others * vcol[(fc * kSyVals + 7) * 256]);
-              contrib[f] = others;
-              target[f] = sys_target(slot);
-            }
-          }
-#pragma unroll
-          for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f) {
-            if (target[f] < 0) continue;
-            bool first = true;
-#pragma unroll
-            for (int g = 0; g < f; ++g)
-              if (target[g] == target[f]) first = false;
-            if (!first) continue;  // summed with the first factor of this target
-            float sum = 0.0f;
-#pragma unroll
-            for (int g = f; g < PINN_TERM_MAX_FACTORS; ++g)
-              if (target[g] == target[f]) sum += contrib[g];
-            acol[target[f] * 256] += rb * sum;
-          }
-        }
-      }
-    }
-
-    // ---- the coefficient sums: rbar_e(m) prod_f phi_{m,f}, the product from 1.0f in ascending f ----
-    if (COEF) {
-#pragma unroll
-      for (int m = 0; m < PINN_SYSTEM_MAX_TERMS; ++m) {
-        if (m < p.n_terms) {
-          const unsigned slots = p.slots[m];
-          const int nf = p.n_factors[m];
-          const int eq = p.eq[m];
-          float rb = rbar[0];
-#pragma unroll
-          for (int e = 1; e < PINN_SYSTEM_MAX_EQUATIONS; ++e)
-            if (e == eq) rb = rbar[e];
-          float prod = 1.0f;
-#pragma unroll
-          for (int f = 0; f < PINN_TERM_MAX_FACTORS; ++f)
-            if (f < nf) prod *= sys_value(vcol, (slots >> (8 * f)) & 255u, cx, cy, cz, ct);
-          cg[m] += (double)(rb * prod);
-        }
-      }
-    }
-
-    // ---- the cotangent blocks: every row of every block is written ----
-    if (want_cot) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float* a = acol + c * kSyAcc * 256;
-        float* __restrict__ c0 = p.cot[3 * c];
-#pragma unroll
-        for (int s = 0; s < 7; ++s) {
-          const int row = sys_row0(s, p.nt[c], p.nx0[c]);
-          if (row >= 0) c0[(long long)row * N + n] = a[s * 256];
-        }
-        if (p.nx1[c] >= 1) {  // row 0 of a further block is zero: the whole cotangent of the value went to block (c, 0)
-          float* __restrict__ c1 = p.cot[3 * c + 1];
-          c1[n] = 0.0f;
-          c1[N + n] = a[7 * 256];
-          if (p.nx1[c] >= 2) c1[2 * N + n] = a[8 * 256];
-        }
-        if (p.nx2[c] >= 1) {
-          float* __restrict__ c2 = p.cot[3 * c + 2];
-          c2[n] = 0.0f;
-          c2[N + n] = a[9 * 256];
-          if (p.nx2[c] >= 2) c2[2 * N + n] = a[10 * 256];
-        }
-      }
-    }
-  }
-
-  if (REDUCE) {
-    __shared__ double red[256];
-    const int rows = COEF ? kSyRow : PINN_SYSTEM_MAX_EQUATIONS;
-#pragma unroll
-    for (int k = 0; k < kSyRow; ++k) {
-      if (k < rows) {
-        red[threadIdx.x] = k < PINN_SYSTEM_MAX_EQUATIONS ? loss_acc[k < PINN_SYSTEM_MAX_EQUATIONS ? k : 0]
-                                                         : cg[COEF ? k - PINN_SYSTEM_MAX_EQUATIONS : 0];
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-          if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-          __syncthreads();
-        }
-        if (threadIdx.x == 0) partial[blockIdx.x * kSyRow + k] = red[0];
-        __syncthreads();
-      }
-    }
-  }
-}
-
-// thread k: sum k of the block partials in block order, in double.  k < 4: the loss sum of equation k, added to
-// eq_loss_sums[k]; thread 0 also adds sum_e w_e S_e (ascending e, in double) to loss_sum_out.  k >= 4: coefficient sum k - 4.
-__global__ void term_system_finish_kernel(const double* partial, int blocks, int n_eq, int n_terms, double w0, double w1, double w2,
-                                          double w3, float* loss_sum_out, float* eq_loss_sums, float* coef_grads) {
-  const int k = threadIdx.x;
-  if (k == 0 && loss_sum_out) {
-    const double w[PINN_SYSTEM_MAX_EQUATIONS] = {w0, w1, w2, w3};
-    double total = 0.0;
-    for (int e = 0; e < n_eq; ++e) {
-      double s = 0.0;
-      for (int b = 0; b < blocks; ++b) s += partial[b * kSyRow + e];
-      total += w[e] * s;
-    }
-    loss_sum_out[0] = (float)((double)loss_sum_out[0] + total);
-  }
-  float* out = nullptr;
-  if (k < PINN_SYSTEM_MAX_EQUATIONS) {
-    if (k < n_eq && eq_loss_sums) out = eq_loss_sums + k;
-  } else if (k - PINN_SYSTEM_MAX_EQUATIONS < n_terms && coef_grads) {
-    out = coef_grads + (k - PINN_SYSTEM_MAX_EQUATIONS);
-  }
-  if (!out) return;
-  double s = 0.0;
-  for (int b = 0; b < blocks; ++b) s += partial[b * kSyRow + k];
-  out[0] = (float)((double)out[0] + s);
-}
-
-// the stream sets the library has axis-0 units for (csrc/Makefile: SETS)
-bool sys_set_compiled(int nt, int nx) {
-  static const int sets[][2] = {{0, 0}, {1, 0}, {1, 1}, {1, 2}, {1, 3}, {1, 4}, {2, 0}, {2, 2}};
-  for (const auto& s : sets)
-    if (s[0] == nt && s[1] == nx) return true;
-  return false;
-}
-
-template <int C>
-void sys_launch(bool reduce, bool coef_sums, int blocks, hipStream_t st, const SysProg& p, const float* coef, const float* x,
-                const float* t, long long N, const float* rbar_in, float* residual_out, double* partial) {
-  if (!reduce)
-    hipLaunchKernelGGL((term_system_kernel<C, false, false>), dim3(blocks), dim3(256), 0, st, p, coef, x, t, N, rbar_in, residual_out, partial);
-  else if (coef_sums)
-    hipLaunchKernelGGL((term_system_kernel<C, true, true>), dim3(blocks), dim3(256), 0, st, p, coef, x, t, N, rbar_in, residual_out, partial);
-  else
-    hipLaunchKernelGGL((term_system_kernel<C, true, false>), dim3(blocks), dim3(256), 0, st, p, coef, x, t, N, rbar_in, residual_out, partial);
-}
-
-}  // namespace
-
-extern "C" int pinn_internal_fail(int code, const char* msg);  // pinn_abi.hip: sets pinn_last_error()
-
-static int sys_launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return PINN_OK;
-  char msg[256];
-  snprintf(msg, sizeof(msg), "HIP error %d: %s (%s)", (int)e, hipGetErrorString(e), what);
-  return pinn_internal_fail(PINN_ERR_HIP, msg);
-}
+// Coupled PDE systems given as data (include/pinn_jet.h, "term residuals of coupled systems"): level PLAIN of
+// term_system_kernel.h, up to 4 x 13 values and 4 x 11 derivative accumulators per point.
+#include "term_system_host.h"
 
 extern "C" int pinn_term_residual_system(const PinnTermPdeSystem* pde, const float* coef_values, const float* const* jets,
                                          const float* x, const float* t, int64_t N, float grad_scale,
                                          const float* residual_cotangent, float* residual_out, float* loss_sum_out,
                                          float* eq_loss_sums, float* const* jet_cotangents, float* coef_grads, double* scratch,
                                          void* stream) {
-  char msg[256];
-#define SYS_BAD(...)                                  \
-  do {                                                \
-    snprintf(msg, sizeof(msg), __VA_ARGS__);          \
-    return pinn_internal_fail(PINN_ERR_BAD_DESC, msg); \
-  } while (0)
-  if (!pde) SYS_BAD("pinn_term_residual_system: null descriptor");
-  const int dim = pde->dimension, C = pde->n_fields, E = pde->n_equations;
-  if (dim < 1 || dim > 3) SYS_BAD("pinn_term_residual_system: dimension %d outside [1, 3]", dim);
-  if (C < 1 || C > PINN_SYSTEM_MAX_FIELDS) SYS_BAD("pinn_term_residual_system: n_fields %d outside [1, %d]", C, PINN_SYSTEM_MAX_FIELDS);
-  if (E < 1 || E > PINN_SYSTEM_MAX_EQUATIONS)
-    SYS_BAD("pinn_term_residual_system: n_equations %d outside [1, %d]", E, PINN_SYSTEM_MAX_EQUATIONS);
-  if (pde->n_terms < 0 || pde->n_terms > PINN_SYSTEM_MAX_TERMS)
-    SYS_BAD("pinn_term_residual_system: n_terms %d outside [0, %d]", (int)pde->n_terms, PINN_SYSTEM_MAX_TERMS);
-  SysProg p;
-  memset(&p, 0, sizeof(p));
-  p.n_terms = pde->n_terms;
-  p.n_eq = E;
-  p.dim = dim;
-  p.loss = pde->loss;
-  p.huber_delta = pde->huber_delta;
-  for (int c = 0; c < C; ++c) {
-    const int nt = pde->time_order[c], nx0 = pde->space_order[c][0];
-    if (!sys_set_compiled(nt, nx0))
-      SYS_BAD("pinn_term_residual_system: field %d: axis-0 stream set (nt=%d, nx=%d) is not compiled", c, nt, nx0);
-    for (int a = 1; a < 3; ++a) {
-      const int so = pde->space_order[c][a];
-      if (so < 0 || so > (a < dim ? 2 : 0))
-        SYS_BAD("pinn_term_residual_system: field %d: space_order[%d] = %d outside [0, %d] (dimension %d)", c, a, so, a < dim ? 2 : 0, dim);
-    }
-    p.nt[c] = nt;
-    p.nx0[c] = nx0;
-    p.nx1[c] = pde->space_order[c][1];
-    p.nx2[c] = pde->space_order[c][2];
-  }
-  for (int e = 0; e < E; ++e) {
-    const float w = pde->eq_weight[e];
-    if (!std::isfinite(w) || w < 0.0f) SYS_BAD("pinn_term_residual_system: eq_weight[%d] = %g is negative or not finite", e, (double)w);
-    p.gw[e] = grad_scale * w;
-    p.w[e] = (double)w;
-  }
-  for (int m = 0; m < PINN_SYSTEM_MAX_TERMS; ++m) p.slots[m] = 0xffffffffu;
-  for (int m = 0; m < pde->n_terms; ++m) {
-    const PinnTermPdeTerm& tm = pde->terms[m];
-    const int eq = pde->equation_of[m];
-    if (eq < 0 || eq >= E) SYS_BAD("pinn_term_residual_system: equation_of[%d] = %d outside [0, %d)", m, eq, E);
-    if (tm.n_factors < 0 || tm.n_factors > PINN_TERM_MAX_FACTORS)
-      SYS_BAD("pinn_term_residual_system: term %d has n_factors %d outside [0, %d]", m, (int)tm.n_factors, PINN_TERM_MAX_FACTORS);
-    unsigned packed = 0xffffffffu;
-    for (int f = 0; f < tm.n_factors; ++f) {
-      const int byte = tm.factor[f];
-      if (byte < 0 || byte > 255) SYS_BAD("pinn_term_residual_system: term %d, factor %d: %d is not one byte (field * 32 + code)", m, f, byte);
-      const int code = byte & 31, field = byte >> 5;
-      int slot;
-      if (code == PINN_TERM_X || code == PINN_TERM_Y || code == PINN_TERM_Z || code == PINN_TERM_T) {  // the field bits are ignored
-        if ((code == PINN_TERM_Y && dim < 2) || (code == PINN_TERM_Z && dim < 3))
-          SYS_BAD("pinn_term_residual_system: term %d, factor %d names a coordinate (code %d) that dimension %d does not hold", m, f, code, dim);
-        p.uses_coord |= code == PINN_TERM_X ? USE_X : (code == PINN_TERM_Y ? USE_Y : (code == PINN_TERM_Z ? USE_Z : USE_T));
-        slot = kSyCoord + (code == PINN_TERM_X ? 0 : (code == PINN_TERM_Y ? 1 : (code == PINN_TERM_Z ? 2 : 3)));
-      } else {
-        const int vs = sys_value_slot(code);
-        if (vs < 0) SYS_BAD("pinn_term_residual_system: term %d, factor %d: unknown factor code %d (mixed derivatives are not available in systems)", m, f, code);
-        if (field >= C) SYS_BAD("pinn_term_residual_system: term %d, factor %d names field %d of %d", m, f, field, C);
-        bool held = true;
-        if (code < 7) held = sys_row0(code, p.nt[field], p.nx0[field]) >= 0;
-        else if (code == PINN_TERM_UY || code == PINN_TERM_UYY) held = p.nx1[field] >= code - PINN_TERM_UY + 1;
-        else if (code == PINN_TERM_UZ || code == PINN_TERM_UZZ) held = p.nx2[field] >= code - PINN_TERM_UZ + 1;
-        if (!held)
-          SYS_BAD("pinn_term_residual_system: term %d, factor %d names a stream (code %d) that field %d (nt=%d, space orders %d, %d, %d) does not hold",
-                  m, f, code, field, p.nt[field], p.nx0[field], p.nx1[field], p.nx2[field]);
-        if (vs == 7 || vs == 8) p.uses_trig[field] = 1;
-        slot = field * kSyVals + vs;
-      }
-      packed = (packed & ~(255u << (8 * f))) | ((unsigned)slot << (8 * f));
-    }
-    p.slots[m] = packed;
-    p.n_factors[m] = (unsigned char)tm.n_factors;
-    p.eq[m] = (unsigned char)eq;
-  }
-  if (N < 0) SYS_BAD("pinn_term_residual_system: N < 0");
-  if (N == 0) return PINN_OK;
-  if (!jets || !coef_values) SYS_BAD("pinn_term_residual_system: null jets table or coef_values");
-  for (int c = 0; c < C; ++c) {
-    const int so[3] = {1, p.nx1[c], p.nx2[c]};  // block (c, 0) always holds the value stream
-    for (int a = 0; a < 3; ++a) {
-      const bool need = a < dim && so[a] > 0;
-      p.jets[3 * c + a] = need ? jets[3 * c + a] : nullptr;
-      p.cot[3 * c + a] = (jet_cotangents && need) ? jet_cotangents[3 * c + a] : nullptr;
-      if (need && (!p.jets[3 * c + a] || (jet_cotangents && !p.cot[3 * c + a])))
-        SYS_BAD("pinn_term_residual_system: null block (field %d, axis %d) of the jets or jet_cotangents table", c, a);
-    }
-  }
-  if (((p.uses_coord & (USE_X | USE_Y | USE_Z)) && !x) || ((p.uses_coord & USE_T) && !t))
-    SYS_BAD("pinn_term_residual_system: a term names X / Y / Z / T but the coordinate array is null");
-  const bool reduce = loss_sum_out || eq_loss_sums || coef_grads;
-  if (reduce && !scratch) SYS_BAD("pinn_term_residual_system: null scratch with a loss or coefficient sum");
-#undef SYS_BAD
-  if (reinterpret_cast<uintptr_t>(scratch) & 7u)
-    return pinn_internal_fail(PINN_ERR_MISALIGNED, "pinn_term_residual_system: scratch must be 8-byte aligned");
-
-  long long nb = ((long long)N + 255) / 256;
-  const int blocks = (int)(nb > kSyBlocks ? kSyBlocks : nb);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool cs = coef_grads != nullptr;
-  switch (C) {
-    case 1: sys_launch<1>(reduce, cs, blocks, st, p, coef_values, x, t, (long long)N, residual_cotangent, residual_out, scratch); break;
-    case 2: sys_launch<2>(reduce, cs, blocks, st, p, coef_values, x, t, (long long)N, residual_cotangent, residual_out, scratch); break;
-    case 3: sys_launch<3>(reduce, cs, blocks, st, p, coef_values, x, t, (long long)N, residual_cotangent, residual_out, scratch); break;
-    default: sys_launch<4>(reduce, cs, blocks, st, p, coef_values, x, t, (long long)N, residual_cotangent, residual_out, scratch); break;
-  }
-  int rc = sys_launched("term_system_kernel");
-  if (rc || !reduce) return rc;
-  hipLaunchKernelGGL(term_system_finish_kernel, dim3(1), dim3(64), 0, st, scratch, blocks, E, (int)p.n_terms, p.w[0], p.w[1], p.w[2], p.w[3],
-                     loss_sum_out, eq_loss_sums, coef_grads);
-  return sys_launched("term_system_finish_kernel");
+  const SysCall a = {coef_values, jets, x, t, nullptr, nullptr, nullptr, (long long)N, grad_scale, residual_cotangent, residual_out,
+                     loss_sum_out, eq_loss_sums, jet_cotangents, coef_grads, nullptr, scratch, static_cast<hipStream_t>(stream)};
+  return sys_residual<PLAIN>("pinn_term_residual_system", pde, a);
 }

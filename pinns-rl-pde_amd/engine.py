@@ -1061,6 +1061,26 @@ def term_residual_system_mixed(td: MixedSystemTermDesc, jets: Sequence[Optional[
                                  loss_sum, want_cotangents, coef_grads, eq_loss_sums)
 
 
+def _check_fn_values(who: str, fn_values: Optional[Tensor], K: int) -> None:
+    """fn_values of a coupled-system call: a contiguous float32 (K, N) tensor, None only without functions."""
+    if fn_values is None:
+        if K:
+            raise ValueError(f"{who}: fn_values is None but the descriptor has {K} functions")
+    elif (fn_values.dim() != 2 or fn_values.shape[0] != K or fn_values.dtype != torch.float32 or not fn_values.is_contiguous()):
+        raise ValueError(f"{who}: fn_values must be a contiguous float32 ({K}, N) tensor "
+                         f"(got {fn_values.dtype} {tuple(fn_values.shape)})")
+
+
+def _check_nl_params(who: str, nl_params: Optional[Tensor], KN: int) -> None:
+    """nl_params of a coupled-system call: a contiguous float32 (KN, 3) tensor, None only without nonlinear functions."""
+    if nl_params is None:
+        if KN:
+            raise ValueError(f"{who}: nl_params is None but the descriptor has {KN} nonlinear functions")
+    elif tuple(nl_params.shape) != (KN, 3) or nl_params.dtype != torch.float32 or not nl_params.is_contiguous():
+        raise ValueError(f"{who}: nl_params must be a contiguous float32 ({KN}, 3) tensor "
+                         f"(got {nl_params.dtype} {tuple(nl_params.shape)})")
+
+
 def term_residual_system_fn(td: FnSystemTermDesc, jets: Sequence[Optional[Tensor]], fn_values: Optional[Tensor], x: Tensor, t: Tensor,
                             grad_scale: float = 0.0, residual_cotangent: Optional[Tensor] = None, want_residual: bool = True,
                             loss_sum: Optional[Tensor] = None, want_cotangents: bool = False, coef_grads: Optional[Tensor] = None,
@@ -1069,12 +1089,7 @@ def term_residual_system_fn(td: FnSystemTermDesc, jets: Sequence[Optional[Tensor
     contiguous float32 (len(td.functions), N) tensor on the device of the jets (`td.fn_values(x, t)`), row k function k; None
     only where the descriptor has no function.  The kernel reads it at launch time, and only the rows some term names."""
     K = len(td.functions)
-    if fn_values is None:
-        if K:
-            raise ValueError(f"term_residual_system_fn: fn_values is None but the descriptor has {K} functions")
-    elif (fn_values.dim() != 2 or fn_values.shape[0] != K or fn_values.dtype != torch.float32 or not fn_values.is_contiguous()):
-        raise ValueError(f"term_residual_system_fn: fn_values must be a contiguous float32 ({K}, N) tensor "
-                         f"(got {fn_values.dtype} {tuple(fn_values.shape)})")
+    _check_fn_values("term_residual_system_fn", fn_values, K)
     return _term_residual_system("term_residual_system_fn", True, td, jets, x, t, grad_scale, residual_cotangent, want_residual,
                                  loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=fn_values, with_fn=True)
 
@@ -1089,18 +1104,8 @@ def term_residual_system_nl(td: NlSystemTermDesc, jets: Sequence[Optional[Tensor
     {shift, scale, exponent} of function k; None only where the descriptor has no nonlinear function.  The kernel reads it at
     launch time, and only the rows of the functions it evaluates."""
     K, KN = len(td.functions), len(td.nonlinear)
-    if fn_values is None:
-        if K:
-            raise ValueError(f"term_residual_system_nl: fn_values is None but the descriptor has {K} functions")
-    elif (fn_values.dim() != 2 or fn_values.shape[0] != K or fn_values.dtype != torch.float32 or not fn_values.is_contiguous()):
-        raise ValueError(f"term_residual_system_nl: fn_values must be a contiguous float32 ({K}, N) tensor "
-                         f"(got {fn_values.dtype} {tuple(fn_values.shape)})")
-    if nl_params is None:
-        if KN:
-            raise ValueError(f"term_residual_system_nl: nl_params is None but the descriptor has {KN} nonlinear functions")
-    elif tuple(nl_params.shape) != (KN, 3) or nl_params.dtype != torch.float32 or not nl_params.is_contiguous():
-        raise ValueError(f"term_residual_system_nl: nl_params must be a contiguous float32 ({KN}, 3) tensor "
-                         f"(got {nl_params.dtype} {tuple(nl_params.shape)})")
+    _check_fn_values("term_residual_system_nl", fn_values, K)
+    _check_nl_params("term_residual_system_nl", nl_params, KN)
     return _term_residual_system("term_residual_system_nl", True, td, jets, x, t, grad_scale, residual_cotangent, want_residual,
                                  loss_sum, want_cotangents, coef_grads, eq_loss_sums, fn_values=fn_values, nl_params=nl_params,
                                  with_nl=True)
@@ -1117,18 +1122,8 @@ def term_residual_system_inv(td: InvSystemTermDesc, jets: Sequence[Optional[Tens
     descriptor has no parameter.  coef_grads[m] is the sum with respect to the EFFECTIVE coefficient;
     param_grads[p] += the derivative of the same scalar with respect to parameter p (>= n_params floats, accumulated)."""
     K, KN, P = len(td.functions), len(td.nonlinear), int(td.desc.n_params)
-    if fn_values is None:
-        if K:
-            raise ValueError(f"term_residual_system_inv: fn_values is None but the descriptor has {K} functions")
-    elif (fn_values.dim() != 2 or fn_values.shape[0] != K or fn_values.dtype != torch.float32 or not fn_values.is_contiguous()):
-        raise ValueError(f"term_residual_system_inv: fn_values must be a contiguous float32 ({K}, N) tensor "
-                         f"(got {fn_values.dtype} {tuple(fn_values.shape)})")
-    if nl_params is None:
-        if KN:
-            raise ValueError(f"term_residual_system_inv: nl_params is None but the descriptor has {KN} nonlinear functions")
-    elif tuple(nl_params.shape) != (KN, 3) or nl_params.dtype != torch.float32 or not nl_params.is_contiguous():
-        raise ValueError(f"term_residual_system_inv: nl_params must be a contiguous float32 ({KN}, 3) tensor "
-                         f"(got {nl_params.dtype} {tuple(nl_params.shape)})")
+    _check_fn_values("term_residual_system_inv", fn_values, K)
+    _check_nl_params("term_residual_system_inv", nl_params, KN)
     if param_values is None:
         if P:
             raise ValueError(f"term_residual_system_inv: param_values is None but the descriptor has {P} parameters")
