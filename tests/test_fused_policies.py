@@ -5,7 +5,9 @@ the full-depth / full-width parity tests run again in child processes with every
 LayerNorm node fused (kernels the default policy leaves to the unfused path must stay correct: they are selectable),
 and with the two GEMM-side choices of lm_engine.hip switched back (PINN_LM_WRES16, PINN_LM_NT_BATCH).  The variant matrix
 (test_lm_variants_gpu.py) runs again with everything unfused — the whole element-wise matrix — and with every LayerNorm
-node fused — the LayerNorm reverse epilogues at depth 256, which the default policy never launches.
+node fused — the LayerNorm reverse epilogues at depth 256, which the default policy never launches.  The chunk loop of
+lm_run, which the 1 GB record target never enters at test sizes, runs in children with PINN_LM_RECORD_MB=1: three networks
+through residual_loss_grad, and tests/lm_chunk_cases.py — every entry point, fused and unfused.
 
 A child that dies on a signal or runs into its time limit fails its test, and no later test of this file starts another
 child: what faulted the GPU once is not given a second process to fault."""
@@ -107,3 +109,35 @@ def test_multi_chunk_loop_of_the_layer_major_engine():
     e = dict(os.environ, PINN_LM_RECORD_MB="1")
     r = _run_child([sys.executable, "-c", _CHUNK_SCRIPT], e, 900)
     assert r.returncode == 0 and "multi-chunk ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+# Time limit of one child of test_chunk_loop_cases_under_policy.  Measured on the MI355X through this driver, start-up of the
+# child included: 7.9 s fused, 7.2 s unfused (the child of test_multi_chunk_loop_of_the_layer_major_engine: 3.2 s); three
+# times the slower one, rounded up to 10 s.
+CHUNK_CASES_TIMEOUT = 30
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env", [{"PINN_LM_RECORD_MB": "1"}, {"PINN_LM_RECORD_MB": "1", "PINN_LM_FUSED": "0"}],
+                         ids=["fused-grid", "element-wise-grid"])
+def test_chunk_loop_cases_under_policy(env):
+    """tests/lm_chunk_cases.py in a child process whose record target is 1 MB: every entry point of the layer-major engine
+    (jets_forward, jets_backward, jets_backward_inputs in three forms, residual_forward, residual_loss_grad with and without
+    coefficient sums, residual_loss_grad_inverse, residual_backward) over three chunks, a third chunk of one point and two
+    exact chunks, every case having first proved from pinn_workspace_bytes that its chunk is 64 tiles.  The default policy
+    sizes the fused kernels' grids by the chunk (fused_grid), PINN_LM_FUSED=0 the element-wise ones (ew_grid).  The module is
+    not collected by the ordinary run, so a case that silently does not run is a failure here: the child's summary line must
+    show exactly the declared number of cases passed and nothing else."""
+    import re
+
+    import lm_chunk_cases
+
+    e = dict(os.environ, **env)
+    r = _run_child([sys.executable, "-m", "pytest", "tests/lm_chunk_cases.py", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"],
+                   e, CHUNK_CASES_TIMEOUT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    summary = [line for line in r.stdout.splitlines() if re.search(r"\b\d+ passed\b", line)]
+    assert summary, r.stdout[-2000:]
+    counts = dict((what, int(n)) for n, what in re.findall(r"(\d+) ([a-z]+)", summary[-1].split(" in ")[0]))
+    counts.pop("warnings", None), counts.pop("warning", None)
+    assert counts == {"passed": lm_chunk_cases.N_CASES}, summary[-1]
